@@ -6,7 +6,11 @@ synthetic inputs (xequinet_amd/data/synthetic.py).
     python bench.py [--gpus N --steps K --warmup W] [--workload qm9_1024 | qm9_65536 | ...]     (N > 1: starts its N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR     (the last timed step's results as DIR/<name>.npy)
+    python bench.py ... --full                 (adds the one-at-a-time, host-launched and native-operator timings, the
+                                                per-kernel roofline and the CPU baseline)
 
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure is behind --full.
 One process per GPU; molecules are independent, so ranks never exchange data.
   * default (qm9_1024, BASELINE.json configs[1]): every rank evaluates its own 1024-molecule batch -- weak scaling.
   * --workload qm9_65536 (configs[4]): ONE 65536-molecule batch, cut into contiguous molecule ranges balanced on edge
@@ -32,6 +36,28 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s mea
 F32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, exact f32 (= the f32 vector rate)
 SHARDED = ("qm9_65536", "qm9_8192_sharded")   # workloads that are ONE batch sharded over the ranks (strong scaling); the second: the
                                                # 8192-molecule batch cut over the ranks, the size a one-card rehearsal of the sharded path can afford
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(out, directory, rank=0, world=1):
+    """Write the arrays of ``out`` (what the timed path handed back in its last step) as ``directory/<name>.npy``: floating
+    arrays in their own precision (float32 / float64), integer ones as float64; ``<name>_rank<r>.npy`` when several ranks
+    run.  Beyond this rank's share of DUMP_LIMIT_BYTES the same fixed, seeded sample of rows is kept from every array."""
+    arrays = {}
+    for k, v in out.items():
+        if not isinstance(v, torch.Tensor):
+            continue
+        a = v.detach().cpu()
+        a = a.double() if not a.is_floating_point() or a.dtype == torch.float64 else a.float()
+        arrays[k.replace("/", "_")] = a.numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES // world
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        if total > budget and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * budget / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(directory, f"{k}_rank{rank}.npy" if world > 1 else f"{k}.npy"), a)
 
 
 def _oracle_eval(orc, oracle, p, zz, pp):
@@ -147,7 +173,7 @@ def run_train(args, rank, world, dev, dtype, xdist):
     def step():
         d = {k: v for k, v in data.items() if not k.startswith("_")}
         d["pos"] = d["pos"].detach().clone()
-        return train.train_step(ddp, d, target, opt, weights)[0]
+        return train.train_step(ddp, d, target, opt, weights)
 
     for _ in range(max(args.warmup, 15 if args.forces else 5)):     # (the caching allocator of a new step shape settles in ~15 steps)
         step()
@@ -155,10 +181,12 @@ def run_train(args, rank, world, dev, dtype, xdist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, result = step()
     torch.cuda.synchronize()
     xdist.barrier()
     elapsed, edges_all = xdist.reduce_timing(time.perf_counter() - t0, float(n_edges), device=dev)
+    if args.dump_outputs:
+        dump_outputs({"loss": loss, **result}, args.dump_outputs, rank, world)
     if rank == 0:
         print(json.dumps({
             "metric": "training step: edges/sec, " + ("energy + forces loss (twice-differentiated pass)" if args.forces else "energy loss (native pass)"),
@@ -202,7 +230,7 @@ def main():
                     help="whole-step graph of an open-boundary batch: D steps in flight (runtime.GraphedStepsInFlight: D contexts with their own "
                          "buffers and captured graphs, each replayed on its own stream, in turn; every step's results are bit for bit those of "
                          "D = 1).  The K timed steps are still K whole steps, all finished before the clock stops; what overlaps is the "
-                         "front / the tails of one step with the body of the next.  D = 1: one step at a time (also reported by the default "
+                         "front / the tails of one step with the body of the next.  D = 1: one step at a time (also reported by a --full "
                          "run as ms_per_step_one_in_flight)")
     ap.add_argument("--train", action="store_true",
                     help="time ONE OPTIMISATION STEP per step instead of an inference step (SURVEY 8f-4; utils/trainer.py:290-308): forward in train "
@@ -214,7 +242,15 @@ def main():
                     help="feed K different draws of the workload in turn (different atom and edge counts every step) through the "
                          "one captured graph.  Default: as many draws as steps in flight (two contexts evaluate two different "
                          "batches: a stream of batches, not one batch twice), one draw with --in-flight 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also time the same step one at a time, with host launches and as the native operator "
+                         "(checked against the timed path), per kernel (the roofline figures) and on the CPU oracle (unless "
+                         "--no-cpu-baseline); with --eager the kernels are timed inside the timed region.  Off: only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.vary_batch < 0:   # (a sharded workload is ONE batch by definition: every step evaluates this rank's share of it)
         args.vary_batch = 1 if args.workload in SHARDED else max(1, args.in_flight)
 
@@ -407,7 +443,7 @@ def main():
     n_atoms = pos_d.shape[0]
 
     # ---- timed region: exactly K steps between barrier + synchronize
-    ops.KERNEL_TIMER.reset(enabled=args.eager)
+    ops.KERNEL_TIMER.reset(enabled=args.eager and args.full)
     xdist.barrier()
     torch.cuda.synchronize()
     if chunk_graphs:
@@ -433,20 +469,29 @@ def main():
     if chunk_graphs:
         edges_done = int(gchunks.edge_total.item())
         assert not gchunks.overflowed(), "a chunk's neighbour list outgrew its capacity"
-        if gchunks.depth > 1:                              # the same chunks one at a time
-            one = runtime.GraphedChunks(model, ptr, max_edges=max_edges, depth=1, compute_forces=True)
-            for _ in range(2):
-                one(pos_d, z_d, ptr_d, batch_d)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                one(pos_d, z_d, ptr_d, batch_d)
-            torch.cuda.synchronize()
-            one_ms = (time.perf_counter() - t1) / args.steps * 1e3
-            del one
     elif n_flight > 1:
         out = gstep.result(ticket[0])
         edges_timed = int(gstep.edge_total.item())
+    if whole_step:
+        edges_done = edges_timed if n_flight > 1 else int((gstep.edge_total if cell is None else edge_total).item())   # the device-side counts of the K timed steps
+        if cell is not None:
+            assert not gpbc.overflowed(), "the periodic list outgrew its capacity inside the timed region"
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, rank, world)
+    # ---- --full: everything past the headline figure
+    out_is_draw0 = max(1, args.vary_batch) == 1
+    if args.full and chunk_graphs and gchunks.depth > 1:   # the same chunks one at a time
+        one = runtime.GraphedChunks(model, ptr, max_edges=max_edges, depth=1, compute_forces=True)
+        for _ in range(2):
+            one(pos_d, z_d, ptr_d, batch_d)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            one(pos_d, z_d, ptr_d, batch_d)
+        torch.cuda.synchronize()
+        one_ms = (time.perf_counter() - t1) / args.steps * 1e3
+        del one
+    elif args.full and n_flight > 1:
         one = runtime.GraphedStep(model, cap, compute_forces=True)   # the same step, ONE at a time (its latency): a lone step's own capture
         p_k, z_k, ptr_k, _, b_k = draws[0]
         for _ in range(3):
@@ -459,17 +504,12 @@ def main():
         one_ms = (time.perf_counter() - t1) / args.steps * 1e3
         out = one(p_k, z_k, ptr_k, batch=b_k)             # draw 0 again: what the host-launched and native-operator runs below are checked against
         out_is_draw0 = True
-    if whole_step:
-        edges_done = edges_timed if n_flight > 1 else int((gstep.edge_total if cell is None else edge_total).item())   # the device-side counts of the K timed steps
-        if cell is not None:
-            assert not gpbc.overflowed(), "the periodic list outgrew its capacity inside the timed region"
     eager_ms = native_ms = None
-    out_is_draw0 = locals().get("out_is_draw0", False) or max(1, args.vary_batch) == 1
-    if args.eager:
+    kernel_ms, kernel_timing, cal = {}, None, args.steps      # (no per-kernel figures, hence no roofline, without --full)
+    if args.full and args.eager:
         kernel_ms = ops.KERNEL_TIMER.summary()       # HIP events recorded on the launch stream, in the timed region
         kernel_timing = "HIP events around every launch of the timed region, on the launch stream"
-        cal = args.steps
-    else:
+    elif args.full:
         # HIP offers no per-node event timing inside a graph launch on this stack (torch: "External events are disallowed
         # in rocm"), so the message kernels' launch durations are read right after the timed region: the same kernels on
         # the same inputs, launched from the host between HIP events on the launch stream
@@ -592,13 +632,15 @@ def main():
                                                 "traffic": traffic1}
 
         what = "ONE batch sharded by molecule over the GPUs" if sharded else "per GPU"
+        # None where a figure was not measured (the other forms of the step are timed by --full only)
+        one_at_a_time_ms = one_ms if one_ms is not None else (ms_per_step if n_flight == 1 else None)
         line = {
             "metric": METRIC, "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_per_step_eager": eager_ms if eager_ms is not None else ms_per_step,
-            "ms_per_step_native_op": native_ms, "ms_per_step_one_in_flight": one_ms if one_ms is not None else ms_per_step,
+            "ms_per_step": ms_per_step, "ms_per_step_eager": eager_ms if eager_ms is not None else (ms_per_step if args.eager else None),
+            "ms_per_step_native_op": native_ms, "ms_per_step_one_in_flight": one_at_a_time_ms,
             # the headline `value` is THROUGHPUT (edges/s of K whole steps between the two barriers) and, since round 5, is taken with
             # `in_flight` steps overlapped; the one-step-at-a-time figure (rounds 1-4's definition, a step's latency) stays next to it
-            "value_one_in_flight": (edges_total / args.steps) / ((one_ms if one_ms is not None else ms_per_step) * 1e-3) if world == 1 else None,
+            "value_one_in_flight": (edges_total / args.steps) / (one_at_a_time_ms * 1e-3) if world == 1 and one_at_a_time_ms else None,
             "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
             "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": f"{args.workload}: {syn.WORKLOADS[args.workload]} ({what}), 5 A cutoff, default XPaiNN (865141 params, "
@@ -619,7 +661,7 @@ def main():
                        "ms_per_step_native_op": "the same step as ONE registered operator (xeq::xpainn_eval: kernels enqueued from C++, no capture): what a stream of batches with ever-new edge counts pays"},
             "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(pos, z, ptr, sd)
         print(json.dumps(line), flush=True)
     if world > 1:

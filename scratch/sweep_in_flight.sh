@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box): scratch/sweep_in_flight.sh   -- the development knobs again with two steps in flight (bench default), one box
-run() { python bench.py --steps 40 --warmup 5 --no-cpu-baseline > /tmp/g.json 2>/dev/null; python - "$1" <<'PY'
+run() { python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline > /tmp/g.json 2>/dev/null; python - "$1" <<'PY'
 import json, sys
 d = json.load(open("/tmp/g.json"))
 print(f"{sys.argv[1]:44s} {d['ms_per_step']:.4f} ms   one at a time {d['ms_per_step_one_in_flight']:.4f} ms", flush=True)

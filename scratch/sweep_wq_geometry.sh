@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box): scratch/sweep_wq_geometry.sh   -- chunk geometry of the wq message kernels (development env knobs), one box
-run() { python bench.py --steps 30 --warmup 5 --no-cpu-baseline > /tmp/g.json 2>/dev/null; python - "$1" <<'PY'
+run() { python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > /tmp/g.json 2>/dev/null; python - "$1" <<'PY'
 import json, sys
 d = json.load(open("/tmp/g.json")); k = d["roofline"]["kernels_ms_per_step"]
 print(f"{sys.argv[1]:44s} {d['ms_per_step']:.4f} ms  " + "  ".join(f"{n.replace('xeq_message_','')} {v*1e3:.1f}" for n, v in k.items()))
