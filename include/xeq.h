@@ -654,6 +654,21 @@ int xeq_uv_reduce_fwd(int dtype, const void* uv_bt, int64_t n, const int32_t mul
 int xeq_uv_reduce_bwd(int dtype, const void* uv_bt, const void* g_p, const void* g_cat, int64_t ld_cat, int node_dim,
                       int64_t n, const int32_t mul[3], double eps, const void* g_x_out, const void* a, void* g_uv_bt,
                       void* stream);
+/* Charge / spin embeddings of XPaiNN (nn/electronic.py:13-90 with the bias-free ResidualLayer of nn/basic.py:11-31; inserted between
+ * the embedding and the first message block by nn/model.py:85-96), f32, csrc/xeq_electronic.hip.  kind 0: ChargeEmbedding, a_g =
+ * relu([t_g, -t_g]); kind 1: SpinEmbedding, a_g = [t_g]; total[G] (f32) holds t_g per graph.  With key_in = a_g / max(a_g, 1):
+ *   attn_n = softplus(<W_q s_n + b_q, W_k key_in(g(n))> / sqrt(F)),  c_n = attn_n (W_v a_g(n)) / sum_{m in g(n)} attn_m,
+ *   out_n = s_n + (c_n + SiLU(W_2 SiLU(W_1 c_n))) / sqrt(2).
+ * Two launches (xeq_electronic_attn, xeq_electronic_mix).  s [n, lds] (lds % 4 == 0), ptr [G + 1] (int64, graph g = atoms ptr[g] ..
+ * ptr[g + 1] - 1), wq_packed = xeq_mlp_pack(W_q, b_q, F, F, 0), w_k / w_v the nn.Linear weights [F, 2] (charge) or [F, 1] (spin),
+ * w1_packed / w2_packed = xeq_mlp_pack(residual.mlp.{0,2}.weight, NULL, F, F, 0); attn [n] is workspace; out [n, F] must not overlap s.
+ * The graph sums run in an order fixed by the graph's own atoms, without atomics: a molecule gets the same bits alone, in a batch or
+ * in a shard.  xeq_electronic_supported: f32, node_dim a multiple of 32, <= 256 (1 / 0, not a status). */
+int xeq_electronic_supported(int dtype, int node_dim);
+int xeq_electronic_fwd(int kind, const void* s, int64_t lds, int64_t n, int node_dim, const int64_t* ptr, int64_t n_graphs, const void* total,
+                       const void* wq_packed, const void* w_k, const void* w_v, const void* w1_packed, const void* w2_packed, void* attn,
+                       void* out, void* stream);
+
 /* Output stage of XPainnUpdate (nn/xpainn.py:218-229) with a = [a_vv C | a_sv F | a_ss F], ip = dot_lin(p):
  * s_out = s + a_sv*ip + a_ss, x_out = x + U (x) a_vv (x, x_out in e3nn layout; x_out may be NULL: not computed); and the reverse
  * (g_uv_bt may be NULL: dL/dU = g_x_out a_vv is then left to xeq_uv_reduce_bwd; g_x_out may be NULL: zero). */

@@ -462,7 +462,8 @@ void build_wq_plan(Graph& g, bool reverse, WqPlan& p) {
 }
 
 // ---------------------------------------------------------------------------------------------- model description
-// iparams: [node_dim, mul0, mul1, mul2, num_basis, n_blocks, rbf_kind, cutoff_kind, layer_norm, embed_kind, xhat_unused]
+// iparams: [node_dim, mul0, mul1, mul2, num_basis, n_blocks, rbf_kind, cutoff_kind, layer_norm, embed_kind(, charge_embed, spin_embed)]
+//   (the last two only for a model with a charge / spin embedding: lists without them describe a model without either)
 // fparams: [cutoff, invariant_eps]
 // params (flat, in this order; undefined-by-absence entries are passed as empty tensors):
 //   0 embed_table [87, A] (embed_kind 0) or embedding matrix [100, F] (embed_kind 1);  1 embed_w [F, A];  2 embed_b [F]
@@ -473,7 +474,9 @@ void build_wq_plan(Graph& g, bool reverse, WqPlan& p) {
 //     +14 dot_w [F, C]  +15 mlp3_w [F, F+C]  +16 mlp3_b  +17 mlp4_w [C+2F, F]  +18 mlp4_b  +19 ln_w  +20 ln_b  +21 eq_w  +22 eq_b
 //     (+23..26 reserved)
 //   tail: out0_w [Hd, F], out0_b, out2_w [1, Hd], out2_b
-constexpr int P_BLOCK0 = 5, P_PER_BLOCK = 27;
+//   then, per electronic module present (charge first, then spin; nn/electronic.py): linear_q.weight [F, F], linear_q.bias [F],
+//   linear_k.weight [F, 2|1], linear_v.weight [F, 2|1], residual.mlp.0.weight [F, F], residual.mlp.2.weight [F, F]
+constexpr int P_BLOCK0 = 5, P_PER_BLOCK = 27, P_ELECTRONIC = 6;
 struct Hyper {
   int F, mul[3], B, blocks, rbf_kind, cutoff_kind, layer_norm, embed_kind;
   double cutoff, inv_eps;
@@ -609,7 +612,8 @@ struct UpdSaved {
 std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_numbers, const Tensor& edge_index, const Tensor& ptr,
                                      const c10::optional<Tensor>& cell_o, const c10::optional<Tensor>& cell_offsets_o,
                                      const std::vector<Tensor>& prm, const std::vector<int64_t>& ip, const std::vector<double>& fp,
-                                     bool center_sorted, bool symmetric, bool compute_forces, bool compute_virial) {
+                                     bool center_sorted, bool symmetric, bool compute_forces, bool compute_virial,
+                                     const c10::optional<Tensor>& charge_o, const c10::optional<Tensor>& spin_o) {
   need_hip(pos_in, "pos");
   need_hip(edge_index, "edge_index");
   TORCH_CHECK(ip.size() >= 10 && fp.size() >= 2, "xeq::xpainn_eval: malformed hyper-parameter lists");
@@ -626,8 +630,10 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
   hy.embed_kind = (int)ip[9];
   hy.cutoff = fp[0];
   hy.inv_eps = fp[1];
-  TORCH_CHECK((int64_t)prm.size() == P_BLOCK0 + (int64_t)P_PER_BLOCK * hy.blocks + 4, "xeq::xpainn_eval: expected ",
-              P_BLOCK0 + P_PER_BLOCK * hy.blocks + 4, " parameter tensors, got ", prm.size());
+  // charge / spin embeddings (nn/electronic.py): flags at the end of iparams, parameters behind the head tail
+  const bool el_charge = ip.size() >= 12 && ip[10] != 0, el_spin = ip.size() >= 12 && ip[11] != 0;
+  const int64_t n_prm = P_BLOCK0 + (int64_t)P_PER_BLOCK * hy.blocks + 4 + P_ELECTRONIC * ((int)el_charge + (int)el_spin);
+  TORCH_CHECK((int64_t)prm.size() == n_prm, "xeq::xpainn_eval: expected ", n_prm, " parameter tensors, got ", prm.size());
   TORCH_CHECK(edge_index.dim() == 2 && edge_index.size(0) == 2 && edge_index.scalar_type() == at::kLong, "edge_index must be int64 [2, E]");
   const Tensor pos = pos_in.detach().contiguous();
   const auto fopt = pos.options();
@@ -637,6 +643,15 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
   const int32_t mul[3] = {hy.mul[0], hy.mul[1], hy.mul[2]};
   const Tensor ptr64 = ptr.to(at::kLong).contiguous();
   void* st = cur_stream();
+  // a module runs when the model has it AND the per-graph value is given (the module is the identity otherwise, electronic.py:31-32)
+  const bool run_charge = el_charge && charge_o.has_value() && charge_o->defined();
+  const bool run_spin = el_spin && spin_o.has_value() && spin_o->defined();
+  const bool run_el = run_charge || run_spin;
+  if (run_el) {
+    need_hip(run_charge ? *charge_o : *spin_o, run_charge ? "charge" : "spin");
+    TORCH_CHECK(dt == XEQ_F32 && xeq_electronic_supported(XEQ_F32, F), "xeq::xpainn_eval: the charge / spin embeddings run in f32 with "
+                "node_dim a multiple of 32, <= 256: use the Python modules");
+  }
 
   const Tensor ei_c = edge_index.contiguous();
   const int64_t E = ei_c.size(1);
@@ -679,8 +694,15 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
   Tensor x = at::zeros({N, D}, fopt);
   bool front_done = false;
   const bool z_int = atomic_numbers.scalar_type() == at::kInt || atomic_numbers.scalar_type() == at::kLong;
-  if (hy.embed_kind == 0 && hy.blocks > 0 && dt == XEQ_F32 && hy.layer_norm && hy.mul[0] == F && prm[0].scalar_type() == at::kFloat &&
-      prm[0].dim() == 2 && prm[0].stride(1) == 1 && prm[0].stride(0) % 4 == 0 && lin_pack(prm[1], prm[2]) != nullptr) {
+  const bool table_form = hy.embed_kind == 0 && hy.blocks > 0 && dt == XEQ_F32 && hy.layer_norm && hy.mul[0] == F &&
+                          prm[0].scalar_type() == at::kFloat && prm[0].dim() == 2 && prm[0].stride(1) == 1 && prm[0].stride(0) % 4 == 0 &&
+                          lin_pack(prm[1], prm[2]) != nullptr;
+  if (table_form && run_el) {
+    // behind a charge / spin embedding the first block's scalars no longer depend on the element alone: the node scalars are gathered
+    // from the per-element rows (nn/xpainn.py::XEmbedding.forward, ELEMENT_ROWS) and the first block takes its per-node launches
+    const ElementFront* ef = element_front(hy, prm[0], prm[1], prm[2], &prm[P_BLOCK0]);
+    s = ef->rows_s.index_select(0, (z_int ? atomic_numbers : atomic_numbers.to(at::kLong)));
+  } else if (table_form) {
     const ElementFront* ef = element_front(hy, prm[0], prm[1], prm[2], &prm[P_BLOCK0]);
     const Tensor z = (z_int ? atomic_numbers : atomic_numbers.to(at::kLong)).contiguous();
     MsgSaved& m = msv[0];
@@ -699,6 +721,31 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
     s = linear_fwd(prm[0], prm[1], prm[2], 0, &z32);   // table lookup + Linear in one launch (nn/xpainn.py::XEmbedding._embed)
   }
   else s = prm[0].index_select(0, atomic_numbers.to(at::kLong));
+
+  // ---- charge, then spin embedding (nn/electronic.py, csrc/xeq_electronic.hip): two launches each, before the first block
+  if (run_el) {
+    int64_t base = P_BLOCK0 + (int64_t)P_PER_BLOCK * hy.blocks + 4;
+    for (int kind = 0; kind < 2; ++kind) {
+      const bool has = kind == 0 ? el_charge : el_spin;
+      const bool run = kind == 0 ? run_charge : run_spin;
+      const Tensor* e = &prm[base];
+      if (has) base += P_ELECTRONIC;
+      if (!run) continue;
+      const Tensor total = (kind == 0 ? *charge_o : *spin_o).reshape({-1}).to(at::kFloat).contiguous();
+      TORCH_CHECK(total.numel() == G, "xeq::xpainn_eval: ", kind == 0 ? "charge" : "spin", " has ", total.numel(), " values for ", G, " graphs");
+      const LinPack* pq = lin_pack(e[0], e[1]);
+      const LinPack* p1 = lin_pack(e[4], Tensor());
+      const LinPack* p2 = lin_pack(e[5], Tensor());
+      TORCH_CHECK(pq && p1 && p2, "xeq::xpainn_eval: the electronic module's weights cannot be packed");
+      s = s.contiguous();
+      Tensor attn = at::empty({N}, fopt), s_out = at::empty({N, (int64_t)F}, fopt);
+      const Tensor wk = e[2].contiguous(), wv = e[3].contiguous();
+      XCALL(xeq_electronic_fwd(kind, s.data_ptr(), s.stride(0), N, F, (const int64_t*)ptr64.data_ptr(), G, total.data_ptr(),
+                               pq->fwd.data_ptr(), wk.data_ptr(), wv.data_ptr(), p1->fwd.data_ptr(), p2->fwd.data_ptr(), attn.data_ptr(),
+                               s_out.data_ptr(), st));
+      s = s_out;
+    }
+  }
   const Tensor& p0 = prm[3];
   const Tensor& p1 = prm[4];
 
@@ -1049,11 +1096,12 @@ class XpainnEvalFn : public torch::autograd::Function<XpainnEvalFn> {
   static variable_list forward(AutogradContext* ctx, const Tensor& pos, const Tensor& atomic_numbers, const Tensor& edge_index,
                                const Tensor& ptr, const c10::optional<Tensor>& cell, const c10::optional<Tensor>& cell_offsets,
                                std::vector<Tensor> prm, std::vector<int64_t> ip, std::vector<double> fp, bool center_sorted,
-                               bool symmetric, bool compute_forces, bool compute_virial) {
+                               bool symmetric, bool compute_forces, bool compute_virial, const c10::optional<Tensor>& charge,
+                               const c10::optional<Tensor>& spin) {
     at::AutoDispatchBelowADInplaceOrView guard;
     const bool need = compute_forces || pos.requires_grad();
     auto out = xpainn_eval_impl(pos, atomic_numbers, edge_index, ptr, cell, cell_offsets, prm, ip, fp, center_sorted, symmetric, need,
-                                compute_virial);
+                                compute_virial, charge, spin);
     ctx->save_for_backward({out[2], ptr});
     ctx->mark_non_differentiable({out[1], out[2], out[3]});
     return {out[0], out[1], out[2], out[3]};
@@ -1069,7 +1117,7 @@ class XpainnEvalFn : public torch::autograd::Function<XpainnEvalFn> {
       const Tensor per_atom = at::repeat_interleave(grads[0].reshape({-1}), counts, 0, N);
       g_pos = forces.neg() * per_atom.unsqueeze(1);
     }
-    variable_list r(13);
+    variable_list r(15);
     r[0] = g_pos;
     return r;
   }
@@ -1078,9 +1126,10 @@ class XpainnEvalFn : public torch::autograd::Function<XpainnEvalFn> {
 std::vector<Tensor> xpainn_eval(const Tensor& pos, const Tensor& atomic_numbers, const Tensor& edge_index, const Tensor& ptr,
                                 const c10::optional<Tensor>& cell, const c10::optional<Tensor>& cell_offsets, std::vector<Tensor> prm,
                                 std::vector<int64_t> ip, std::vector<double> fp, bool center_sorted, bool symmetric,
-                                bool compute_forces, bool compute_virial) {
+                                bool compute_forces, bool compute_virial, const c10::optional<Tensor>& charge,
+                                const c10::optional<Tensor>& spin) {
   return XpainnEvalFn::apply(pos, atomic_numbers, edge_index, ptr, cell, cell_offsets, prm, ip, fp, center_sorted, symmetric,
-                             compute_forces, compute_virial);
+                             compute_forces, compute_virial, charge, spin);
 }
 
 // open-boundary neighbour list; one device-to-host read of the edge count, as the reference's nonzero()
@@ -1206,7 +1255,7 @@ TORCH_LIBRARY(xeq, m) {
   m.def(
       "xpainn_eval(Tensor pos, Tensor atomic_numbers, Tensor edge_index, Tensor ptr, Tensor? cell, Tensor? cell_offsets, "
       "Tensor[] params, int[] iparams, float[] fparams, bool center_sorted, bool symmetric, bool compute_forces, "
-      "bool compute_virial) -> Tensor[]");
+      "bool compute_virial, Tensor? charge=None, Tensor? spin=None) -> Tensor[]");
   m.def("radius_graph(Tensor pos, Tensor ptr, float cutoff) -> (Tensor, Tensor)");
   m.def("radius_graph_pbc(Tensor pos, Tensor cell, Tensor pbc, float cutoff) -> (Tensor, Tensor, Tensor)");
   m.def("linear(Tensor x, Tensor W, Tensor? b) -> Tensor", linear_op);   // differentiable to every order (XeqLinearFn / XeqWGradFn)

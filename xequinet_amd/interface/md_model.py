@@ -65,7 +65,8 @@ class XPaiNNLMP(XPaiNN):
             # mirror); the engine's list (LAMMPS) promises nothing
             graph = data.get(keys.EDGE_GRAPH)
             out = self._native(pos, data[keys.ATOMIC_NUMBERS], data[keys.EDGE_INDEX], ptr, data.get(keys.CELL), data.get(keys.CELL_OFFSETS),
-                               graph is not None and graph.c_perm is None, graph is not None and graph.mirror_walk, compute_forces, compute_virial)
+                               graph is not None and graph.c_perm is None, graph is not None and graph.mirror_walk, compute_forces, compute_virial,
+                               data.get(keys.TOTAL_CHARGE), data.get(keys.TOTAL_SPIN))
             result = {keys.TOTAL_ENERGY: out[0], keys.ATOMIC_ENERGIES: out[1]}
             if compute_forces:
                 result[keys.FORCES] = out[2]

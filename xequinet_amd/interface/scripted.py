@@ -75,6 +75,11 @@ def _flatten_params(model) -> List[torch.Tensor]:
         out += [empty] * 4
     head = model.mods["output_energy"].out_mlp
     out += [head[0].weight, head[0].bias, head[2].weight, head[2].bias]
+    for name in ("charge_embedding", "spin_embedding"):   # behind the head tail, charge first (nn/electronic.py)
+        if name in model.mods:
+            e = model.mods[name]
+            out += [e.linear_q.weight, e.linear_q.bias, e.linear_k.weight, e.linear_v.weight, e.residual.mlp[0].weight,
+                    e.residual.mlp[2].weight]
     return [t.detach().to(dt).contiguous() for t in out]
 
 
@@ -89,6 +94,11 @@ class XPaiNNNative(nn.Module):
 
         if not isinstance(model, XPaiNN):
             raise TypeError("XPaiNNNative wraps an nn.XPaiNN")
+        electronic = [model.mods[k] for k in ("charge_embedding", "spin_embedding") if k in model.mods]
+        for e in electronic:
+            if not (isinstance(e.residual.mlp[1], nn.SiLU) and isinstance(e.residual.mlp[3], nn.SiLU)
+                    and lib.load().xeq_electronic_supported(lib.XEQ_F32, e.node_dim)):
+                raise NotImplementedError("xeq::xpainn_eval runs the charge / spin embeddings with SiLU and node_dim a multiple of 32, <= 256")
         emb, msg0, upd0 = model.mods["embedding"], model.mods["message_0"], model.mods["update_0"]
         for k, m in model.mods.items():
             if hasattr(m, "scalar_mlp") and not isinstance(m.scalar_mlp[1], nn.SiLU):
@@ -110,13 +120,17 @@ class XPaiNNNative(nn.Module):
         self.iparams: List[int] = [int(msg0.node_dim), int(mul[0]), int(mul[1]), int(mul[2]), int(msg0.num_basis), int(n_blocks),
                                    int(lib.RBF_KINDS[emb.rbf.kind]), int(lib.CUTOFF_KINDS[emb.cutoff_fn.kind]),
                                    int(isinstance(msg0.norm, nn.LayerNorm)), int(isinstance(emb.embedding, nn.Embedding))]
+        if electronic:   # the module flags go at the end, only for a model that has one (lists without them stay valid)
+            self.iparams += [int("charge_embedding" in model.mods), int("spin_embedding" in model.mods)]
         self.fparams: List[float] = [float(emb.cutoff_fn.cutoff), float(upd0.invariant.eps)]
         self.cutoff_radius: float = float(model.cutoff_radius)
 
     def forward(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, edge_index: torch.Tensor, ptr: torch.Tensor,
                 cell: Optional[torch.Tensor] = None, cell_offsets: Optional[torch.Tensor] = None, center_sorted: bool = False,
-                symmetric: bool = False, compute_forces: bool = True, compute_virial: bool = False) -> List[torch.Tensor]:
-        """-> [energy [G], atomic_energies [N], forces [N, 3] (empty unless asked), virial [G, 3, 3] (empty unless asked)]"""
+                symmetric: bool = False, compute_forces: bool = True, compute_virial: bool = False, charge: Optional[torch.Tensor] = None,
+                spin: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """-> [energy [G], atomic_energies [N], forces [N, 3] (empty unless asked), virial [G, 3, 3] (empty unless asked)].
+        ``charge`` / ``spin``: per-graph totals [G] for a model with a charge / spin embedding (ignored by a model without one)."""
         params: List[torch.Tensor] = []
         for i in range(len(self.offsets)):
             shape = self.shapes[i]
@@ -125,7 +139,7 @@ class XPaiNNNative(nn.Module):
                 n *= d
             params.append(self.flat[self.offsets[i]:self.offsets[i] + n].view(shape))
         return torch.ops.xeq.xpainn_eval(pos, atomic_numbers, edge_index, ptr, cell, cell_offsets, params, self.iparams,
-                                         self.fparams, center_sorted, symmetric, compute_forces, compute_virial)
+                                         self.fparams, center_sorted, symmetric, compute_forces, compute_virial, charge, spin)
 
 
 class XPaiNNLMPScript(nn.Module):
@@ -133,9 +147,12 @@ class XPaiNNLMPScript(nn.Module):
     ``forward(data, compute_forces, compute_virial) -> {energy, atomic_energies[, forces][, virial]}`` in LAMMPS units; ``data``
     holds ``atomic_numbers``, ``pos`` and the neighbour list LAMMPS built (``edge_index`` [+ ``cell``, ``cell_offsets``])."""
 
-    def __init__(self, model, unit_style: str = "metal") -> None:
+    def __init__(self, model, unit_style: str = "metal", net_charge: Optional[int] = None) -> None:
         super().__init__()
         self.core = XPaiNNNative(model)
+        # interface/jit_model.py:64-67: a fixed net charge handed to the charge embedding (data["charge"] / ["spin"] otherwise)
+        self.has_net_charge: bool = net_charge is not None
+        self.net_charge: int = 0 if net_charge is None else int(net_charge)
         units = get_default_units()
         lmp = keys.LAMMPS_UNIT_STYLE[unit_style]
         self.pos_unit_factor: float = float(unit_conversion(lmp[keys.POSITIONS], units[keys.POSITIONS]))
@@ -156,8 +173,16 @@ class XPaiNNLMPScript(nn.Module):
         if "cell" in data:
             cell = data["cell"]
             cell_offsets = data["cell_offsets"]
+        charge: Optional[torch.Tensor] = None
+        if self.has_net_charge:
+            charge = torch.tensor([self.net_charge], dtype=torch.long, device=pos.device)
+        elif "charge" in data:
+            charge = data["charge"]
+        spin: Optional[torch.Tensor] = None
+        if "spin" in data:
+            spin = data["spin"]
         out = self.core(pos, data["atomic_numbers"], data["edge_index"], ptr, cell, cell_offsets, False, False, compute_forces,
-                        compute_virial)
+                        compute_virial, charge, spin)
         result: Dict[str, torch.Tensor] = {"energy": out[0] * self.energy_unit_factor, "atomic_energies": out[1]}
         if compute_forces:
             result["forces"] = out[2] * self.forces_unit_factor
@@ -173,9 +198,11 @@ class XPaiNNGMXScript(nn.Module):
     ``single_radius_graph`` order and cell offsets, the same list the Python ``XPaiNNGMX`` searches, bit for bit --
     ``xeq::radius_graph`` for open boundaries."""
 
-    def __init__(self, model) -> None:
+    def __init__(self, model, net_charge: Optional[int] = None) -> None:
         super().__init__()
         self.core = XPaiNNNative(model)
+        self.has_net_charge: bool = net_charge is not None       # interface/jit_model.py:204-207
+        self.net_charge: int = 0 if net_charge is None else int(net_charge)
         units = get_default_units()
         self.pos_unit_factor: float = float(unit_conversion("nm", units[keys.POSITIONS]))
         self.energy_unit_factor: float = float(unit_conversion(units[keys.TOTAL_ENERGY], "kJ/mol"))
@@ -185,6 +212,9 @@ class XPaiNNGMXScript(nn.Module):
                 pbc: Optional[torch.Tensor] = None) -> torch.Tensor:
         pos = positions * self.pos_unit_factor
         ptr = torch.tensor([0, pos.shape[0]], dtype=torch.long, device=pos.device)
+        charge: Optional[torch.Tensor] = None
+        if self.has_net_charge:
+            charge = torch.tensor([self.net_charge], dtype=torch.long, device=pos.device)
         periodic = False
         if pbc is not None and box is not None:
             periodic = bool(pbc.any())
@@ -194,22 +224,23 @@ class XPaiNNGMXScript(nn.Module):
             with torch.no_grad():
                 edge_index, cell_offsets, _ = torch.ops.xeq.radius_graph_pbc(pos, cell, pbc, self.cutoff_radius)
             # (this package's own periodic search: center-sorted, every edge with its mirror image -- the operator's mirror map)
-            out = self.core(pos, atomic_numbers, edge_index, ptr, cell.unsqueeze(0), cell_offsets, True, True, False, False)
+            out = self.core(pos, atomic_numbers, edge_index, ptr, cell.unsqueeze(0), cell_offsets, True, True, False, False, charge)
         else:
             with torch.no_grad():
                 edge_index, _ = torch.ops.xeq.radius_graph(pos, ptr, self.cutoff_radius)
-            out = self.core(pos, atomic_numbers, edge_index, ptr, None, None, True, True, False, False)
+            out = self.core(pos, atomic_numbers, edge_index, ptr, None, None, True, True, False, False, charge)
         return out[0] * self.energy_unit_factor
 
 
 def compile_model(model, mode: str = "lmp", unit_style: str = "metal", output_file: Optional[str] = None,
-                  fusion_strategy: str = "DYNAMICS,3"):
+                  fusion_strategy: str = "DYNAMICS,3", net_charge: Optional[int] = None):
     """run/jit_script.py:28-86 for a built model: script the MD front end and (with ``output_file``) save it with the
-    reference's ``_extra_files`` (cutoff radius in engine units, fusion strategy, number of species, periodic table)."""
+    reference's ``_extra_files`` (cutoff radius in engine units, fusion strategy, number of species, periodic table).  ``net_charge``:
+    the fixed total charge the front hands to a model with a charge embedding (run/jit_script.py passes it to the fronts)."""
     if mode == "lmp":
-        front = XPaiNNLMPScript(model, unit_style=unit_style)
+        front = XPaiNNLMPScript(model, unit_style=unit_style, net_charge=net_charge)
     elif mode == "gmx":
-        front = XPaiNNGMXScript(model)
+        front = XPaiNNGMXScript(model, net_charge=net_charge)
     else:
         raise NotImplementedError(f"Unsupported mode {mode}")
     scripted = torch.jit.script(front.eval())

@@ -35,6 +35,7 @@ VIRIAL: Final[str] = "virial"
 ENERGY_PER_ATOM: Final[str] = "energy/atom"     # loss-only property (utils/loss.py:59-67)
 
 TOTAL_CHARGE: Final[str] = "charge"
+TOTAL_SPIN: Final[str] = "spin"
 
 GRAD_PROPERTIES: Final[Set[str]] = {FORCES, VIRIAL}
 

@@ -2,6 +2,7 @@
 factory -- host-side mirror of the reference's ``xequinet/nn/basic.py``."""
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -36,6 +37,22 @@ class Int2c1eEmbedding(nn.Module):
 
     def forward(self, at_no: torch.Tensor) -> torch.Tensor:
         return self.embed_ten[at_no.long()]
+
+
+class ResidualLayer(nn.Module):
+    """nn/basic.py:11-31: x -> (x + MLP(x)) / sqrt(2), the MLP n_layers x (bias-free Linear(node_dim, node_dim), activation)."""
+
+    def __init__(self, node_dim: int = 128, n_layers: int = 2, activation: str = "silu") -> None:
+        super().__init__()
+        act_fn = resolve_activation(activation)
+        self.mlp = nn.Sequential()
+        for _ in range(n_layers):
+            self.mlp.append(nn.Linear(node_dim, node_dim, bias=False))
+            self.mlp.append(act_fn)
+        self.inv_sqrt_2 = 1 / math.sqrt(2)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.inv_sqrt_2 * (x + self.mlp(x))
 
 
 def edge_graph(data: Dict[str, torch.Tensor]) -> ops.EdgeGraph:

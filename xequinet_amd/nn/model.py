@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from . import training
 from .basic import compute_edge_data, compute_properties
+from .electronic import ChargeEmbedding, SpinEmbedding
 from .output import resolve_output
 from .xpainn import XEmbedding, XPainnMessage, XPainnUpdate
 
@@ -80,7 +81,7 @@ class BaseModel(nn.Module):
 
 
 class XPaiNN(BaseModel):
-    """eXtended PaiNN (nn/model.py:49-122); charge/spin embeddings are off-path."""
+    """eXtended PaiNN (nn/model.py:49-122), with the optional charge / spin embeddings (nn/electronic.py)."""
 
     def __init__(self, **kwargs) -> None:
         super().__init__()
@@ -98,14 +99,16 @@ class XPaiNN(BaseModel):
         charge_embed: bool = kwargs.get("charge_embed", False)
         spin_embed: bool = kwargs.get("spin_embed", False)
         output_modes: Union[str, List[str]] = kwargs.get("output_modes", ["energy"])
-        if charge_embed or spin_embed:
-            raise NotImplementedError("charge/spin embeddings are outside the energy+force hot path (SURVEY 2)")
 
         self.cutoff_radius = cutoff
         self.mods["embedding"] = XEmbedding(
             node_dim=node_dim, node_irreps=node_irreps, embed_basis=embed_basis, aux_basis=aux_basis,
             num_basis=num_basis, rbf_kernel=rbf_kernel, cutoff=cutoff, cutoff_fn=cutoff_fn,
         )
+        if charge_embed:   # nn/model.py:85-96: charge before spin, both between the embedding and the first message block
+            self.mods["charge_embedding"] = ChargeEmbedding(node_dim=node_dim, activation=activation)
+        if spin_embed:
+            self.mods["spin_embedding"] = SpinEmbedding(node_dim=node_dim, activation=activation)
         for i in range(action_blocks):
             self.mods[f"message_{i}"] = XPainnMessage(
                 node_dim=node_dim, node_irreps=node_irreps, num_basis=num_basis, activation=activation, layer_norm=layer_norm,
@@ -113,7 +116,9 @@ class XPaiNN(BaseModel):
             self.mods[f"update_{i}"] = XPainnUpdate(
                 node_dim=node_dim, node_irreps=node_irreps, activation=activation, layer_norm=layer_norm,
             )
-        if action_blocks > 0:                # the embedding gathers the first message block's front half with the node scalars
+        # the embedding gathers the first message block's front half with the node scalars -- not behind a charge / spin embedding:
+        # there the first block's scalars no longer depend on the element alone (the block still sees the zero-equivariant tag)
+        if action_blocks > 0 and not (charge_embed or spin_embed):
             self.mods["embedding"]._next_message = [self.mods["message_0"]]
         for i in range(action_blocks - 1):   # an update block launches the front half of the message block behind it (nn/fused.py::NodeBlock)
             self.mods[f"update_{i}"]._next_message = [self.mods[f"message_{i + 1}"]]

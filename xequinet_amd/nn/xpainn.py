@@ -225,7 +225,7 @@ class XPainnMessage(nn.Module):
 
             front = first_block_front(self, elem[0], elem[1], ori_scalar.shape[0])
             if front is not None:   # norms and scalar_mlp of the first block from the element table: the message kernel alone is left
-                pre = (ori_scalar, ori_equi, front[0], front[1], ops.lib.XHAT_HIGHER_L_ZERO)
+                pre = (ori_scalar, ori_equi, front[1], front[2], ops.lib.XHAT_HIGHER_L_ZERO)   # front = (s, h, xhat)
         if self.fused and pre is not None and pre[0] is ori_scalar and pre[1] is ori_equi and not data.get(training.PARAM_GRADS, False):
             # norms and scalar_mlp came out of the update block's launch: the message kernel alone is left (nn/fused.py::NodeBlock)
             p0, p1 = rbf.params()

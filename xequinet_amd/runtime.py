@@ -36,6 +36,20 @@ class _Captured:
         self.outputs_same: Dict[str, torch.Tensor] = {}
 
 
+def refuse_electronic(model, who: str) -> None:
+    """The whole-step and capacity-sized capture classes take no charge / spin input: a model with a charge or spin embedding
+    (nn/electronic.py) would silently evaluate the neutral, spin-free molecule there, so it is refused."""
+    m = model
+    while not isinstance(m, torch.nn.Module) and hasattr(m, "model"):    # a plain callable around a module (md_model._Core)
+        m = m.model
+    if isinstance(m, torch.nn.Module):
+        from .nn.electronic import ChargeEmbedding, SpinEmbedding
+
+        if any(isinstance(x, (ChargeEmbedding, SpinEmbedding)) for x in m.modules()):
+            raise ValueError(f"{who} takes no charge / spin input: a model with a charge or spin embedding is refused "
+                             "(use GraphedModel, which captures data['charge'] / data['spin'], or the eager model)")
+
+
 class GraphedModel:
     """``GraphedModel(model)(data) -> {energy, atomic_energies, forces[, virial]}`` with HIP-graph replay.
 
@@ -44,6 +58,8 @@ class GraphedModel:
     next call with the same signature: clone what must outlive it."""
 
     _TENSOR_KEYS = (keys.POSITIONS, keys.ATOMIC_NUMBERS, keys.EDGE_INDEX, keys.BATCH, keys.BATCH_PTR, keys.CELL, keys.CELL_OFFSETS)
+    # per-graph inputs of the charge / spin embeddings (nn/electronic.py): captured and copied in like `pos` when present
+    _ELECTRONIC_KEYS = (keys.TOTAL_CHARGE, keys.TOTAL_SPIN)
 
     def __init__(self, model: torch.nn.Module, compute_forces: bool = True, compute_virial: bool = False,
                  max_graphs: int = 8, warmup: int = 2, tune_gemms: bool = True, reuse_unchanged_topology: bool = False) -> None:
@@ -84,8 +100,10 @@ class GraphedModel:
 
     def _signature(self, data, eg: ops.EdgeGraph) -> tuple:
         pos = data[keys.POSITIONS]
-        return (tuple(pos.shape), pos.dtype, pos.device.index, int(data[keys.EDGE_INDEX].shape[1]),
-                int(data[keys.BATCH_PTR].numel()), keys.CELL in data, eg.c_perm is None, eg.mirror_walk, eg.periodic)
+        sig = (tuple(pos.shape), pos.dtype, pos.device.index, int(data[keys.EDGE_INDEX].shape[1]),
+               int(data[keys.BATCH_PTR].numel()), keys.CELL in data, eg.c_perm is None, eg.mirror_walk, eg.periodic)
+        el = tuple((k, data[k].dtype, data[k].numel()) for k in self._ELECTRONIC_KEYS if k in data)
+        return sig + (el,) if el else sig
 
     @staticmethod
     def _edge_graph(data) -> ops.EdgeGraph:
@@ -104,7 +122,7 @@ class GraphedModel:
 
     def _capture(self, data, eg: ops.EdgeGraph) -> _Captured:
         c = _Captured()
-        c.inputs = {k: data[k].clone() for k in self._TENSOR_KEYS if k in data}
+        c.inputs = {k: data[k].clone() for k in self._TENSOR_KEYS + self._ELECTRONIC_KEYS if k in data}
         c.derived_batch = keys.BATCH not in c.inputs
         if c.derived_batch:
             ptr = c.inputs[keys.BATCH_PTR]
@@ -205,7 +223,7 @@ class GraphedModel:
         ei, ref = data[keys.EDGE_INDEX], c.inputs[keys.EDGE_INDEX]
         if ei.shape != ref.shape or ei.dtype != ref.dtype:
             return False
-        for k in (keys.POSITIONS, keys.ATOMIC_NUMBERS, keys.BATCH_PTR, keys.CELL_OFFSETS, keys.CELL) + (() if c.derived_batch else (keys.BATCH,)):
+        for k in (keys.POSITIONS, keys.ATOMIC_NUMBERS, keys.BATCH_PTR, keys.CELL_OFFSETS, keys.CELL, *GraphedModel._ELECTRONIC_KEYS) + (() if c.derived_batch else (keys.BATCH,)):
             if (k in data) != (k in c.inputs) or (k in data and (data[k].shape != c.inputs[k].shape or data[k].dtype != c.inputs[k].dtype)):
                 return False
         # one launch and one read-back for all of them (ops.any_differs): the list itself; ptr when the graph index was derived from it;
@@ -275,6 +293,7 @@ class GraphedStep:
 
     def __init__(self, model: torch.nn.Module, capacity, cutoff: Optional[float] = None, compute_forces: bool = True, warmup: int = 2,
                  device=None, dtype=None) -> None:
+        refuse_electronic(model, "GraphedStep")
         self.model = model
         self.n_atoms, self.n_graphs, self.n_edges = (int(c) for c in capacity)
         self.n_graphs += 1                                   # + the padding graph
@@ -416,6 +435,7 @@ class GraphedLanes:
 
     def __init__(self, model: torch.nn.Module, capacity, lanes: int = 2, cutoff: Optional[float] = None, compute_forces: bool = True,
                  warmup: int = 2, slack: float = 0.15) -> None:
+        refuse_electronic(model, "GraphedLanes")
         from . import lib
 
         assert 2 <= lanes <= lib.COPY_MANY_MAX // 3
@@ -547,6 +567,7 @@ class GraphedStepsInFlight:
     NODE_BLOCK_WAVES = 4
 
     def __init__(self, model: torch.nn.Module, capacity, depth: int = 2, **kw) -> None:
+        refuse_electronic(model, "GraphedStepsInFlight")
         assert depth >= 1
         self.depth = int(depth)
         self.steps = [GraphedStep(model, capacity, **kw) for _ in range(self.depth)]
@@ -645,6 +666,7 @@ class GraphedChunks:
     ``ptr_host``: the batch's graph pointer on the host (sizes the chunks once; a batch with another pointer needs another object)."""
 
     def __init__(self, model: torch.nn.Module, ptr_host, max_edges: int = None, depth: int = 2, compute_forces: bool = True) -> None:
+        refuse_electronic(model, "GraphedChunks")
         import numpy as np
 
         from .dist import plan_chunks
@@ -777,6 +799,7 @@ class GraphedStepPBC:
                  compute_forces: bool = True, warmup: int = 2) -> None:
         """``model``: a BaseModel, or any callable ``(data, compute_forces, compute_virial) -> results`` that wraps one in ``.model``
         (the MD front ends' unit-free core)."""
+        refuse_electronic(model, "GraphedStepPBC")
         self.model = model
         net = model if isinstance(model, torch.nn.Module) else model.model
         self.n_atoms, self.n_edges = int(n_atoms), int(edge_capacity)

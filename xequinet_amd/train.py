@@ -106,6 +106,7 @@ class GraphedTrainStep:
                  forces_weight: Optional[float] = None, grad_clip: Optional[float] = None, ema_decay: Optional[float] = None) -> None:
         from . import runtime
 
+        runtime.refuse_electronic(model, "GraphedTrainStep")
         if prop not in (keys.TOTAL_ENERGY, keys.ENERGY_PER_ATOM):
             raise ValueError("GraphedTrainStep captures an energy loss (energy or energy_per_atom)")
         if loss_fn.lower() not in ("l2", "mse", "l1", "mae"):
