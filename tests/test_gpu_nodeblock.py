@@ -89,12 +89,12 @@ def _modules(seed):
     return upd, msg
 
 
-def _reference(upd, msg, s, x):
-    """f64 restatement with the oracle's operator definitions."""
+def _reference(upd, msg, s, x, dtype=torch.float64):
+    """f64 restatement with the oracle's operator definitions (``dtype``: the same restatement in another precision, on the CPU)."""
     from oracle import xpainn_oracle as orc
 
-    sd = {k: v.detach().double().cpu() for k, v in upd.state_dict().items()}
-    s, x = s.double().cpu(), x.double().cpu()
+    sd = {k: v.detach().to(dtype).cpu() for k, v in upd.state_dict().items()}
+    s, x = s.to(dtype).cpu(), x.to(dtype).cpu()
     n = s.shape[0]
     out = {}
     mean = s.mean(1)
@@ -103,7 +103,7 @@ def _reference(upd, msg, s, x):
     mean0 = x0.mean(1)
     xc = x.clone()
     xc[:, :MUL[0]] -= mean0[:, None]
-    sq = torch.zeros(n, dtype=torch.float64)
+    sq = torch.zeros(n, dtype=dtype)
     off = 0
     for l, mul in enumerate(MUL):
         d = 2 * l + 1
@@ -128,7 +128,7 @@ def _reference(upd, msg, s, x):
     x2 = x + orc.elementwise_tp(IRREPS, U, a_vv)
     out["s_out"], out["x_out"] = s2, x2
     if msg is not None:
-        md = {k: v.detach().double().cpu() for k, v in msg.state_dict().items()}
+        md = {k: v.detach().to(dtype).cpu() for k, v in msg.state_dict().items()}
         shat2 = F_.layer_norm(s2, (F,), md["norm.weight"], md["norm.bias"], 1e-5)
         out["xhat2"] = orc.equivariant_layer_norm(IRREPS, x2, md["o3norm.affine_weight"], md["o3norm.affine_bias"])
         pre2 = F_.linear(shat2, md["scalar_mlp.0.weight"], md["scalar_mlp.0.bias"])
@@ -192,11 +192,12 @@ def test_node_block_forward_rows_do_not_depend_on_the_batch():
         assert torch.equal(nodeblock.native_to_rows(full[k], 300, width)[37:171], nodeblock.native_to_rows(part[k], 134, width)), k
 
 
-def _reference_diff(upd, msg, s, x):
-    """The same restatement as a differentiable f64 function of (s, x) -> (s_out, x_out[, h2, xhat2 (e3nn layout)])."""
+def _reference_diff(upd, msg, s, x, dtype=torch.float64):
+    """The same restatement as a differentiable f64 function of (s, x) -> (s_out, x_out[, h2, xhat2 (e3nn layout)]);
+    ``dtype``: the precision of the weights (s, x are taken as given)."""
     from oracle import xpainn_oracle as orc
 
-    sd = {k: v.detach().double().cpu() for k, v in upd.state_dict().items()}
+    sd = {k: v.detach().to(dtype).cpu() for k, v in upd.state_dict().items()}
     shat = F_.layer_norm(s, (F,), sd["norm.weight"], sd["norm.bias"], 1e-5)
     xhat = orc.equivariant_layer_norm(IRREPS, x, sd["o3norm.affine_weight"], sd["o3norm.affine_bias"])
     U = orc.o3_linear(IRREPS, xhat, sd["update_U.weight"], sd["update_U.bias"])
@@ -210,7 +211,7 @@ def _reference_diff(upd, msg, s, x):
     x2 = x + orc.elementwise_tp(IRREPS, U, a_vv)
     if msg is None:
         return s2, x2
-    md = {k: v.detach().double().cpu() for k, v in msg.state_dict().items()}
+    md = {k: v.detach().to(dtype).cpu() for k, v in msg.state_dict().items()}
     shat2 = F_.layer_norm(s2, (F,), md["norm.weight"], md["norm.bias"], 1e-5)
     xhat2 = orc.equivariant_layer_norm(IRREPS, x2, md["o3norm.affine_weight"], md["o3norm.affine_bias"])
     h2 = F_.linear(F_.silu(F_.linear(shat2, md["scalar_mlp.0.weight"], md["scalar_mlp.0.bias"])), md["scalar_mlp.2.weight"],

@@ -1,7 +1,11 @@
 """The few-row forms of the node-side products (csrc/xeq_linear.hip k_linear_s, ...): 16 x 16 exact-f32 tiles for systems that do not
 fill the chip (MD-sized: interface/jit_model.py:148-216).  An exact-f32 matrix instruction is a chain of fused multiply-adds in k
 order whatever its tile shape, so the forms must agree BIT FOR BIT with the 32-row forms: the row count picks a form, never a result
-(sharded == unsharded across the size threshold)."""
+(sharded == unsharded across the size threshold).
+
+The bit-equality checked here is a SELF-comparison (one form of this library against another); the products are otherwise compared
+only to 1e-4 (1 + max).  Parity of the few-row forms with the f64 oracle comes from
+tests/test_gpu_tile_edges.py::test_few_row_forms_against_the_oracle (forms forced on for every row count just below the row limit)."""
 import os
 
 import pytest
@@ -135,7 +139,8 @@ def test_update_block_few_row_forms_change_no_bit(n, irreps, layer_norm):
 @pytest.mark.parametrize("system", ["aspirin", "qm9_8", "qm9_64", "qm9_230"])
 def test_whole_evaluation_does_not_depend_on_the_few_row_forms(system):
     """Energies and forces of MD-sized systems (interface/jit_model.py:148-216) with every few-row form on against all of them off: bit for bit, eager and through the captured whole step.
-    qm9_230 (4.1 k atoms) lies across the forms' row limit: a batch and its shards take different forms and still agree."""
+    qm9_230 (4.1 k atoms) lies across the forms' row limit: a batch and its shards take different forms and still agree.
+    A self-comparison: the oracle comparison of both settings is tests/test_gpu_tile_edges.py::test_few_row_forms_against_the_oracle."""
     from tests.test_gpu_parity import _build, _t
     from xequinet_amd import runtime
     from xequinet_amd.data import NeighborTransform, XequiBatch
