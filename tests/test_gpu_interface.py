@@ -1,6 +1,7 @@
 """GPU parity of the MD front ends: the LAMMPS / GROMACS models and the ASE calculator against the
 CPU oracle evaluated in the model's own units and converted with the golden unit factors.  Run:  pytest tests -m gpu"""
 import json
+import math
 import os
 
 import numpy as np
@@ -766,3 +767,38 @@ def test_any_differs_compares_several_pairs_in_one_launch():
     assert ops.any_differs([(a, a[:, :-1])]) and ops.any_differs([(c, c.to(torch.int32))])
     assert not ops.any_differs([(a, a), (torch.empty(0, device="cuda"), torch.empty(0, device="cuda"))])
     assert ops.any_differs([(a.t(), a2.t())]) and not ops.any_differs([(a.t(), a.clone().t())])    # non-contiguous: torch.equal
+
+
+@pytest.mark.parametrize("n_mol", [24, 400])
+def test_native_operator_packs_follow_the_weights(n_mol):
+    """xeq::xpainn_eval keeps no packed copy past a change of a weight it was made from: one weight per pack cache of csrc/xeq_torch.cpp is
+    modified in place, and the next evaluation equals, bit for bit, one on freshly allocated tensors with the same values.  The parameters
+    are XPaiNNNative's, each in a tensor of its own (the views of the module's flat buffer share ONE version counter: a change of any
+    of them would make every cache miss, and the test would not tell the caches apart).  24 molecules: the chain of small node kernels
+    (MLP, linear, U / V and element-table packs); 400: the fused node blocks and the wq message kernels (their weight programs)."""
+    from xequinet_amd.data import NeighborTransform, XequiBatch
+    from xequinet_amd.interface.scripted import XPaiNNNative
+
+    model, _ = P._build(torch.float32)
+    native = XPaiNNNative(model)
+    pos, z, ptr = syn.synth_qm9_batch(n_mol, seed=13)
+    data = NeighborTransform(5.0)(XequiBatch(P._t(pos, torch.float32), P._t(z), P._t(ptr))).to_dict()
+    prm = [native.flat[o:o + math.prod(shape)].view(shape).clone() for o, shape in zip(native.offsets, native.shapes)]
+
+    def evaluate(params):
+        return torch.ops.xeq.xpainn_eval(data["pos"].detach(), data["atomic_numbers"], data["edge_index"], data["ptr"], None, None, params,
+                                         native.iparams, native.fparams, True, True, True, False, None, None)
+
+    evaluate(prm)
+    blk0, blk1, head = 5, 5 + 27, 5 + 27 * native.iparams[5]      # the parameter layout of csrc/xeq_torch.cpp
+    sites = {"embedding weight (element table front)": 1, "block 0 scalar_mlp.0.bias (element table front)": blk0 + 1,
+             "block 1 scalar_mlp.2.weight (MLP pack / node block program)": blk1 + 2, "block 1 rbf_lin.weight (wq weight pack)": blk1 + 4,
+             "block 0 U|V pack l=1 (U / V pack / node block program)": blk0 + 11, "block 0 U|V bias (U / V pack / node block bias)": blk0 + 13,
+             "block 0 dot_lin.weight (linear pack / node block program)": blk0 + 14, "block 0 update_mlp.0.weight (MLP pack / node block program)": blk0 + 15,
+             "block 0 update_mlp.2.bias": blk0 + 18, "head.0.weight (linear pack)": head, "head.0.bias (linear pack)": head + 1}
+    for name, i in sites.items():
+        with torch.no_grad():
+            prm[i].mul_(1.25).add_(0.01)
+        got, want = evaluate(prm), evaluate([t.clone() for t in prm])
+        for k in range(3):
+            assert torch.equal(got[k], want[k]), f"after a change of {name}: output {k} differs by {(got[k] - want[k]).abs().max().item():.2e}"

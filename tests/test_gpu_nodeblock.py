@@ -324,3 +324,47 @@ def test_node_block_results_do_not_depend_on_the_waves_per_workgroup(n, monkeypa
     for other in (again, outs["4"], outs["8"]):
         for a, b in zip(auto, other):
             assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("how", ["in_place", "new_storage"])
+def test_packs_follow_every_weight_that_feeds_them(how):
+    """No packed copy outlives a change of a weight it was made from: after every single change -- in place (the version counter moves)
+    or as a new storage under the same parameter (the address moves) -- an update block + next message block pair gives, bit for bit,
+    what a freshly constructed pair holding the same weights gives.  Both the fused node block and the update block's own kernels."""
+    from xequinet_amd.nn import fused
+
+    dev = _dev()
+    n = 4100
+    upd, msg = (m.to(dev).eval().requires_grad_(False) for m in _modules(5))
+    D = upd.node_irreps.dim
+    g = torch.Generator().manual_seed(0)
+    s0, x0 = torch.randn(n, F, generator=g).to(dev), torch.randn(n, D, generator=g).to(dev)
+    g_out = [torch.randn(*shape, generator=g).to(dev) for shape in ((n, F), (n, D), (n, msg.hidden_dim), (n * D,))]
+
+    def evaluate(u, m):
+        s, x = s0.clone().requires_grad_(True), x0.clone().requires_grad_(True)
+        with torch.enable_grad():
+            block = fused.NodeBlock.apply(s, x, u, m)
+            g_block = torch.autograd.grad(block, [s, x], g_out)
+            chain = fused.UpdateBlock.apply(s, x, u)
+            g_chain = torch.autograd.grad(chain, [s, x], g_out[:2])
+        return [t.detach() for t in (*block, *g_block, *chain, *g_chain)]
+
+    evaluate(upd, msg)
+    weights = {"update_mlp.0.weight": upd.update_mlp[0].weight, "update_mlp.0.bias": upd.update_mlp[0].bias,
+               "update_mlp.2.weight": upd.update_mlp[2].weight, "update_mlp.2.bias": upd.update_mlp[2].bias,
+               "update_U.weight": upd.update_U.weight, "update_U.bias": upd.update_U.bias, "update_V.weight": upd.update_V.weight,
+               "update_V.bias": upd.update_V.bias, "dot_lin.weight": upd.dot_lin.weight, "next scalar_mlp.0.weight": msg.scalar_mlp[0].weight,
+               "next scalar_mlp.0.bias": msg.scalar_mlp[0].bias, "next scalar_mlp.2.weight": msg.scalar_mlp[2].weight,
+               "next scalar_mlp.2.bias": msg.scalar_mlp[2].bias}
+    for name, p in weights.items():
+        with torch.no_grad():
+            if how == "in_place":
+                p.mul_(1.25).add_(0.01)
+            else:
+                p.data = p.data * 1.25 + 0.01
+        fresh_u, fresh_m = (m.to(dev).eval().requires_grad_(False) for m in _modules(6))
+        fresh_u.load_state_dict(upd.state_dict())
+        fresh_m.load_state_dict(msg.state_dict())
+        for k, (got, want) in enumerate(zip(evaluate(upd, msg), evaluate(fresh_u, fresh_m))):
+            assert torch.equal(got, want), f"after a change of {name} ({how}): output {k} differs by {(got - want).abs().max().item():.2e}"

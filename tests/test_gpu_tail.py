@@ -59,7 +59,7 @@ def test_first_block_front_is_the_three_gathers():
         z = torch.tensor([1, 6, 8, 1, 9, 7, 6, 0, 86], device=DEV, dtype=dt)
         rows = emb._embedded_rows(z)
         s, h, xhat = first_block_front(msg, z, rows, z.shape[0])
-        _, h_t, x0_t = msg._element_front
+        _, (h_t, x0_t) = msg._element_front
         assert torch.equal(s, rows.index_select(0, z.long()))
         assert torch.equal(h, h_t.index_select(0, z.long()))
         n, F = z.shape[0], 128

@@ -462,3 +462,39 @@ def test_graphed_train_step_checks_the_edge_capacity_on_the_host():
     assert runtime.pair_capacity(ptr_host) == 264
     with pytest.raises(ValueError, match="capacity is 100"):
         step(None, None, torch.tensor(ptr_host), None, ptr_host=ptr_host)
+
+
+def test_pack_cache_helper_rebuilds_exactly_when_its_key_moves():
+    """lib.cached, the one packed-weight cache of the Python front: a rebuild when a tensor is modified in place, when its storage is
+    replaced, when the pack epoch is bumped, when the flags change and when a tensor is absent instead of present -- and only then."""
+    from xequinet_amd import lib
+
+    class Owner:
+        pass
+
+    owner, builds = Owner(), []
+    w, b = torch.randn(4, 3), torch.randn(4)
+
+    def get(tensors, extra=(), slot="_pack"):
+        def build():
+            assert not torch.is_grad_enabled()
+            builds.append(slot)
+            return len(builds)
+
+        return lib.cached(owner, slot, tensors, build, extra)
+
+    assert get((w, b)) == 1 and get((w, b)) == 1 and len(builds) == 1        # nothing changed: no rebuild
+    with torch.no_grad():
+        b.add_(1.0)                                                          # (a) in place: the version counter moves
+    assert get((w, b)) == 2 and get((w, b)) == 2
+    version, address = w._version, w.data_ptr()
+    w.data = w.data.clone()                                                  # (b) a new storage under the same tensor and version
+    assert w._version == version and w.data_ptr() != address
+    assert get((w, b)) == 3 and get((w, b)) == 3
+    lib.bump_pack_epoch()                                                    # (c) parameters changed behind autograd's back
+    assert get((w, b)) == 4 and get((w, b)) == 4
+    assert get((w, b), (True,)) == 5 and get((w, b), (True,)) == 5           # (d) another form of the pack
+    assert get((w, b), (False,)) == 6
+    assert get((w, None)) == 7 and get((w, None)) == 7 and get((w, b)) == 8  # an absent tensor is not a present one
+    assert get((w, b), slot="_other") == 9 and get((w, b)) == 8              # slots do not share entries
+    assert owner._pack[1] == 8 and owner._pack[0] == lib.pack_key((w, b))

@@ -25,8 +25,10 @@
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
+#include <array>
 #include <cmath>
 #include <cstdlib>
+#include <map>
 #include <mutex>
 #include <optional>
 #include <unordered_map>
@@ -47,8 +49,8 @@ using torch::autograd::variable_list;
   } while (0)
 
 void* cur_stream() { return (void*)c10::hip::getCurrentHIPStream().stream(); }
-const void* P(const Tensor& t) { return t.defined() && t.numel() > 0 ? t.data_ptr() : (t.defined() ? t.data_ptr() : nullptr); }
-void* Pm(Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; }
+const float* PF(const Tensor& t) { return t.defined() ? (const float*)t.data_ptr() : nullptr; }   // f32 kernels; nullptr: absent
+float* PFm(Tensor& t) { return t.defined() ? (float*)t.data_ptr() : nullptr; }
 int dcode(const Tensor& t) {
   TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kDouble, "xequinet_amd: float32 / float64 tensors only");
   return t.scalar_type() == at::kFloat ? XEQ_F32 : XEQ_F64;
@@ -57,10 +59,10 @@ void need_hip(const Tensor& t, const char* what) {
   TORCH_CHECK(t.is_cuda(), "xequinet_amd ops run on MI355X (HIP) tensors only and have no CPU fallback; ", what, " is on ", t.device());
 }
 
-// ---------------------------------------------------------------------------------------------- two-layer MLPs
-// Linear-SiLU-Linear on the matrix cores (xeq_mlp2_fwd / _bwd, csrc/xeq_mlp.hip); nn/fused.py::_mlp_fwd / _mlp_bwd are the
-// Python twins.  The fragment-order weight copies are cached per weight tensor and rebuilt when a version counter moves.
-// An entry is valid only while the storage it was packed from is ALIVE (weak references): a freed parameter's address is
+// ---------------------------------------------------------------------------------------------- the packed-weight cache
+// Every packed copy of a weight this file makes lives in ONE cache, `packed<Entry>` below (xequinet_amd/lib.py::cached is what the
+// Python front uses).  An entry is rebuilt when a version counter, the pack epoch or an address of one of its tensors moves, and
+// is valid only while the storage it was packed from is ALIVE (weak references): a freed parameter's address is
 // reused by the allocator, typically by the next model's parameter of the same shape with the same version count.
 // The references are to the STORAGE (not the tensor object): XPaiNNNative hands over fresh views of one flat parameter
 // buffer on every call -- same storage, same address, shared version counter -- and those must hit the cache.
@@ -89,24 +91,46 @@ struct Owners {
     return true;
   }
 };
-struct MlpPacks {
-  int64_t key[8];
-  Owners owners;
-  Tensor w1p, w2p, w2tp, w1tp;
-};
+// The entry of (`slot_key`: the address of the site's leading weight, `form`: which form of the pack, for a site with several), made
+// by `build(entry)` from `tensors` (an undefined tensor: an absent one).  One mutex and one map per Entry type; the key is formed
+// here and nowhere else: (version counter + pack epoch, address) per tensor, on the stack (this runs once per launch site).
+constexpr size_t PACK_MAX_TENSORS = 12;
+template <class Entry, class Build>
+Entry& packed(const void* slot_key, std::initializer_list<const Tensor*> tensors, int64_t form, Build&& build) {
+  struct Slot {
+    std::array<int64_t, 2 * PACK_MAX_TENSORS> key;
+    Owners owners;
+    Entry entry;
+  };
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int64_t>, Slot> cache;
+  TORCH_INTERNAL_ASSERT(tensors.size() <= PACK_MAX_TENSORS);
+  const int64_t epoch = (int64_t)xeq_pack_epoch() << 32;
+  std::array<int64_t, 2 * PACK_MAX_TENSORS> key{};
+  size_t n = 0;
+  for (const Tensor* t : tensors) {
+    key[n++] = t->defined() ? (int64_t)t->_version() + epoch : -1;
+    key[n++] = t->defined() && t->numel() > 0 ? (int64_t)(intptr_t)t->data_ptr() : 0;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  Slot& s = cache[{slot_key, form}];
+  if (!s.owners.same(tensors) || s.key != key) {   // (a fresh slot has no owners: it misses)
+    build(s.entry);
+    s.owners.set(tensors);
+    s.key = key;
+  }
+  return s.entry;
+}
+
+// ---------------------------------------------------------------------------------------------- two-layer MLPs
+// Linear-SiLU-Linear on the matrix cores (xeq_mlp2_fwd / _bwd, csrc/xeq_mlp.hip) from fragment-order weight copies;
+// Python: nn/fused.py::_mlp_packs / _mlp_fwd / _mlp_bwd.
+struct MlpPacks { Tensor w1p, w2p, w2tp, w1tp; };
 const MlpPacks* mlp_packs(const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2) {
   if (w1.scalar_type() != at::kFloat || b1.numel() == 0 || b2.numel() == 0 ||
       !xeq_mlp2_supported(XEQ_F32, (int)w1.size(1), (int)w1.size(0), (int)w2.size(0)))
     return nullptr;
-  static std::mutex mu;
-  static std::unordered_map<const void*, MlpPacks> cache;
-  const int64_t key[8] = {(int64_t)w1._version() + ((int64_t)xeq_pack_epoch() << 32), (int64_t)(intptr_t)w1.data_ptr(), (int64_t)b1._version(), (int64_t)(intptr_t)b1.data_ptr(),
-                          (int64_t)w2._version(), (int64_t)(intptr_t)w2.data_ptr(), (int64_t)b2._version(), (int64_t)(intptr_t)b2.data_ptr()};
-  std::lock_guard<std::mutex> lock(mu);
-  MlpPacks& e = cache[w1.data_ptr()];
-  bool same = e.w1p.defined() && e.owners.same({&w1, &b1, &w2, &b2});
-  for (int i = 0; i < 8 && same; ++i) same = e.key[i] == key[i];
-  if (!same) {
+  return &packed<MlpPacks>(w1.data_ptr(), {&w1, &b1, &w2, &b2}, 0, [&](MlpPacks& e) {
     const int h = (int)w1.size(0), k1 = (int)w1.size(1), n2 = (int)w2.size(0);
     const Tensor w1c = w1.detach().contiguous(), w2c = w2.detach().contiguous();
     auto pack = [&](const Tensor& w, const Tensor* bias, int n_out, int k_in, int transposed) {
@@ -119,36 +143,19 @@ const MlpPacks* mlp_packs(const Tensor& w1, const Tensor& b1, const Tensor& w2, 
     e.w2p = pack(w2c, &b2, n2, h, 0);
     e.w2tp = pack(w2c, nullptr, h, n2, 1);
     e.w1tp = pack(w1c, nullptr, k1, h, 1);
-    e.owners.set({&w1, &b1, &w2, &b2});
-    for (int i = 0; i < 8; ++i) e.key[i] = key[i];
-  }
-  return &e;
+  });
 }
-// rbf_lin's rows in the wq message kernels' LDS layout (xeq_message_wq_pack_weights; ops.wq_packed_weights is the Python twin), cached
-// per weight version like the packs above: the kernels then stage a unit's weights with coalesced loads (XEQ_WQ_PACKED_WEIGHTS)
-struct WqWeightPack {
-  int64_t key[4];
-  Owners owners;
-  Tensor packed;
-};
+// rbf_lin's rows in the wq message kernels' LDS layout (xeq_message_wq_pack_weights; Python: ops.wq_packed_weights): the kernels
+// then stage a unit's weights with coalesced loads (XEQ_WQ_PACKED_WEIGHTS)
+struct WqWeightPack { Tensor packed; };
 const Tensor* wq_weight_pack(const Tensor& w, const Tensor& b, int num_basis, int node_dim, const int32_t mul[3]) {
   const int64_t n = xeq_message_wq_packed_weight_floats(num_basis, node_dim, mul);
   if (n <= 0 || w.scalar_type() != at::kFloat || !b.defined() || b.numel() == 0) return nullptr;
-  static std::mutex mu;
-  static std::unordered_map<const void*, WqWeightPack> cache;
-  const int64_t key[4] = {(int64_t)w._version() + ((int64_t)xeq_pack_epoch() << 32), (int64_t)(intptr_t)w.data_ptr(), (int64_t)b._version(), (int64_t)(intptr_t)b.data_ptr()};
-  std::lock_guard<std::mutex> lock(mu);
-  WqWeightPack& e = cache[w.data_ptr()];
-  bool same = e.packed.defined() && e.owners.same({&w, &b});
-  for (int i = 0; i < 4 && same; ++i) same = e.key[i] == key[i];
-  if (!same) {
+  return &packed<WqWeightPack>(w.data_ptr(), {&w, &b}, 0, [&](WqWeightPack& e) {
     const Tensor wc = w.detach().contiguous(), bc = b.detach().contiguous();
     e.packed = at::empty({n}, w.options());
     XCALL(xeq_message_wq_pack_weights(wc.data_ptr(), bc.data_ptr(), num_basis, node_dim, mul, e.packed.data_ptr(), cur_stream()));
-    e.owners.set({&w, &b});
-    for (int i = 0; i < 4; ++i) e.key[i] = key[i];
-  }
-  return &e.packed;
+  }).packed;
 }
 // x: [n, k1] rows with stride ldx (a column slice of a wider buffer is fine)
 void mlp_fwd(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, Tensor& pre, Tensor& y) {
@@ -176,25 +183,14 @@ Tensor mlp_bwd(const Tensor& g_y, const Tensor& pre, const Tensor& w1, const Ten
 }
 
 // Single linear layers (dot_lin, the embedding, the head's first layer) through xeq_linear_fwd (csrc/xeq_linear.hip);
-// nn/fused.py::_linear_pack / _linear / linear_module_fwd / linear_module_bwd are the Python twins.  Packs cached per weight.
-struct LinPack {
-  int64_t key[4];
-  Owners owners;
-  Tensor fwd, bwd;
-};
+// Python: nn/fused.py::_linear_pack / _linear / linear_module_fwd / linear_module_bwd.
+struct LinPack { Tensor fwd, bwd; };
 const LinPack* lin_pack(const Tensor& w, const Tensor& b) {
   const int n_out = (int)w.size(0), k_in = (int)w.size(1);
   if (w.scalar_type() != at::kFloat || !xeq_linear_supported(XEQ_F32, k_in, n_out)) return nullptr;
   const bool has_bwd = xeq_linear_supported(XEQ_F32, n_out, k_in) != 0;   // (the embedding's 56 inputs: forward only, nobody differentiates it)
-  static std::mutex mu;
-  static std::unordered_map<const void*, LinPack> cache;
   const bool hb = b.defined() && b.numel() > 0;
-  const int64_t key[4] = {(int64_t)w._version() + ((int64_t)xeq_pack_epoch() << 32), (int64_t)(intptr_t)w.data_ptr(), hb ? (int64_t)b._version() : -1, hb ? (int64_t)(intptr_t)b.data_ptr() : 0};
-  std::lock_guard<std::mutex> lock(mu);
-  LinPack& e = cache[w.data_ptr()];
-  bool same = e.fwd.defined() && e.owners.same({&w, &b});
-  for (int i = 0; i < 4 && same; ++i) same = e.key[i] == key[i];
-  if (!same) {
+  return &packed<LinPack>(w.data_ptr(), {&w, &b}, 0, [&](LinPack& e) {
     const Tensor wc = w.detach().contiguous();
     e.fwd = at::empty({xeq_mlp_packed_floats(n_out, k_in)}, w.options());
     XCALL(xeq_mlp_pack((const float*)wc.data_ptr(), hb ? (const float*)b.data_ptr() : nullptr, n_out, k_in, 0, (float*)e.fwd.data_ptr(), cur_stream()));
@@ -203,10 +199,7 @@ const LinPack* lin_pack(const Tensor& w, const Tensor& b) {
       e.bwd = at::empty({xeq_mlp_packed_floats(k_in, n_out)}, w.options());
       XCALL(xeq_mlp_pack((const float*)wc.data_ptr(), nullptr, k_in, n_out, 1, (float*)e.bwd.data_ptr(), cur_stream()));
     }
-    e.owners.set({&w, &b});
-    for (int i = 0; i < 4; ++i) e.key[i] = key[i];
-  }
-  return &e;
+  });
 }
 // y = act(x W^T + b); row_index (int32, optional) gathers the rows of x; pre (optional) receives the pre-activation
 Tensor linear_fwd(const Tensor& x, const Tensor& w, const Tensor& b, int act = 0, const Tensor* row_index = nullptr, Tensor* pre = nullptr) {
@@ -236,7 +229,7 @@ Tensor linear_bwd(const Tensor& g_in, const Tensor& w, const Tensor& b) {   // d
 }
 
 // XPainnUpdate's two independent products side by side (xeq_mlp2_and_linear: one launch for MD-sized systems);
-// nn/fused.py::mlp_and_linear_fwd / _bwd are the Python twins.
+// Python: nn/fused.py::mlp_and_linear_fwd / _bwd.
 void mlp_and_linear_fwd(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2, const Tensor& p, const Tensor& wl,
                         Tensor& pre, Tensor& y, Tensor& ip) {
   const MlpPacks* pk = (x.stride(1) == 1 && x.stride(0) % 4 == 0) ? mlp_packs(w1, b1, w2, b2) : nullptr;
@@ -275,29 +268,16 @@ void mlp_and_linear_bwd(const Tensor& g_y, const Tensor& pre, const Tensor& w1, 
 }
 
 // [W_U | W_V] / sqrt(mul) blocks (prm layout: one [mul, 2 mul] tensor per l, empty when absent) in fragment order for
-// xeq_update_uv_fwd; nn/fused.py::_packed_uv_frag is the Python twin.  Cached per weight tensor like the MLP packs.
+// xeq_update_uv_fwd / _bwd; Python: nn/fused.py::_packed_uv_frag.
 struct UvFrag {
-  int64_t key[8];
-  Owners owners;
   Tensor w[3], wt[3];   // forward ([k_in = mul][n_out = 2 mul], biases folded) and reverse ([n_out = mul][k_in = 2 mul]) packs
 };
-constexpr int64_t UV_BWD_FUSE_NORM_MAX_NODES = 0;   // nn/fused.py::UV_BWD_FUSE_NORM_MAX_NODES (never fused: batch-independent bits)
+constexpr int64_t UV_BWD_FUSE_NORM_MAX_NODES = 0;   // the constant of the same name in nn/fused.py, which says why
 const UvFrag* uv_frag(const Tensor* q /* [W0, W1, W2, bias pair] */, int node_dim, const int32_t mul[3]) {
   if (q[0].scalar_type() != at::kFloat || !xeq_update_uv_supported(XEQ_F32, node_dim, mul)) return nullptr;
-  static std::mutex mu;
-  static std::unordered_map<const void*, UvFrag> cache;
-  int64_t key[8];
-  for (int i = 0; i < 4; ++i) {
-    key[2 * i] = q[i].numel() > 0 ? (int64_t)q[i]._version() + ((int64_t)xeq_pack_epoch() << 32) : -1;
-    key[2 * i + 1] = q[i].numel() > 0 ? (int64_t)(intptr_t)q[i].data_ptr() : 0;
-  }
-  std::lock_guard<std::mutex> lock(mu);
   int first = 0;
   while (first < 3 && mul[first] == 0) ++first;
-  UvFrag& e = cache[q[first].data_ptr()];
-  bool same = e.w[first].defined() && e.owners.same({&q[0], &q[1], &q[2], &q[3]});
-  for (int i = 0; i < 8 && same; ++i) same = e.key[i] == key[i];
-  if (!same) {
+  return &packed<UvFrag>(q[first].data_ptr(), {&q[0], &q[1], &q[2], &q[3]}, 0, [&](UvFrag& e) {
     for (int l = 0; l < 3; ++l) {
       e.w[l] = Tensor();
       e.wt[l] = Tensor();
@@ -309,43 +289,19 @@ const UvFrag* uv_frag(const Tensor* q /* [W0, W1, W2, bias pair] */, int node_di
       e.wt[l] = at::empty({xeq_mlp_packed_floats(mul[l], 2 * mul[l])}, W.options());
       XCALL(xeq_mlp_pack((const float*)W.data_ptr(), nullptr, mul[l], 2 * mul[l], 0, (float*)e.wt[l].data_ptr(), cur_stream()));
     }
-    e.owners.set({&q[0], &q[1], &q[2], &q[3]});
-    for (int i = 0; i < 8; ++i) e.key[i] = key[i];
-  }
-  return &e;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- fused node blocks
 // One launch per direction for an update block and the front half of the message block behind it (csrc/xeq_nodeblock.hip;
-// nn/nodeblock.py / nn/fused.py::NodeBlock are the Python twins).  The packed weight programs are cached per update_mlp weight.
-struct NbPacks {
-  std::vector<int64_t> key;
-  Owners owners;
-  Tensor fwd, bwd, bias_uv;
-};
+// Python: nn/nodeblock.py::packed_fwd / packed_bwd / _uv_bias).  The packed weight programs are cached per update_mlp weight.
+struct NbPacks { Tensor fwd, bwd, bias_uv; };
 // q: the block's parameters (layout below), qn: the next block's (nullptr: no front half); gx: dL/dx_out is not zero
 const NbPacks* nb_packs(const Tensor* q, const Tensor* qn, bool gx) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, NbPacks> cache[4];
   const bool tail = qn != nullptr;
-  std::vector<const Tensor*> ws = {&q[15], &q[10], &q[11], &q[12], &q[14], &q[17], &q[13]};
-  if (tail) {
-    ws.push_back(&qn[0]);
-    ws.push_back(&qn[2]);
-  }
-  std::vector<int64_t> key;
-  for (const Tensor* t : ws) {
-    key.push_back(t->defined() ? (int64_t)t->_version() + ((int64_t)xeq_pack_epoch() << 32) : -1);
-    key.push_back(t->defined() && t->numel() > 0 ? (int64_t)(intptr_t)t->data_ptr() : 0);
-  }
-  std::lock_guard<std::mutex> lock(mu);
-  NbPacks& e = cache[(tail ? 2 : 0) + (gx ? 1 : 0)][q[15].data_ptr()];
-  bool same = e.fwd.defined() && e.key == key;
-  if (same) {
-    if (tail) same = e.owners.same({ws[0], ws[1], ws[2], ws[3], ws[4], ws[5], ws[6], ws[7], ws[8]});
-    else same = e.owners.same({ws[0], ws[1], ws[2], ws[3], ws[4], ws[5], ws[6]});
-  }
-  if (!same) {
+  const Tensor none;
+  return &packed<NbPacks>(q[15].data_ptr(), {&q[15], &q[10], &q[11], &q[12], &q[14], &q[17], &q[13], tail ? &qn[0] : &none, tail ? &qn[2] : &none},
+                          (tail ? 2 : 0) + (gx ? 1 : 0), [&](NbPacks& e) {
     const auto bopt = q[15].options().dtype(at::kByte);
     const Tensor w3 = q[15].detach().contiguous(), dot = q[14].detach().contiguous(), w4 = q[17].detach().contiguous();
     const Tensor uv0 = q[10].contiguous(), uv1 = q[11].contiguous(), uv2 = q[12].contiguous();
@@ -354,17 +310,12 @@ const NbPacks* nb_packs(const Tensor* q, const Tensor* qn, bool gx) {
       w1n = qn[0].detach().contiguous();
       w2n = qn[2].detach().contiguous();
     }
-    auto fp = [](const Tensor& t) { return t.defined() ? (const float*)t.data_ptr() : nullptr; };
     e.fwd = at::empty({xeq_node_block_fwd_tiles(tail) * 3072}, bopt);
-    XCALL(xeq_node_block_pack_fwd(fp(w3), fp(uv0), fp(uv1), fp(uv2), fp(dot), fp(w4), fp(w1n), fp(w2n), e.fwd.data_ptr(), cur_stream()));
+    XCALL(xeq_node_block_pack_fwd(PF(w3), PF(uv0), PF(uv1), PF(uv2), PF(dot), PF(w4), PF(w1n), PF(w2n), e.fwd.data_ptr(), cur_stream()));
     e.bwd = at::empty({xeq_node_block_bwd_tiles(tail, gx) * 3072}, bopt);
-    XCALL(xeq_node_block_pack_bwd(fp(w3), fp(uv0), fp(uv1), fp(uv2), fp(dot), fp(w4), fp(w1n), fp(w2n), gx, e.bwd.data_ptr(), cur_stream()));
+    XCALL(xeq_node_block_pack_bwd(PF(w3), PF(uv0), PF(uv1), PF(uv2), PF(dot), PF(w4), PF(w1n), PF(w2n), gx, e.bwd.data_ptr(), cur_stream()));
     e.bias_uv = q[13].numel() > 0 ? q[13].detach().contiguous() : Tensor();
-    if (tail) e.owners.set({ws[0], ws[1], ws[2], ws[3], ws[4], ws[5], ws[6], ws[7], ws[8]});
-    else e.owners.set({ws[0], ws[1], ws[2], ws[3], ws[4], ws[5], ws[6]});
-    e.key = key;
-  }
-  return &e;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- graph plumbing
@@ -518,38 +469,20 @@ NormOut norm_fwd(const Hyper& hy, const Tensor& s, const Tensor& x, const Tensor
   o.shat = shat_out;
   o.xhat = at::empty({n * hy.D()}, x.options());
   o.stats = at::empty({n, 4}, s.options());
-  const int32_t mul[3] = {hy.mul[0], hy.mul[1], hy.mul[2]};
   XCALL(xeq_norm_fwd(dcode(s), s.data_ptr(), x.data_ptr(), hy.layer_norm ? lw.data_ptr() : nullptr,
                      hy.layer_norm ? lb.data_ptr() : nullptr, hy.layer_norm ? ew.data_ptr() : nullptr,
-                     hy.layer_norm ? eb.data_ptr() : nullptr, n, hy.F, mul, hy.layer_norm, o.shat.data_ptr(), ld,
+                     hy.layer_norm ? eb.data_ptr() : nullptr, n, hy.F, hy.mul, hy.layer_norm, o.shat.data_ptr(), ld,
                      o.xhat.data_ptr(), o.stats.data_ptr(), cur_stream()));
   return o;
 }
-// Front half of the FIRST message block from the element table (nn/fused.py::first_block_front is the Python twin): behind the embedding a
+// Front half of the FIRST message block from the element table (Python: nn/fused.py::first_block_front): behind the embedding a
 // node's scalars are a function of its element and x = 0, so LayerNorm, EquivariantLayerNorm and scalar_mlp (nn/xpainn.py:128-139) are
 // evaluated once per table row -- the same xeq_linear_fwd / xeq_norm_fwd / xeq_mlp2_fwd launches, which give a row the same bits in any
-// batch -- and cached per weight version; an evaluation gathers (s, h, xhat's 0e block) by atomic number in ONE launch
+// batch -- and cached; an evaluation gathers (s, h, xhat's 0e block) by atomic number in ONE launch
 // (xeq_first_block_front).  q: the first block's parameters.
-struct ElementFront {
-  std::vector<int64_t> key;
-  Owners owners;
-  Tensor rows_s, rows_h, rows_x0;
-};
+struct ElementFront { Tensor rows_s, rows_h, rows_x0; };
 const ElementFront* element_front(const Hyper& hy, const Tensor& table, const Tensor& ew, const Tensor& eb, const Tensor* q) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, ElementFront> cache;
-  const Tensor* ts[11] = {&table, &ew, &eb, &q[0], &q[1], &q[2], &q[3], &q[6], &q[7], &q[8], &q[9]};
-  std::vector<int64_t> key;
-  key.push_back((int64_t)xeq_pack_epoch());
-  for (const Tensor* t : ts) {
-    key.push_back((int64_t)t->_version());
-    key.push_back((int64_t)(intptr_t)t->data_ptr());
-  }
-  std::lock_guard<std::mutex> lock(mu);
-  ElementFront& e = cache[table.data_ptr()];
-  const bool same = e.rows_s.defined() && e.key == key &&
-                    e.owners.same({ts[0], ts[1], ts[2], ts[3], ts[4], ts[5], ts[6], ts[7], ts[8], ts[9], ts[10]});
-  if (!same) {
+  return &packed<ElementFront>(table.data_ptr(), {&table, &ew, &eb, &q[0], &q[1], &q[2], &q[3], &q[6], &q[7], &q[8], &q[9]}, 0, [&](ElementFront& e) {
     const int64_t zt = table.size(0);
     const Tensor z_all = at::arange(zt, table.options().dtype(at::kInt));
     e.rows_s = linear_fwd(table, ew, eb, 0, &z_all, nullptr);
@@ -559,10 +492,7 @@ const ElementFront* element_front(const Hyper& hy, const Tensor& table, const Te
     mlp_fwd(no.shat, q[0], q[1], q[2], q[3], pre, e.rows_h);
     e.rows_h = e.rows_h.contiguous();
     e.rows_x0 = no.xhat.slice(0, 0, zt * hy.F).view({zt, (int64_t)hy.F}).contiguous();   // BT layout: the 0e block comes first
-    e.owners.set({ts[0], ts[1], ts[2], ts[3], ts[4], ts[5], ts[6], ts[7], ts[8], ts[9], ts[10]});
-    e.key = key;
-  }
-  return &e;
+  });
 }
 void norm_bwd(const Hyper& hy, const Tensor& s, const Tensor& x, const Tensor& lw, const Tensor& ew, const Tensor& stats,
               const Tensor& g_shat, int64_t ld, const Tensor& g_xhat, const Tensor& res_s, const Tensor& res_x, Tensor& g_s,
@@ -570,16 +500,14 @@ void norm_bwd(const Hyper& hy, const Tensor& s, const Tensor& x, const Tensor& l
   const int64_t n = x.size(0);
   g_s = at::empty_like(s);
   g_x = at::empty_like(x);
-  const int32_t mul[3] = {hy.mul[0], hy.mul[1], hy.mul[2]};
   XCALL(xeq_norm_bwd(dcode(s), s.data_ptr(), x.data_ptr(), hy.layer_norm ? lw.data_ptr() : nullptr,
-                     hy.layer_norm ? ew.data_ptr() : nullptr, stats.data_ptr(), n, hy.F, mul, hy.layer_norm, g_shat.data_ptr(), ld,
+                     hy.layer_norm ? ew.data_ptr() : nullptr, stats.data_ptr(), n, hy.F, hy.mul, hy.layer_norm, g_shat.data_ptr(), ld,
                      g_xhat.data_ptr(), res_s.defined() ? res_s.data_ptr() : nullptr, res_x.defined() ? res_x.data_ptr() : nullptr,
                      g_s.data_ptr(), g_x.data_ptr(), cur_stream()));
 }
 
-// what one block keeps for the reverse pass
 // The seed of an inference reverse pass behind the fused head: MINUS one (a [1] f32 constant, cached per device; nn/basic.py::_seed and
-// nn/fused.py::constant_vector are the Python twins).  The reverse pass then returns -dE/dx = the forces without a negation launch -- and
+// nn/fused.py::constant_vector are its Python counterparts).  The reverse pass then returns -dE/dx = the forces without a negation launch -- and
 // with the bits of the Python front: the bf16 matrix instructions are not symmetric in the sign (profiles/r05_mfma_sign.txt), so a pass
 // seeded with +1 and negated afterwards differs in the last bit wherever a cotangent runs through the fused node block.  Not cached while
 // a HIP graph is being captured (the tensor would live in that graph's pool).
@@ -600,13 +528,426 @@ Tensor minus_one(const at::TensorOptions& fopt) {
   return t;
 }
 
-struct MsgSaved {
+// ---------------------------------------------------------------------------------------------- the blocks of an evaluation
+// One function per block and direction, named after its counterpart in nn/fused.py; xpainn_eval_impl below is their sequence.
+// hy: the model, g: the edge list and its plans, q: the block's parameters (layout above), s / x: the node features, replaced by
+// the block's outputs; g_s / g_x: their gradients, replaced likewise (an undefined g_x is zero).
+struct MsgSaved {   // what a message block keeps for the reverse pass
   Tensor s, x, stats, pre, h, xhat;
-  int impl = 0;   // 0 wq, 1 sb
 };
-struct UpdSaved {
+struct UpdSaved {   // ... and an update block
   Tensor s, x, stats, uv, pre, a, ip;
 };
+struct EdgeGrad {   // dL/dvec over the blocks of the reverse pass (Python: ops.EdgeGradDeferral, same order: last block first)
+  bool defer = false;             // wq: the blocks' partials are added up and the chain rule to dL/dvec runs ONCE, behind block 0
+  std::vector<Tensor> part_sets;
+  Tensor total;
+};
+
+// rbf_lin's rows for the wq kernels: the packed copy
+const void* wq_weights(const Hyper& hy, const Tensor* q) {
+  const Tensor* pk = wq_weight_pack(q[4], q[5], hy.B, hy.F, hy.mul);
+  TORCH_CHECK(pk != nullptr, "xeq::xpainn_eval: rbf_lin weights cannot be packed for the wq kernels");
+  return pk->data_ptr();
+}
+
+// XEmbedding.forward (nn/xpainn.py) and, where the table form covers the layout, nn/fused.py::first_block_front: the node scalars
+// and the first block's norms and scalar_mlp in one gather by atomic number from per-element rows (m0.h is then defined).
+// x: the zero equivariant features; wq: the wq message kernels follow; run_el: a charge / spin embedding follows.
+Tensor embed_and_first_front(const Hyper& hy, const std::vector<Tensor>& prm, const Tensor& atomic_numbers, const Tensor& x, bool wq,
+                             bool run_el, MsgSaved& m0) {
+  const int64_t N = x.size(0);
+  const int F = hy.F, D = hy.D(), H = hy.H();
+  const auto fopt = x.options();
+  const bool z_int = atomic_numbers.scalar_type() == at::kInt || atomic_numbers.scalar_type() == at::kLong;
+  const bool table_form = hy.embed_kind == 0 && hy.blocks > 0 && x.scalar_type() == at::kFloat && hy.layer_norm && hy.mul[0] == F &&
+                          prm[0].scalar_type() == at::kFloat && prm[0].dim() == 2 && prm[0].stride(1) == 1 && prm[0].stride(0) % 4 == 0 &&
+                          lin_pack(prm[1], prm[2]) != nullptr;
+  if (table_form && run_el) {
+    // behind a charge / spin embedding the first block's scalars no longer depend on the element alone: the node scalars are gathered
+    // from the per-element rows (nn/xpainn.py::XEmbedding.forward, ELEMENT_ROWS) and the first block takes its per-node launches
+    const ElementFront* ef = element_front(hy, prm[0], prm[1], prm[2], &prm[P_BLOCK0]);
+    return ef->rows_s.index_select(0, (z_int ? atomic_numbers : atomic_numbers.to(at::kLong)));
+  }
+  if (table_form) {
+    const ElementFront* ef = element_front(hy, prm[0], prm[1], prm[2], &prm[P_BLOCK0]);
+    const Tensor z = (z_int ? atomic_numbers : atomic_numbers.to(at::kLong)).contiguous();
+    Tensor s = at::empty({N, (int64_t)F}, fopt);
+    m0.h = at::empty({N, (int64_t)H}, fopt);
+    m0.xhat = at::empty({N * (int64_t)D}, fopt);
+    // the wq kernels never read xhat's l > 0 blocks behind the embedding (XEQ_XHAT_HIGHER_L_ZERO): those are then not even written
+    XCALL(xeq_first_block_front(z.data_ptr(), z.scalar_type() == at::kLong, N, ef->rows_s.size(0), ef->rows_s.data_ptr(),
+                                ef->rows_h.data_ptr(), ef->rows_x0.data_ptr(), F, H, wq ? F : D, s.data_ptr(), m0.h.data_ptr(),
+                                m0.xhat.data_ptr(), cur_stream()));
+    m0.s = s;
+    m0.x = x;
+    return s;
+  }
+  if (hy.embed_kind == 0) {
+    const Tensor z32 = atomic_numbers.to(at::kInt).contiguous();
+    return linear_fwd(prm[0], prm[1], prm[2], 0, &z32);   // table lookup + Linear in one launch (nn/xpainn.py::XEmbedding._embed)
+  }
+  return prm[0].index_select(0, atomic_numbers.to(at::kLong));
+}
+
+// nn/electronic.py (csrc/xeq_electronic.hip): the charge, then the spin embedding, two launches each.  e: the first electronic
+// parameter; has[kind]: the model has the module; total[kind]: the per-graph value, nullptr where the module does not run
+Tensor electronic_fwd(const Hyper& hy, const Tensor* e, const bool has[2], const Tensor* const total_in[2], Tensor s, const Tensor& ptr64) {
+  const int64_t N = s.size(0), G = ptr64.numel() - 1;
+  for (int kind = 0; kind < 2; ++kind) {
+    const Tensor* w = e;
+    if (has[kind]) e += P_ELECTRONIC;
+    if (!total_in[kind]) continue;
+    const Tensor total = total_in[kind]->reshape({-1}).to(at::kFloat).contiguous();
+    TORCH_CHECK(total.numel() == G, "xeq::xpainn_eval: ", kind == 0 ? "charge" : "spin", " has ", total.numel(), " values for ", G, " graphs");
+    const LinPack* pq = lin_pack(w[0], w[1]);
+    const LinPack* p1 = lin_pack(w[4], Tensor());
+    const LinPack* p2 = lin_pack(w[5], Tensor());
+    TORCH_CHECK(pq && p1 && p2, "xeq::xpainn_eval: the electronic module's weights cannot be packed");
+    s = s.contiguous();
+    Tensor attn = at::empty({N}, s.options()), s_out = at::empty({N, (int64_t)hy.F}, s.options());
+    const Tensor wk = w[2].contiguous(), wv = w[3].contiguous();
+    XCALL(xeq_electronic_fwd(kind, s.data_ptr(), s.stride(0), N, hy.F, (const int64_t*)ptr64.data_ptr(), G, total.data_ptr(),
+                             pq->fwd.data_ptr(), wk.data_ptr(), wv.data_ptr(), p1->fwd.data_ptr(), p2->fwd.data_ptr(), attn.data_ptr(),
+                             s_out.data_ptr(), cur_stream()));
+    s = s_out;
+  }
+  return s;
+}
+
+// ops.message_forward's record launch: the radial / angular records of every edge for the message kernels.  wq (`wq`): along the
+// forward plan, or the reverse one (`reverse`), with the derivative records when `want_d`; sb: value and derivative rows per edge
+void edge_basis(const Hyper& hy, Graph& g, const Tensor& vec, const Tensor& p0, const Tensor& p1, bool wq, bool reverse, bool want_d) {
+  const auto fopt = vec.options();
+  if (wq) {
+    WqPlan& w = reverse ? g.rev : g.fwd;
+    build_wq_plan(g, reverse, w);
+    w.basis = at::empty({w.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
+    if (want_d) w.dbasis = at::empty({w.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
+    XCALL(xeq_edge_basis_wq(vec.data_ptr(), g.N, g.E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
+                            hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1), w.basis.data_ptr(),
+                            w.dbasis.defined() ? w.dbasis.data_ptr() : nullptr, cur_stream()));
+  } else {
+    const int w = xeq_edge_basis_width(hy.B);
+    g.sb_basis = at::empty({g.E, w}, fopt);
+    g.sb_dbasis = at::empty({g.E, w}, fopt);
+    XCALL(xeq_edge_basis(dcode(vec), vec.data_ptr(), g.E, hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1),
+                         g.sb_basis.data_ptr(), g.sb_dbasis.data_ptr(), cur_stream()));
+  }
+}
+
+// The front half of fused.MessageBlock.forward (nn/xpainn.py:128-139): both norms and scalar_mlp, per node
+void message_front_fwd(const Hyper& hy, const Tensor* q, const Tensor& s, const Tensor& x, MsgSaved& m) {
+  m.s = s;
+  m.x = x;
+  NormOut no = norm_fwd(hy, s, x, q[6], q[7], q[8], q[9], Tensor(), 0);
+  m.stats = no.stats;
+  m.xhat = no.xhat;
+  mlp_fwd(no.shat, q[0], q[1], q[2], q[3], m.pre, m.h);
+}
+// ... and of MessageBlock.backward: g_s / g_x arrive as the residual path's gradients
+void message_front_bwd(const Hyper& hy, const Tensor* q, const MsgSaved& m, const Tensor& g_h, const Tensor& g_xhat, Tensor& g_s, Tensor& g_x) {
+  const Tensor g_shat = mlp_bwd(g_h, m.pre, q[0], q[1], q[2], q[3]);
+  Tensor ns, nx;
+  norm_bwd(hy, m.s, m.x, q[6], q[8], m.stats, g_shat, hy.F, g_xhat, g_s, g_x, ns, nx);
+  g_s = ns;
+  g_x = nx;
+}
+
+// fused.MessageBlock.forward (nn/xpainn.py:128-161): the front half unless a gather or a fused node block has left it in m, then
+// the message kernel.  first: the block behind the embedding (x = 0)
+void message_block_fwd(const Hyper& hy, Graph& g, const Tensor* q, bool wq, bool first, MsgSaved& m, Tensor& s, Tensor& x) {
+  if (!m.h.defined()) message_front_fwd(hy, q, s, x, m);
+  Tensor s_out = at::empty_like(s), x_out = at::empty_like(x);
+  if (wq) {
+    XCALL(xeq_message_fwd_wq(g.N, g.E, g.fwd.n_ranges, (const int32_t*)g.fwd.sq.data_ptr(), (const int32_t*)g.fwd.sn.data_ptr(),
+                             (const int32_t*)g.fwd.win.data_ptr(), (const int32_t*)g.fwd.rowptr.data_ptr(),
+                             (const int32_t*)g.fwd.pgath.data_ptr(), (const int32_t*)g.fwd.qinfo.data_ptr(), g.fwd.basis.data_ptr(),
+                             m.h.data_ptr(), m.xhat.data_ptr(), s.data_ptr(), x.data_ptr(), wq_weights(hy, q), nullptr, hy.B,
+                             hy.F, hy.mul, s_out.data_ptr(), x_out.data_ptr(), (first ? (1 | XEQ_XHAT_HIGHER_L_ZERO) : 1) | XEQ_WQ_PACKED_WEIGHTS, cur_stream()));
+  } else {
+    XCALL(xeq_message_fwd_sb(dcode(s), g.N, g.E, (const int32_t*)g.c_rowptr.data_ptr(),
+                             g.c_perm.defined() ? (const int32_t*)g.c_perm.data_ptr() : nullptr,
+                             (const int64_t*)g.ei.select(0, 1).data_ptr(), g.sb_basis.data_ptr(), m.h.data_ptr(), m.xhat.data_ptr(),
+                             s.data_ptr(), x.data_ptr(), q[4].data_ptr(), q[5].data_ptr(), hy.B, hy.F, hy.mul, s_out.data_ptr(),
+                             x_out.data_ptr(), 1, cur_stream()));
+  }
+  s = s_out;
+  x = x_out;
+}
+
+// fused.MessageBlock.backward without its front half: the message kernel's reverse; dL/dvec goes to eg.  g_h / g_xhat: the gradients
+// of (h, xhat), undefined for the first block of a wq pass (only dL/dvec leaves it, the kernel then stores no node gradients)
+void message_block_bwd(const Hyper& hy, Graph& g, const Tensor* q, bool wq, bool first, const Tensor& vec, const MsgSaved& m, const Tensor& g_s,
+                       const Tensor& g_x, Tensor& g_h, Tensor& g_xhat, EdgeGrad& eg) {
+  const int64_t N = g.N, E = g.E;
+  void* st = cur_stream();
+  const bool node_grads = !first || !wq;
+  g_h = node_grads ? at::empty_like(m.h) : Tensor();
+  g_xhat = node_grads ? at::empty_like(m.xhat) : Tensor();
+  Tensor g_vec = at::empty_like(vec);
+  if (wq) {
+    Tensor parts = at::empty({std::max<int64_t>(1, xeq_message_wq_parts_floats(N, E, hy.mul))}, vec.options());
+    const WqPlan& w = g.mirror ? g.fwd : g.rev;
+    const int xl_bwd = (first ? (1 | XEQ_XHAT_HIGHER_L_ZERO) : 1) | (g.mirror ? XEQ_WQ_MIRROR_WALK : 0);
+    XCALL(xeq_message_bwd_wq(N, E, w.n_ranges, (const int32_t*)w.sq.data_ptr(), (const int32_t*)w.sn.data_ptr(),
+                             (const int32_t*)w.win.data_ptr(), (const int32_t*)w.rowptr.data_ptr(),
+                             (const int32_t*)w.pgath.data_ptr(), (const int32_t*)w.qinfo.data_ptr(),
+                             w.basis.data_ptr(), w.dbasis.data_ptr(), m.h.data_ptr(), m.xhat.data_ptr(), g_s.data_ptr(),
+                             g_x.data_ptr(), wq_weights(hy, q), nullptr, hy.B, hy.F, hy.mul, node_grads ? g_h.data_ptr() : nullptr,
+                             node_grads ? g_xhat.data_ptr() : nullptr, parts.data_ptr(), xl_bwd | XEQ_WQ_PACKED_WEIGHTS, st));
+    const int32_t* mirror_map = g.mirror ? (const int32_t*)g.mirror_map.data_ptr() : nullptr;
+    if (eg.defer) {
+      eg.part_sets.push_back(parts);
+      if (first) {
+        std::vector<const void*> pp;
+        for (const Tensor& ps : eg.part_sets) pp.push_back(ps.data_ptr());
+        XCALL(xeq_message_wq_edge_grad_sum(vec.data_ptr(), N, E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
+                                           mirror_map, hy.mul, (int)pp.size(), pp.data(), g_vec.data_ptr(), st));
+        eg.total = g_vec;
+      }
+    } else {
+      XCALL(xeq_message_wq_edge_grad(vec.data_ptr(), N, E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
+                                     mirror_map, hy.mul, parts.data_ptr(), g_vec.data_ptr(), st));
+      eg.total = eg.total.defined() ? eg.total + g_vec : g_vec;
+    }
+  } else {
+    g.sorted_view();
+    // the blocks share ONE dL/dvec buffer: the first to run stores, the others add (XEQ_SB_ACCUM_VEC; ops.message_backward does the same)
+    const bool accum = eg.total.defined();
+    if (!accum) eg.total = g_vec;
+    XCALL(xeq_message_bwd_sb(dcode(vec), N, E, (const int32_t*)g.n_rowptr.data_ptr(), (const int32_t*)g.n_perm.data_ptr(),
+                             (const int64_t*)g.ei.select(0, 0).data_ptr(), g.sb_basis.data_ptr(), g.sb_dbasis.data_ptr(),
+                             m.h.data_ptr(), m.xhat.data_ptr(), g_s.data_ptr(), g_x.data_ptr(), q[4].data_ptr(), q[5].data_ptr(),
+                             hy.B, hy.F, hy.mul, g_h.data_ptr(), g_xhat.data_ptr(), eg.total.data_ptr(), 1 | (accum ? XEQ_SB_ACCUM_VEC : 0), st));
+  }
+}
+
+// fused.NodeBlock.forward (nn/nodeblock.py::node_block_fwd): the update block and, with the next block's parameters qn, the front
+// half of the message block behind it (saved in *mn) in one launch
+void node_block_fwd(const Hyper& hy, const Tensor* q, const Tensor* qn, UpdSaved& u, MsgSaved* mn, Tensor& s, Tensor& x) {
+  const int64_t N = s.size(0);
+  const int F = hy.F, C = hy.C(), D = hy.D(), H = hy.H();
+  const auto fopt = s.options();
+  u.s = s;
+  u.x = x;
+  const NbPacks* pk = nb_packs(q, qn, qn != nullptr);
+  const int64_t NR = xeq_node_block_rows(N);   // internal tensors: whole workgroups, wave-native layout
+  u.uv = at::empty({2 * NR * D}, fopt);
+  u.stats = at::empty({N, 4}, fopt);
+  u.pre = at::empty({NR, F}, fopt);
+  u.a = at::empty({NR, C + 2 * F}, fopt);
+  u.ip = at::empty({NR, F}, fopt);
+  Tensor p_scr = at::empty({NR, C}, fopt);
+  Tensor s_out = at::empty_like(s), x_out = qn ? at::empty_like(x) : Tensor();
+  if (mn) {
+    mn->stats = at::empty({N, 4}, fopt);
+    mn->xhat = at::empty({N * D}, fopt);
+    mn->pre = at::empty({NR, F}, fopt);
+    mn->h = at::empty({N, H}, fopt);
+  }
+  XCALL(xeq_node_block_fwd(N, PF(s), PF(x), PF(q[19]), PF(q[20]), PF(q[21]), PF(q[22]), PF(pk->bias_uv), PF(q[16]), PF(q[18]),
+                           hy.inv_eps, pk->fwd.data_ptr(), PFm(p_scr), PFm(u.uv), PFm(u.stats), PFm(u.pre), PFm(u.a), PFm(u.ip),
+                           PFm(s_out), PFm(x_out), qn ? PF(qn[6]) : nullptr, qn ? PF(qn[7]) : nullptr, qn ? PF(qn[8]) : nullptr,
+                           qn ? PF(qn[9]) : nullptr, qn ? PF(qn[1]) : nullptr, qn ? PF(qn[3]) : nullptr,
+                           mn ? PFm(mn->stats) : nullptr, mn ? PFm(mn->xhat) : nullptr, mn ? PFm(mn->pre) : nullptr,
+                           mn ? PFm(mn->h) : nullptr, cur_stream()));
+  s = s_out;
+  x = x_out;
+  if (mn) {
+    mn->s = s;
+    mn->x = x;
+  }
+}
+
+// fused.NodeBlock.backward (nn/nodeblock.py::node_block_bwd).  pend_gh / pend_gxhat: the gradients of the next block's (h, xhat)
+void node_block_bwd(const Hyper& hy, const Tensor* q, const Tensor* qn, const UpdSaved& u, const MsgSaved* mn, const Tensor& pend_gh,
+                    const Tensor& pend_gxhat, Tensor& g_s, Tensor& g_x) {
+  const int64_t N = u.s.size(0);
+  const int C = hy.C(), D = hy.D();
+  const auto fopt = u.s.options();
+  const bool last_blk = qn == nullptr;
+  const NbPacks* pk = nb_packs(q, qn, !last_blk);
+  Tensor ns = at::empty_like(u.s), nx = at::empty_like(u.x);
+  const int64_t NR = xeq_node_block_rows(N);
+  Tensor gxo = last_blk ? Tensor() : at::empty({NR, D}, fopt);
+  Tensor gp = at::empty({NR, C}, fopt), gv = at::empty({NR, C}, fopt), gw = at::empty({NR, D}, fopt);
+  if (!last_blk && !g_x.defined()) g_x = at::zeros({N, D}, fopt);
+  XCALL(xeq_node_block_bwd(N, PF(pend_gh), PF(pend_gxhat), PF(g_s), PF(g_x), mn ? PF(mn->s) : nullptr, mn ? PF(mn->x) : nullptr,
+                           mn ? PF(mn->stats) : nullptr, mn ? PF(mn->pre) : nullptr, qn ? PF(qn[6]) : nullptr,
+                           qn ? PF(qn[8]) : nullptr, PF(u.uv), PF(u.a), PF(u.ip), PF(u.pre), PF(u.s), PF(u.x), PF(u.stats), PF(q[19]),
+                           PF(q[21]), hy.inv_eps, pk->bwd.data_ptr(), PFm(gxo), PFm(gp), PFm(gv), PFm(gw), PFm(ns), PFm(nx), cur_stream()));
+  g_s = ns;
+  g_x = nx;
+}
+
+// fused.UpdateBlock.forward (nn/xpainn.py:206-231).  last: the energy head reads the scalars only, the last equivariant output has
+// no consumer
+void update_block_fwd(const Hyper& hy, const Tensor* q, bool last, UpdSaved& u, Tensor& s, Tensor& x) {
+  const int64_t N = s.size(0);
+  const int F = hy.F, C = hy.C(), D = hy.D(), dt = dcode(s);
+  const auto fopt = s.options();
+  void* st = cur_stream();
+  u.s = s;
+  u.x = x;
+  Tensor cat = at::empty({N, F + C}, fopt);
+  u.uv = at::empty({2 * N * D}, fopt);
+  Tensor p = at::empty({N, C}, fopt);
+  if (const UvFrag* fr = uv_frag(&q[10], F, hy.mul)) {   // norms -> U, V -> v, p in one matrix-core launch
+    u.stats = at::empty({N, 4}, fopt);
+    XCALL(xeq_update_uv_fwd((const float*)s.data_ptr(), (const float*)x.data_ptr(), hy.layer_norm ? PF(q[19]) : nullptr,
+                            hy.layer_norm ? PF(q[20]) : nullptr, hy.layer_norm ? PF(q[21]) : nullptr,
+                            hy.layer_norm ? PF(q[22]) : nullptr, N, F, hy.mul, hy.layer_norm, PF(fr->w[0]), PF(fr->w[1]), PF(fr->w[2]),
+                            q[13].numel() > 0, hy.inv_eps, (float*)cat.data_ptr(), F + C, (float*)p.data_ptr(),
+                            (float*)u.uv.data_ptr(), (float*)u.stats.data_ptr(), st));
+  } else {
+    NormOut no = norm_fwd(hy, s, x, q[19], q[20], q[21], q[22], cat, F + C);
+    u.stats = no.stats;
+    auto xb = bt_blocks(no.xhat, N, hy.mul, 1), ub = bt_blocks(u.uv, N, hy.mul, 2);
+    for (size_t k = 0; k < xb.size(); ++k) {
+      const Tensor& W = q[10 + xb[k].l];
+      if (xb[k].l == 0 && q[13].numel() > 0) at::addmm_out(ub[k].view, q[13], xb[k].view, W);
+      else at::mm_out(ub[k].view, xb[k].view, W);
+    }
+    XCALL(xeq_uv_reduce_fwd(dt, u.uv.data_ptr(), N, hy.mul, hy.inv_eps, cat.data_ptr(), F + C, F, p.data_ptr(), st));
+  }
+  mlp_and_linear_fwd(cat, q[15], q[16], q[17], q[18], p, q[14], u.pre, u.a, u.ip);
+  Tensor s_out = at::empty_like(s), x_out = last ? Tensor() : at::empty_like(x);
+  XCALL(xeq_update_out_fwd(dt, s.data_ptr(), x.data_ptr(), u.uv.data_ptr(), u.a.data_ptr(), u.ip.data_ptr(), N, F, hy.mul,
+                           s_out.data_ptr(), last ? nullptr : x_out.data_ptr(), st));
+  s = s_out;
+  x = x_out;
+}
+
+// fused.UpdateBlock.backward
+void update_block_bwd(const Hyper& hy, const Tensor* q, const UpdSaved& u, Tensor& g_s, Tensor& g_x) {
+  const int64_t N = u.s.size(0);
+  const int F = hy.F, C = hy.C(), D = hy.D(), dt = dcode(u.s);
+  const auto fopt = u.s.options();
+  void* st = cur_stream();
+  Tensor g_a = at::empty_like(u.a), g_ip = at::empty_like(u.ip);
+  const void* gx_ptr = g_x.defined() ? g_x.data_ptr() : nullptr;
+  XCALL(xeq_update_out_bwd(dt, g_s.data_ptr(), gx_ptr, u.uv.data_ptr(), u.a.data_ptr(), u.ip.data_ptr(), N, F, hy.mul,
+                           g_a.data_ptr(), g_ip.data_ptr(), nullptr, st));
+  Tensor g_p, g_cat;
+  mlp_and_linear_bwd(g_a, u.pre, q[15], q[16], q[17], q[18], g_ip, q[14], g_cat, g_p);
+  Tensor ns, nx;
+  const UvFrag* fr = g_cat.is_contiguous() ? uv_frag(&q[10], F, hy.mul) : nullptr;
+  if (fr) {   // dL/dU, dL/dV -> dL/dxhat (-> reverse of both norms) in one matrix-core launch
+    const bool fuse = N <= UV_BWD_FUSE_NORM_MAX_NODES;
+    Tensor g_xhat;
+    if (fuse) {
+      ns = at::empty_like(u.s);
+      nx = at::empty_like(u.x);
+    } else {
+      g_xhat = at::empty({N * D}, fopt);
+    }
+    XCALL(xeq_update_uv_bwd((const float*)u.uv.data_ptr(), (const float*)g_p.data_ptr(), (const float*)g_cat.data_ptr(), F + C,
+                            (const float*)gx_ptr, (const float*)g_s.data_ptr(), (const float*)u.a.data_ptr(), u.a.size(1),
+                            (const float*)u.s.data_ptr(), (const float*)u.x.data_ptr(), (const float*)u.stats.data_ptr(),
+                            hy.layer_norm ? PF(q[19]) : nullptr, hy.layer_norm ? PF(q[21]) : nullptr, N, F, hy.mul, hy.layer_norm,
+                            PF(fr->wt[0]), PF(fr->wt[1]), PF(fr->wt[2]), hy.inv_eps, fuse ? (float*)ns.data_ptr() : nullptr,
+                            fuse ? (float*)nx.data_ptr() : nullptr, fuse ? nullptr : (float*)g_xhat.data_ptr(), st));
+    if (!fuse) norm_bwd(hy, u.s, u.x, q[19], q[21], u.stats, g_cat, F + C, g_xhat, g_s, g_x, ns, nx);
+  } else {
+    Tensor g_uv = at::empty_like(u.uv);
+    if (!g_x.defined()) g_x = at::zeros({N, D}, fopt);   // the kernel chain wants the tensor
+    XCALL(xeq_uv_reduce_bwd(dt, u.uv.data_ptr(), g_p.data_ptr(), g_cat.data_ptr(), F + C, F, N, hy.mul, hy.inv_eps, g_x.data_ptr(),
+                            u.a.data_ptr(), g_uv.data_ptr(), st));
+    Tensor g_xhat = at::empty({N * D}, fopt);
+    auto gb = bt_blocks(g_xhat, N, hy.mul, 1), gub = bt_blocks(g_uv, N, hy.mul, 2);
+    for (size_t k = 0; k < gb.size(); ++k) at::mm_out(gb[k].view, gub[k].view, q[10 + gb[k].l].t());
+    norm_bwd(hy, u.s, u.x, q[19], q[21], u.stats, g_cat, F + C, g_xhat, g_s, g_x, ns, nx);
+  }
+  g_s = ns;
+  g_x = nx;
+}
+
+// EnergyOut.forward (nn/output.py:114-128) in the three forms of the Python front: fused.EnergyReadout (the head with its whole
+// reverse pass saved as one row per node, ONE launch), fused.EnergyHead (the same kernels layer by layer), else the library GEMMs.
+// t: the head's parameters
+struct HeadSaved {
+  const LinPack* pk = nullptr;
+  bool native = false, fused = false;
+  Tensor pre_o, jac;
+};
+void energy_readout_fwd(const Hyper& hy, const Tensor* t, const Tensor& s, const Tensor& ptr64, bool want_bwd, HeadSaved& hd, Tensor& atomic,
+                        Tensor& energy) {
+  const int64_t N = s.size(0), G = ptr64.numel() - 1;
+  const int F = hy.F, dt = dcode(s);
+  const auto fopt = s.options();
+  void* st = cur_stream();
+  hd.pk = dt == XEQ_F32 && t[0].size(0) % 4 == 0 && t[2].size(0) == 1 ? lin_pack(t[0], t[1]) : nullptr;
+  hd.native = hd.pk != nullptr && hd.pk->bwd.defined();
+  hd.fused = hd.native && s.stride(1) == 1 && s.stride(0) % 4 == 0 && t[1].defined() && t[1].numel() > 0 &&
+             xeq_head_supported(XEQ_F32, F, (int)t[0].size(0));
+  if (hd.fused) {
+    atomic = at::empty({N}, fopt);
+    if (want_bwd) hd.jac = at::empty({N, (int64_t)F}, fopt);
+    XCALL(xeq_head_fwd(s.data_ptr(), s.stride(0), N, F, (int)t[0].size(0), hd.pk->fwd.data_ptr(), hd.pk->bwd.data_ptr(), t[2].data_ptr(),
+                       t[3].data_ptr(), atomic.data_ptr(), hd.jac.defined() ? hd.jac.data_ptr() : nullptr, st));
+  } else if (hd.native) {
+    const Tensor hidden = linear_fwd(s, t[0], t[1], 1, nullptr, &hd.pre_o);
+    atomic = at::empty({N}, fopt);
+    XCALL(xeq_head_dot(hidden.data_ptr(), N, (int)t[0].size(0), t[2].data_ptr(), t[3].data_ptr(), atomic.data_ptr(), st));
+  } else {
+    hd.pre_o = at::addmm(t[1], s, t[0].t());
+    atomic = at::addmm(t[3], at::silu(hd.pre_o), t[2].t()).reshape({-1});
+  }
+  energy = at::empty({G}, fopt);
+  XCALL(xeq_segment_sum(dt, atomic.data_ptr(), (const int64_t*)ptr64.data_ptr(), G, 1, energy.data_ptr(), st));
+}
+
+// EnergyReadout.backward / EnergyHead.backward: dE/ds from dE_i/d atomic_i = 1.  The fused form seeds the pass with MINUS one
+// (minus_one above): everything behind it is then minus the gradient, and forces and virial come out without a negation
+Tensor energy_readout_bwd(const Hyper& hy, const Tensor* t, const HeadSaved& hd) {
+  Tensor g_s;
+  if (hd.fused) {
+    // (seed) x d atomic_i / d s_i, the row saved by the forward launch
+    const int64_t N = hd.jac.size(0);
+    const Tensor seed = minus_one(hd.jac.options());
+    g_s = at::empty_like(hd.jac);
+    XCALL(xeq_head_bwd(hd.jac.data_ptr(), N, hy.F, nullptr, 0, seed.data_ptr(), 0, nullptr, g_s.data_ptr(), cur_stream()));
+  } else if (hd.native) {
+    const int64_t N = hd.pre_o.size(0);
+    Tensor g_hidden = at::empty_like(hd.pre_o);
+    XCALL(xeq_head_bwd_hidden(hd.pre_o.data_ptr(), N, (int)hd.pre_o.size(1), t[2].data_ptr(), nullptr, g_hidden.data_ptr(), cur_stream()));
+    g_s = linear_bwd(g_hidden, t[0], t[1]);
+  } else {
+    g_s = at::mm(at::silu_backward(t[2].expand({hd.pre_o.size(0), t[2].size(1)}), hd.pre_o), t[0]);
+  }
+  return g_s;
+}
+
+// ops.EdgeVectors.backward: dL/dvec -> dL/dpos (forces) and sym(sum_e vec_e (x) dE/dvec_e) per graph (virial).  negated: g_vec is
+// minus the gradient already; undefined: zero
+void edge_vectors_bwd_and_virial(Graph& g, const Tensor& vec, Tensor g_vec, const Tensor& ptr64, bool compute_forces,
+                                 bool compute_virial, bool negated, Tensor& forces, Tensor& virial) {
+  if (!g_vec.defined()) g_vec = at::zeros_like(vec);
+  g_vec = g_vec.contiguous();
+  const int64_t G = ptr64.numel() - 1;
+  const auto fopt = vec.options();
+  const int dt = dcode(vec);
+  void* st = cur_stream();
+  if (compute_forces) {
+    Tensor grad_pos = at::empty({g.N, 3}, fopt);
+    XCALL(xeq_edge_vectors_bwd(dt, g_vec.data_ptr(), g.N, (const int32_t*)g.c_rowptr.data_ptr(),
+                               g.c_perm.defined() ? (const int32_t*)g.c_perm.data_ptr() : nullptr,
+                               (const int32_t*)g.rev_rowptr().data_ptr(), (const int32_t*)g.rev_perm().data_ptr(), grad_pos.data_ptr(), st));
+    forces = negated ? grad_pos : grad_pos.neg();
+  }
+  if (compute_virial) {   // edges walked center-sorted
+    Tensor outer = (vec.unsqueeze(2) * g_vec.unsqueeze(1)).reshape({-1, 9});
+    if (g.c_perm.defined()) outer = outer.index_select(0, g.c_perm.to(at::kLong));
+    const Tensor eptr = g.c_rowptr.to(at::kLong).index_select(0, ptr64).contiguous();
+    outer = outer.contiguous();
+    Tensor msum = at::empty({G, 9}, fopt);
+    XCALL(xeq_segment_sum(dt, outer.data_ptr(), (const int64_t*)eptr.data_ptr(), G, 9, msum.data_ptr(), st));
+    msum = msum.view({G, 3, 3});
+    virial = 0.5 * (msum + msum.transpose(1, 2));
+    if (!negated) virial = virial.neg();
+  }
+}
 
 // ---------------------------------------------------------------------------------------------- the evaluation
 std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_numbers, const Tensor& edge_index, const Tensor& ptr,
@@ -617,19 +958,7 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
   need_hip(pos_in, "pos");
   need_hip(edge_index, "edge_index");
   TORCH_CHECK(ip.size() >= 10 && fp.size() >= 2, "xeq::xpainn_eval: malformed hyper-parameter lists");
-  Hyper hy;
-  hy.F = (int)ip[0];
-  hy.mul[0] = (int)ip[1];
-  hy.mul[1] = (int)ip[2];
-  hy.mul[2] = (int)ip[3];
-  hy.B = (int)ip[4];
-  hy.blocks = (int)ip[5];
-  hy.rbf_kind = (int)ip[6];
-  hy.cutoff_kind = (int)ip[7];
-  hy.layer_norm = (int)ip[8];
-  hy.embed_kind = (int)ip[9];
-  hy.cutoff = fp[0];
-  hy.inv_eps = fp[1];
+  const Hyper hy{(int)ip[0], {(int)ip[1], (int)ip[2], (int)ip[3]}, (int)ip[4], (int)ip[5], (int)ip[6], (int)ip[7], (int)ip[8], (int)ip[9], fp[0], fp[1]};
   // charge / spin embeddings (nn/electronic.py): flags at the end of iparams, parameters behind the head tail
   const bool el_charge = ip.size() >= 12 && ip[10] != 0, el_spin = ip.size() >= 12 && ip[11] != 0;
   const int64_t n_prm = P_BLOCK0 + (int64_t)P_PER_BLOCK * hy.blocks + 4 + P_ELECTRONIC * ((int)el_charge + (int)el_spin);
@@ -639,8 +968,7 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
   const auto fopt = pos.options();
   const int dt = dcode(pos);
   const int64_t N = pos.size(0), G = ptr.numel() - 1;
-  const int C = hy.C(), D = hy.D(), H = hy.H(), F = hy.F;
-  const int32_t mul[3] = {hy.mul[0], hy.mul[1], hy.mul[2]};
+  const int F = hy.F;
   const Tensor ptr64 = ptr.to(at::kLong).contiguous();
   void* st = cur_stream();
   // a module runs when the model has it AND the per-graph value is given (the module is the identity otherwise, electronic.py:31-32)
@@ -680,410 +1008,69 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
 
   // ---- which message kernels (ops.select_message_impl, without the generic form).  The family rule is the C ABI's
   // (xeq_message_auto_family: the Python modules ask the same function); this operator carries the wq and sb sequences
-  int impl;
-  const int family = xeq_message_auto_family(dt, N, E, hy.B, F, mul);
-  if (family == XEQ_FAMILY_WQ) impl = 0;
-  else if (family == XEQ_FAMILY_SB) impl = 1;
-  else TORCH_CHECK(false, "xeq::xpainn_eval: this configuration / size needs the generic message kernels: use the Python modules");
+  const int family = xeq_message_auto_family(dt, N, E, hy.B, F, hy.mul);
+  TORCH_CHECK(family == XEQ_FAMILY_WQ || family == XEQ_FAMILY_SB,
+              "xeq::xpainn_eval: this configuration / size needs the generic message kernels: use the Python modules");
+  const bool wq = family == XEQ_FAMILY_WQ;
+  const bool want_bwd = compute_forces || compute_virial;
+  auto Q = [&](int b) { return &prm[P_BLOCK0 + P_PER_BLOCK * b]; };   // block b's parameters; b = blocks: the head's
 
-  // ---- embedding (nn/xpainn.py:55-83) -- and, where the table form covers the layout, the first block's norms and scalar_mlp with it:
-  // one gather by atomic number from per-element rows (element_front above; nn/fused.py::first_block_front)
-  std::vector<MsgSaved> msv(hy.blocks);
+  // ---- embedding, charge / spin embeddings, the first block's front half where the embedding's gather has not made it, edge records:
+  // the order of the Python front (the record launch sits in ops.message_forward, behind MessageBlock's norms and scalar_mlp)
+  std::vector<MsgSaved> msv(hy.blocks + 1);   // (+ 1: embed_and_first_front takes a reference also when the model has no block)
   std::vector<UpdSaved> usv(hy.blocks);
-  Tensor s;
-  Tensor x = at::zeros({N, D}, fopt);
-  bool front_done = false;
-  const bool z_int = atomic_numbers.scalar_type() == at::kInt || atomic_numbers.scalar_type() == at::kLong;
-  const bool table_form = hy.embed_kind == 0 && hy.blocks > 0 && dt == XEQ_F32 && hy.layer_norm && hy.mul[0] == F &&
-                          prm[0].scalar_type() == at::kFloat && prm[0].dim() == 2 && prm[0].stride(1) == 1 && prm[0].stride(0) % 4 == 0 &&
-                          lin_pack(prm[1], prm[2]) != nullptr;
-  if (table_form && run_el) {
-    // behind a charge / spin embedding the first block's scalars no longer depend on the element alone: the node scalars are gathered
-    // from the per-element rows (nn/xpainn.py::XEmbedding.forward, ELEMENT_ROWS) and the first block takes its per-node launches
-    const ElementFront* ef = element_front(hy, prm[0], prm[1], prm[2], &prm[P_BLOCK0]);
-    s = ef->rows_s.index_select(0, (z_int ? atomic_numbers : atomic_numbers.to(at::kLong)));
-  } else if (table_form) {
-    const ElementFront* ef = element_front(hy, prm[0], prm[1], prm[2], &prm[P_BLOCK0]);
-    const Tensor z = (z_int ? atomic_numbers : atomic_numbers.to(at::kLong)).contiguous();
-    MsgSaved& m = msv[0];
-    s = at::empty({N, (int64_t)F}, fopt);
-    m.h = at::empty({N, (int64_t)H}, fopt);
-    m.xhat = at::empty({N * (int64_t)D}, fopt);
-    // the wq kernels never read xhat's l > 0 blocks behind the embedding (XEQ_XHAT_HIGHER_L_ZERO): those are then not even written
-    XCALL(xeq_first_block_front(z.data_ptr(), z.scalar_type() == at::kLong, N, ef->rows_s.size(0), ef->rows_s.data_ptr(),
-                                ef->rows_h.data_ptr(), ef->rows_x0.data_ptr(), F, H, impl == 0 ? F : D, s.data_ptr(), m.h.data_ptr(),
-                                m.xhat.data_ptr(), st));
-    m.s = s;
-    m.x = x;
-    front_done = true;
-  } else if (hy.embed_kind == 0) {
-    const Tensor z32 = atomic_numbers.to(at::kInt).contiguous();
-    s = linear_fwd(prm[0], prm[1], prm[2], 0, &z32);   // table lookup + Linear in one launch (nn/xpainn.py::XEmbedding._embed)
-  }
-  else s = prm[0].index_select(0, atomic_numbers.to(at::kLong));
-
-  // ---- charge, then spin embedding (nn/electronic.py, csrc/xeq_electronic.hip): two launches each, before the first block
+  Tensor x = at::zeros({N, hy.D()}, fopt);
+  Tensor s = embed_and_first_front(hy, prm, atomic_numbers, x, wq, run_el, msv[0]);
   if (run_el) {
-    int64_t base = P_BLOCK0 + (int64_t)P_PER_BLOCK * hy.blocks + 4;
-    for (int kind = 0; kind < 2; ++kind) {
-      const bool has = kind == 0 ? el_charge : el_spin;
-      const bool run = kind == 0 ? run_charge : run_spin;
-      const Tensor* e = &prm[base];
-      if (has) base += P_ELECTRONIC;
-      if (!run) continue;
-      const Tensor total = (kind == 0 ? *charge_o : *spin_o).reshape({-1}).to(at::kFloat).contiguous();
-      TORCH_CHECK(total.numel() == G, "xeq::xpainn_eval: ", kind == 0 ? "charge" : "spin", " has ", total.numel(), " values for ", G, " graphs");
-      const LinPack* pq = lin_pack(e[0], e[1]);
-      const LinPack* p1 = lin_pack(e[4], Tensor());
-      const LinPack* p2 = lin_pack(e[5], Tensor());
-      TORCH_CHECK(pq && p1 && p2, "xeq::xpainn_eval: the electronic module's weights cannot be packed");
-      s = s.contiguous();
-      Tensor attn = at::empty({N}, fopt), s_out = at::empty({N, (int64_t)F}, fopt);
-      const Tensor wk = e[2].contiguous(), wv = e[3].contiguous();
-      XCALL(xeq_electronic_fwd(kind, s.data_ptr(), s.stride(0), N, F, (const int64_t*)ptr64.data_ptr(), G, total.data_ptr(),
-                               pq->fwd.data_ptr(), wk.data_ptr(), wv.data_ptr(), p1->fwd.data_ptr(), p2->fwd.data_ptr(), attn.data_ptr(),
-                               s_out.data_ptr(), st));
-      s = s_out;
-    }
+    const bool has[2] = {el_charge, el_spin};
+    const Tensor* const total[2] = {run_charge ? &*charge_o : nullptr, run_spin ? &*spin_o : nullptr};
+    s = electronic_fwd(hy, &prm[P_BLOCK0 + P_PER_BLOCK * hy.blocks + 4], has, total, s, ptr64);
   }
-  const Tensor& p0 = prm[3];
-  const Tensor& p1 = prm[4];
+  if (hy.blocks > 0 && !msv[0].h.defined()) message_front_fwd(hy, Q(0), s, x, msv[0]);
+  // (wq, mirror walk: the reverse pass runs over the same plan, its derivative records come out of the same launch)
+  edge_basis(hy, g, vec, prm[3], prm[4], wq, false, g.mirror && want_bwd);
 
-  // ---- the first block's norms and scalar MLP where the table form above does not cover the layout (per-node launches)
-  if (hy.blocks > 0 && !front_done) {
-    const Tensor* q = &prm[P_BLOCK0];
-    MsgSaved& m = msv[0];
-    m.s = s;
-    m.x = x;
-    NormOut no = norm_fwd(hy, s, x, q[6], q[7], q[8], q[9], Tensor(), 0);
-    m.stats = no.stats;
-    m.xhat = no.xhat;
-    mlp_fwd(no.shat, q[0], q[1], q[2], q[3], m.pre, m.h);
-  }
-  if (impl == 0) {
-    build_wq_plan(g, false, g.fwd);
-    g.fwd.basis = at::empty({g.fwd.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
-    // a reverse pass over the same plan (mirror walk) follows: its derivative records come out of the same launch (ops.message_forward)
-    if (g.mirror && (compute_forces || compute_virial)) g.fwd.dbasis = at::empty({g.fwd.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
-    XCALL(xeq_edge_basis_wq(vec.data_ptr(), N, E, (const int32_t*)g.fwd.qptr.data_ptr(), (const int32_t*)g.fwd.peid.data_ptr(),
-                            hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1), g.fwd.basis.data_ptr(),
-                            g.fwd.dbasis.defined() ? g.fwd.dbasis.data_ptr() : nullptr, st));
-  } else {
-    const int w = xeq_edge_basis_width(hy.B);
-    g.sb_basis = at::empty({E, w}, fopt);
-    g.sb_dbasis = at::empty({E, w}, fopt);
-    XCALL(xeq_edge_basis(dt, vec.data_ptr(), E, hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1),
-                         g.sb_basis.data_ptr(), g.sb_dbasis.data_ptr(), st));
-  }
-
-  // the wq kernels take rbf_lin's rows from the packed copy (one per weight version)
-  auto wq_w = [&](const Tensor* q) {
-    const Tensor* pk = wq_weight_pack(q[4], q[5], hy.B, F, mul);
-    TORCH_CHECK(pk != nullptr, "xeq::xpainn_eval: rbf_lin weights cannot be packed for the wq kernels");
-    return pk;
-  };
-  // fused node blocks: f32, the default layout, layer norms on (nn/nodeblock.py::supported)
-  const bool nb_ok = dt == XEQ_F32 && hy.layer_norm && xeq_node_block_supported(XEQ_F32, F, mul) && xeq_node_block_auto(N);
+  // ---- the blocks.  Fused node blocks: f32, the default layout, layer norms on (nn/nodeblock.py::supported)
+  const bool nb_ok = dt == XEQ_F32 && hy.layer_norm && xeq_node_block_supported(XEQ_F32, F, hy.mul) && xeq_node_block_auto(N);
   for (int b = 0; b < hy.blocks; ++b) {
-    const Tensor* q = &prm[P_BLOCK0 + P_PER_BLOCK * b];
-    {  // ---- XPainnMessage.forward (nn/xpainn.py:128-161; nn/fused.py::MessageBlock)
-      MsgSaved& m = msv[b];
-      if (b > 0 && !m.h.defined()) {   // (block 0: done above; behind a fused node block: done by its launch)
-        m.s = s;
-        m.x = x;
-        NormOut no = norm_fwd(hy, s, x, q[6], q[7], q[8], q[9], Tensor(), 0);
-        m.stats = no.stats;
-        m.xhat = no.xhat;
-        mlp_fwd(no.shat, q[0], q[1], q[2], q[3], m.pre, m.h);
-      }
-      Tensor s_out = at::empty_like(s), x_out = at::empty_like(x);
-      m.impl = impl;
-      if (impl == 0) {
-        XCALL(xeq_message_fwd_wq(N, E, g.fwd.n_ranges, (const int32_t*)g.fwd.sq.data_ptr(), (const int32_t*)g.fwd.sn.data_ptr(),
-                                 (const int32_t*)g.fwd.win.data_ptr(), (const int32_t*)g.fwd.rowptr.data_ptr(),
-                                 (const int32_t*)g.fwd.pgath.data_ptr(), (const int32_t*)g.fwd.qinfo.data_ptr(), g.fwd.basis.data_ptr(),
-                                 m.h.data_ptr(), m.xhat.data_ptr(), s.data_ptr(), x.data_ptr(), wq_w(q)->data_ptr(), nullptr, hy.B,
-                                 F, mul, s_out.data_ptr(), x_out.data_ptr(), (b == 0 ? (1 | XEQ_XHAT_HIGHER_L_ZERO) : 1) | XEQ_WQ_PACKED_WEIGHTS, st));   // block 0: x = 0
-      } else {
-        XCALL(xeq_message_fwd_sb(dt, N, E, (const int32_t*)g.c_rowptr.data_ptr(),
-                                 g.c_perm.defined() ? (const int32_t*)g.c_perm.data_ptr() : nullptr,
-                                 (const int64_t*)g.ei.select(0, 1).data_ptr(), g.sb_basis.data_ptr(), m.h.data_ptr(), m.xhat.data_ptr(),
-                                 s.data_ptr(), x.data_ptr(), q[4].data_ptr(), q[5].data_ptr(), hy.B, F, mul, s_out.data_ptr(),
-                                 x_out.data_ptr(), 1, st));
-      }
-      s = s_out;
-      x = x_out;
-    }
-    {  // ---- XPainnUpdate.forward (nn/xpainn.py:206-231; nn/fused.py::UpdateBlock)
-      UpdSaved& u = usv[b];
-      u.s = s;
-      u.x = x;
-      const bool last_blk = b == hy.blocks - 1;
-      if (nb_ok) {   // the whole block, and the front half of the next message block, in one launch (nn/fused.py::NodeBlock)
-        const Tensor* qn = last_blk ? nullptr : &prm[P_BLOCK0 + P_PER_BLOCK * (b + 1)];
-        const NbPacks* pk = nb_packs(q, qn, !last_blk);
-        auto fp = [](const Tensor& t) { return t.defined() ? (const float*)t.data_ptr() : nullptr; };
-        auto fpm = [](Tensor& t) { return t.defined() ? (float*)t.data_ptr() : nullptr; };
-        const int64_t NR = xeq_node_block_rows(N);   // internal tensors: whole workgroups, wave-native layout
-        u.uv = at::empty({2 * NR * D}, fopt);
-        u.stats = at::empty({N, 4}, fopt);
-        u.pre = at::empty({NR, F}, fopt);
-        u.a = at::empty({NR, C + 2 * F}, fopt);
-        u.ip = at::empty({NR, F}, fopt);
-        Tensor p_scr = at::empty({NR, C}, fopt);
-        Tensor s_out = at::empty_like(s), x_out = last_blk ? Tensor() : at::empty_like(x);
-        MsgSaved* mn = last_blk ? nullptr : &msv[b + 1];
-        if (mn) {
-          mn->stats = at::empty({N, 4}, fopt);
-          mn->xhat = at::empty({N * D}, fopt);
-          mn->pre = at::empty({NR, F}, fopt);
-          mn->h = at::empty({N, H}, fopt);
-        }
-        XCALL(xeq_node_block_fwd(N, fp(s), fp(x), fp(q[19]), fp(q[20]), fp(q[21]), fp(q[22]), fp(pk->bias_uv), fp(q[16]), fp(q[18]),
-                                 hy.inv_eps, pk->fwd.data_ptr(), fpm(p_scr), fpm(u.uv), fpm(u.stats), fpm(u.pre), fpm(u.a), fpm(u.ip),
-                                 fpm(s_out), fpm(x_out), qn ? fp(qn[6]) : nullptr, qn ? fp(qn[7]) : nullptr, qn ? fp(qn[8]) : nullptr,
-                                 qn ? fp(qn[9]) : nullptr, qn ? fp(qn[1]) : nullptr, qn ? fp(qn[3]) : nullptr,
-                                 mn ? fpm(mn->stats) : nullptr, mn ? fpm(mn->xhat) : nullptr, mn ? fpm(mn->pre) : nullptr,
-                                 mn ? fpm(mn->h) : nullptr, st));
-        s = s_out;
-        x = x_out;
-        if (mn) {
-          mn->s = s;
-          mn->x = x;
-        }
-        continue;
-      }
-      Tensor cat = at::empty({N, F + C}, fopt);
-      u.uv = at::empty({2 * N * D}, fopt);
-      Tensor p = at::empty({N, C}, fopt);
-      if (const UvFrag* fr = uv_frag(&q[10], F, mul)) {   // norms -> U, V -> v, p in one matrix-core launch
-        u.stats = at::empty({N, 4}, fopt);
-        auto fp = [](const Tensor& t) { return t.defined() ? (const float*)t.data_ptr() : nullptr; };
-        XCALL(xeq_update_uv_fwd((const float*)s.data_ptr(), (const float*)x.data_ptr(), hy.layer_norm ? fp(q[19]) : nullptr,
-                                hy.layer_norm ? fp(q[20]) : nullptr, hy.layer_norm ? fp(q[21]) : nullptr,
-                                hy.layer_norm ? fp(q[22]) : nullptr, N, F, mul, hy.layer_norm, fp(fr->w[0]), fp(fr->w[1]), fp(fr->w[2]),
-                                q[13].numel() > 0, hy.inv_eps, (float*)cat.data_ptr(), F + C, (float*)p.data_ptr(),
-                                (float*)u.uv.data_ptr(), (float*)u.stats.data_ptr(), st));
-      } else {
-        NormOut no = norm_fwd(hy, s, x, q[19], q[20], q[21], q[22], cat, F + C);
-        u.stats = no.stats;
-        auto xb = bt_blocks(no.xhat, N, hy.mul, 1), ub = bt_blocks(u.uv, N, hy.mul, 2);
-        for (size_t k = 0; k < xb.size(); ++k) {
-          const Tensor& W = q[10 + xb[k].l];
-          if (xb[k].l == 0 && q[13].numel() > 0) at::addmm_out(ub[k].view, q[13], xb[k].view, W);
-          else at::mm_out(ub[k].view, xb[k].view, W);
-        }
-        XCALL(xeq_uv_reduce_fwd(dt, u.uv.data_ptr(), N, mul, hy.inv_eps, cat.data_ptr(), F + C, F, p.data_ptr(), st));
-      }
-      mlp_and_linear_fwd(cat, q[15], q[16], q[17], q[18], p, q[14], u.pre, u.a, u.ip);
-      const bool last = b == hy.blocks - 1;   // the energy head reads the scalars only: the last equivariant output has no consumer
-      Tensor s_out = at::empty_like(s), x_out = last ? Tensor() : at::empty_like(x);
-      XCALL(xeq_update_out_fwd(dt, s.data_ptr(), x.data_ptr(), u.uv.data_ptr(), u.a.data_ptr(), u.ip.data_ptr(), N, F, mul,
-                               s_out.data_ptr(), last ? nullptr : x_out.data_ptr(), st));
-      s = s_out;
-      x = x_out;
-    }
+    const bool last = b == hy.blocks - 1;
+    message_block_fwd(hy, g, Q(b), wq, b == 0, msv[b], s, x);
+    if (nb_ok) node_block_fwd(hy, Q(b), last ? nullptr : Q(b + 1), usv[b], last ? nullptr : &msv[b + 1], s, x);
+    else update_block_fwd(hy, Q(b), last, usv[b], s, x);
   }
-  // ---- EnergyOut.forward (nn/output.py:114-128)
-  const Tensor* t = &prm[P_BLOCK0 + P_PER_BLOCK * hy.blocks];
-  // (nn/fused.py::EnergyHead is the Python twin: the same kernels where they take the layer, the library GEMMs elsewhere)
-  const LinPack* head_pk = dt == XEQ_F32 && t[0].size(0) % 4 == 0 && t[2].size(0) == 1 ? lin_pack(t[0], t[1]) : nullptr;
-  const bool head_native = head_pk != nullptr && head_pk->bwd.defined();
-  Tensor pre_o, atomic, jac;
-  // round 5: the head with its whole reverse pass saved as one row per node, in ONE launch (nn/fused.py::EnergyReadout is the twin)
-  const bool head_fused = head_native && s.stride(1) == 1 && s.stride(0) % 4 == 0 && t[1].defined() && t[1].numel() > 0 &&
-                          xeq_head_supported(XEQ_F32, F, (int)t[0].size(0));
-  if (head_fused) {
-    atomic = at::empty({N}, fopt);
-    if (compute_forces || compute_virial) jac = at::empty({N, (int64_t)F}, fopt);
-    XCALL(xeq_head_fwd(s.data_ptr(), s.stride(0), N, F, (int)t[0].size(0), head_pk->fwd.data_ptr(), head_pk->bwd.data_ptr(), t[2].data_ptr(),
-                       t[3].data_ptr(), atomic.data_ptr(), jac.defined() ? jac.data_ptr() : nullptr, st));
-  } else if (head_native) {
-    const Tensor hidden = linear_fwd(s, t[0], t[1], 1, nullptr, &pre_o);
-    atomic = at::empty({N}, fopt);
-    XCALL(xeq_head_dot(hidden.data_ptr(), N, (int)t[0].size(0), t[2].data_ptr(), t[3].data_ptr(), atomic.data_ptr(), st));
-  } else {
-    pre_o = at::addmm(t[1], s, t[0].t());
-    atomic = at::addmm(t[3], at::silu(pre_o), t[2].t()).reshape({-1});
-  }
-  Tensor energy = at::empty({G}, fopt);
-  XCALL(xeq_segment_sum(dt, atomic.data_ptr(), (const int64_t*)ptr64.data_ptr(), G, 1, energy.data_ptr(), st));
+  HeadSaved head;
+  Tensor atomic, energy;
+  energy_readout_fwd(hy, Q(hy.blocks), s, ptr64, want_bwd, head, atomic, energy);
 
   Tensor forces, virial;
-  if (compute_forces || compute_virial) {
+  if (want_bwd) {
     // ---- explicit reverse pass: dE/ds of the head, then the blocks backwards, then the edge geometry (nn/basic.py:143-199)
-    Tensor g_s;   // dE_i/d atomic_i = 1
-    const bool neg_seed = head_fused;   // the reverse pass runs on MINUS the gradient: forces (and the virial) come out without a negation
-    if (head_fused) {
-      // (seed) x d atomic_i / d s_i, the row saved by the forward launch (nn/fused.py::EnergyReadout.backward)
-      const Tensor seed = minus_one(fopt);
-      g_s = at::empty_like(jac);
-      XCALL(xeq_head_bwd(jac.data_ptr(), N, F, nullptr, 0, seed.data_ptr(), 0, nullptr, g_s.data_ptr(), st));
-    } else if (head_native) {
-      Tensor g_hidden = at::empty_like(pre_o);
-      XCALL(xeq_head_bwd_hidden(pre_o.data_ptr(), N, (int)pre_o.size(1), t[2].data_ptr(), nullptr, g_hidden.data_ptr(), st));
-      g_s = linear_bwd(g_hidden, t[0], t[1]);
-    } else {
-      g_s = at::mm(at::silu_backward(t[2].expand({N, t[2].size(1)}), pre_o), t[0]);
-    }
+    Tensor g_s = energy_readout_bwd(hy, Q(hy.blocks), head);
     Tensor g_x;   // undefined = zero: the head reads the scalars only, the last block's equivariant output has no consumer
-    Tensor g_vec_total;
-    // round 5: the wq blocks' partials are added up and the chain rule to dL/dvec runs ONCE behind the last block of the reverse pass
-    // (xeq_message_wq_edge_grad_sum; ops.EdgeGradDeferral is the Python twin, same order: last block first)
-    const bool defer_edge_grad = impl == 0 && hy.blocks <= XEQ_WQ_MAX_PART_SETS;
-    std::vector<Tensor> part_sets;
-    if (impl == 0 && !g.mirror) {
-      build_wq_plan(g, true, g.rev);
-      g.rev.basis = at::empty({g.rev.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
-      g.rev.dbasis = at::empty({g.rev.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
-      XCALL(xeq_edge_basis_wq(vec.data_ptr(), N, E, (const int32_t*)g.rev.qptr.data_ptr(), (const int32_t*)g.rev.peid.data_ptr(),
-                              hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1), g.rev.basis.data_ptr(),
-                              g.rev.dbasis.data_ptr(), st));
-    }
+    EdgeGrad eg;
+    eg.defer = wq && hy.blocks <= XEQ_WQ_MAX_PART_SETS;
+    if (wq && !g.mirror) edge_basis(hy, g, vec, prm[3], prm[4], true, true, true);
     Tensor pend_gh, pend_gxhat;   // gradients of the next block's (h, xhat): reversed by the node block of the update in front of it
     for (int b = hy.blocks - 1; b >= 0; --b) {
-      const Tensor* q = &prm[P_BLOCK0 + P_PER_BLOCK * b];
-      if (nb_ok) {  // NodeBlock.backward
-        const UpdSaved& u = usv[b];
-        const bool last_blk = b == hy.blocks - 1;
-        const Tensor* qn = last_blk ? nullptr : &prm[P_BLOCK0 + P_PER_BLOCK * (b + 1)];
-        const NbPacks* pk = nb_packs(q, qn, !last_blk);
-        const MsgSaved* mn = last_blk ? nullptr : &msv[b + 1];
-        auto fp = [](const Tensor& t) { return t.defined() ? (const float*)t.data_ptr() : nullptr; };
-        Tensor ns = at::empty_like(u.s), nx = at::empty_like(u.x);
-        const int64_t NR = xeq_node_block_rows(N);
-        Tensor gxo = last_blk ? Tensor() : at::empty({NR, D}, fopt);
-        Tensor gp = at::empty({NR, C}, fopt), gv = at::empty({NR, C}, fopt), gw = at::empty({NR, D}, fopt);
-        if (!last_blk && !g_x.defined()) g_x = at::zeros({N, D}, fopt);
-        XCALL(xeq_node_block_bwd(N, fp(pend_gh), fp(pend_gxhat), fp(g_s), fp(g_x), mn ? fp(mn->s) : nullptr, mn ? fp(mn->x) : nullptr,
-                                 mn ? fp(mn->stats) : nullptr, mn ? fp(mn->pre) : nullptr, qn ? fp(qn[6]) : nullptr,
-                                 qn ? fp(qn[8]) : nullptr, fp(u.uv), fp(u.a), fp(u.ip), fp(u.pre), fp(u.s), fp(u.x), fp(u.stats), fp(q[19]),
-                                 fp(q[21]), hy.inv_eps, pk->bwd.data_ptr(), gxo.defined() ? (float*)gxo.data_ptr() : nullptr,
-                                 (float*)gp.data_ptr(), (float*)gv.data_ptr(), (float*)gw.data_ptr(), (float*)ns.data_ptr(),
-                                 (float*)nx.data_ptr(), st));
-        g_s = ns;
-        g_x = nx;
+      const bool last = b == hy.blocks - 1;
+      if (nb_ok) {
+        node_block_bwd(hy, Q(b), last ? nullptr : Q(b + 1), usv[b], last ? nullptr : &msv[b + 1], pend_gh, pend_gxhat, g_s, g_x);
         pend_gh = Tensor();
         pend_gxhat = Tensor();
-      } else {  // UpdateBlock.backward
-        const UpdSaved& u = usv[b];
-        Tensor g_a = at::empty_like(u.a), g_ip = at::empty_like(u.ip);
-        const void* gx_ptr = g_x.defined() ? g_x.data_ptr() : nullptr;
-        XCALL(xeq_update_out_bwd(dt, g_s.data_ptr(), gx_ptr, u.uv.data_ptr(), u.a.data_ptr(), u.ip.data_ptr(), N, F, mul,
-                                 g_a.data_ptr(), g_ip.data_ptr(), nullptr, st));
-        Tensor g_p, g_cat;
-        mlp_and_linear_bwd(g_a, u.pre, q[15], q[16], q[17], q[18], g_ip, q[14], g_cat, g_p);
-        Tensor ns, nx;
-        const UvFrag* fr = g_cat.is_contiguous() ? uv_frag(&q[10], F, mul) : nullptr;
-        if (fr) {   // dL/dU, dL/dV -> dL/dxhat (-> reverse of both norms) in one matrix-core launch
-          auto fp = [](const Tensor& t) { return t.defined() ? (const float*)t.data_ptr() : nullptr; };
-          const bool fuse = N <= UV_BWD_FUSE_NORM_MAX_NODES;
-          Tensor g_xhat;
-          if (fuse) {
-            ns = at::empty_like(u.s);
-            nx = at::empty_like(u.x);
-          } else {
-            g_xhat = at::empty({N * D}, fopt);
-          }
-          XCALL(xeq_update_uv_bwd((const float*)u.uv.data_ptr(), (const float*)g_p.data_ptr(), (const float*)g_cat.data_ptr(), F + C,
-                                  (const float*)gx_ptr, (const float*)g_s.data_ptr(), (const float*)u.a.data_ptr(), u.a.size(1),
-                                  (const float*)u.s.data_ptr(), (const float*)u.x.data_ptr(), (const float*)u.stats.data_ptr(),
-                                  hy.layer_norm ? fp(q[19]) : nullptr, hy.layer_norm ? fp(q[21]) : nullptr, N, F, mul, hy.layer_norm,
-                                  fp(fr->wt[0]), fp(fr->wt[1]), fp(fr->wt[2]), hy.inv_eps, fuse ? (float*)ns.data_ptr() : nullptr,
-                                  fuse ? (float*)nx.data_ptr() : nullptr, fuse ? nullptr : (float*)g_xhat.data_ptr(), st));
-          if (!fuse) norm_bwd(hy, u.s, u.x, q[19], q[21], u.stats, g_cat, F + C, g_xhat, g_s, g_x, ns, nx);
-        } else {
-          Tensor g_uv = at::empty_like(u.uv);
-          if (!g_x.defined()) g_x = at::zeros({N, D}, fopt);   // the kernel chain wants the tensor
-          XCALL(xeq_uv_reduce_bwd(dt, u.uv.data_ptr(), g_p.data_ptr(), g_cat.data_ptr(), F + C, F, N, mul, hy.inv_eps, g_x.data_ptr(),
-                                  u.a.data_ptr(), g_uv.data_ptr(), st));
-          Tensor g_xhat = at::empty({N * D}, fopt);
-          auto gb = bt_blocks(g_xhat, N, hy.mul, 1), gub = bt_blocks(g_uv, N, hy.mul, 2);
-          for (size_t k = 0; k < gb.size(); ++k) at::mm_out(gb[k].view, gub[k].view, q[10 + gb[k].l].t());
-          norm_bwd(hy, u.s, u.x, q[19], q[21], u.stats, g_cat, F + C, g_xhat, g_s, g_x, ns, nx);
-        }
-        g_s = ns;
-        g_x = nx;
+      } else {
+        update_block_bwd(hy, Q(b), usv[b], g_s, g_x);
       }
-      {  // MessageBlock.backward
-        const MsgSaved& m = msv[b];
-        const bool node_grads = b > 0 || m.impl != 0;   // first block: only dL/dvec leaves it, the wq kernel then stores no node gradients
-        Tensor g_h = node_grads ? at::empty_like(m.h) : Tensor(), g_xhat = node_grads ? at::empty_like(m.xhat) : Tensor();
-        Tensor g_vec = at::empty_like(vec);
-        if (m.impl == 0) {
-          Tensor parts = at::empty({std::max<int64_t>(1, xeq_message_wq_parts_floats(N, E, mul))}, fopt);
-          const WqPlan& w = g.mirror ? g.fwd : g.rev;
-          const int xl_bwd = (b == 0 ? (1 | XEQ_XHAT_HIGHER_L_ZERO) : 1) | (g.mirror ? XEQ_WQ_MIRROR_WALK : 0);
-          XCALL(xeq_message_bwd_wq(N, E, w.n_ranges, (const int32_t*)w.sq.data_ptr(), (const int32_t*)w.sn.data_ptr(),
-                                   (const int32_t*)w.win.data_ptr(), (const int32_t*)w.rowptr.data_ptr(),
-                                   (const int32_t*)w.pgath.data_ptr(), (const int32_t*)w.qinfo.data_ptr(),
-                                   w.basis.data_ptr(), w.dbasis.data_ptr(), m.h.data_ptr(), m.xhat.data_ptr(), g_s.data_ptr(),
-                                   g_x.data_ptr(), wq_w(q)->data_ptr(), nullptr, hy.B, F, mul, node_grads ? g_h.data_ptr() : nullptr,
-                                   node_grads ? g_xhat.data_ptr() : nullptr, parts.data_ptr(), xl_bwd | XEQ_WQ_PACKED_WEIGHTS, st));
-          if (defer_edge_grad) {
-            part_sets.push_back(parts);
-            if (b == 0) {
-              std::vector<const void*> pp;
-              for (const Tensor& ps : part_sets) pp.push_back(ps.data_ptr());
-              XCALL(xeq_message_wq_edge_grad_sum(vec.data_ptr(), N, E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
-                                                 g.mirror ? (const int32_t*)g.mirror_map.data_ptr() : nullptr, mul, (int)pp.size(), pp.data(),
-                                                 g_vec.data_ptr(), st));
-            }
-          } else {
-            XCALL(xeq_message_wq_edge_grad(vec.data_ptr(), N, E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
-                                           g.mirror ? (const int32_t*)g.mirror_map.data_ptr() : nullptr, mul, parts.data_ptr(),
-                                           g_vec.data_ptr(), st));
-          }
-        } else {
-          g.sorted_view();
-          // the blocks share ONE dL/dvec buffer: the first to run stores, the others add (XEQ_SB_ACCUM_VEC; ops.message_backward does the same)
-          const bool accum = g_vec_total.defined();
-          if (!accum) g_vec_total = g_vec;
-          XCALL(xeq_message_bwd_sb(dt, N, E, (const int32_t*)g.n_rowptr.data_ptr(), (const int32_t*)g.n_perm.data_ptr(),
-                                   (const int64_t*)g.ei.select(0, 0).data_ptr(), g.sb_basis.data_ptr(), g.sb_dbasis.data_ptr(),
-                                   m.h.data_ptr(), m.xhat.data_ptr(), g_s.data_ptr(), g_x.data_ptr(), q[4].data_ptr(), q[5].data_ptr(),
-                                   hy.B, F, mul, g_h.data_ptr(), g_xhat.data_ptr(), g_vec_total.data_ptr(), 1 | (accum ? XEQ_SB_ACCUM_VEC : 0), st));
-        }
-        if (m.impl != 0) {
-          // (summed in the kernel)
-        } else if (defer_edge_grad) {
-          if (b == 0) g_vec_total = g_vec;
-        } else {
-          g_vec_total = g_vec_total.defined() ? g_vec_total + g_vec : g_vec;
-        }
-        if (b == 0) break;   // the first block's node features (embedding, zeros) do not depend on the positions
-        if (nb_ok) {         // the front half of this block is reversed by the node block of update b - 1; g_s, g_x: the residual path
-          pend_gh = g_h;
-          pend_gxhat = g_xhat;
-          continue;
-        }
-        const Tensor g_shat = mlp_bwd(g_h, m.pre, q[0], q[1], q[2], q[3]);
-        Tensor ns, nx;
-        norm_bwd(hy, m.s, m.x, q[6], q[8], m.stats, g_shat, F, g_xhat, g_s, g_x, ns, nx);
-        g_s = ns;
-        g_x = nx;
+      Tensor g_h, g_xhat;
+      message_block_bwd(hy, g, Q(b), wq, b == 0, vec, msv[b], g_s, g_x, g_h, g_xhat, eg);
+      if (b == 0) break;   // the first block's node features (embedding, zeros) do not depend on the positions
+      if (nb_ok) {         // the front half of this block is reversed by the node block of update b - 1; g_s, g_x: the residual path
+        pend_gh = g_h;
+        pend_gxhat = g_xhat;
+      } else {
+        message_front_bwd(hy, Q(b), msv[b], g_h, g_xhat, g_s, g_x);
       }
     }
-    if (!g_vec_total.defined()) g_vec_total = at::zeros_like(vec);
-    g_vec_total = g_vec_total.contiguous();
-    if (compute_forces) {
-      Tensor grad_pos = at::empty({N, 3}, fopt);
-      XCALL(xeq_edge_vectors_bwd(dt, g_vec_total.data_ptr(), N, (const int32_t*)g.c_rowptr.data_ptr(),
-                                 g.c_perm.defined() ? (const int32_t*)g.c_perm.data_ptr() : nullptr,
-                                 (const int32_t*)g.rev_rowptr().data_ptr(), (const int32_t*)g.rev_perm().data_ptr(), grad_pos.data_ptr(), st));
-      forces = neg_seed ? grad_pos : grad_pos.neg();
-    }
-    if (compute_virial) {   // sym(sum_e vec_e (x) dE/dvec_e) per graph, edges walked center-sorted (ops.EdgeVectors.backward)
-      Tensor outer = (vec.unsqueeze(2) * g_vec_total.unsqueeze(1)).reshape({-1, 9});
-      if (g.c_perm.defined()) outer = outer.index_select(0, g.c_perm.to(at::kLong));
-      const Tensor eptr = g.c_rowptr.to(at::kLong).index_select(0, ptr64).contiguous();
-      outer = outer.contiguous();
-      Tensor msum = at::empty({G, 9}, fopt);
-      XCALL(xeq_segment_sum(dt, outer.data_ptr(), (const int64_t*)eptr.data_ptr(), G, 9, msum.data_ptr(), st));
-      msum = msum.view({G, 3, 3});
-      virial = 0.5 * (msum + msum.transpose(1, 2));
-      if (!neg_seed) virial = virial.neg();
-    }
+    edge_vectors_bwd_and_virial(g, vec, eg.total, ptr64, compute_forces, compute_virial, head.fused, forces, virial);
   }
   if (!forces.defined()) forces = at::empty({0, 3}, fopt);
   if (!virial.defined()) virial = at::empty({0, 3, 3}, fopt);

@@ -225,6 +225,26 @@ def bump_pack_epoch() -> None:
     load().xeq_pack_epoch_bump()
 
 
+def pack_key(tensors, extra=()) -> tuple:
+    """THE key of a packed copy: (version counter, address) of every tensor it was made from (None for an absent one), the flags that
+    select its form, the pack epoch.  An in-place update moves the version, a replaced storage the address, a replayed captured
+    optimizer step the epoch."""
+    return (*[None if t is None else (t._version, t.data_ptr()) for t in tensors], *extra, pack_epoch())
+
+
+def cached(owner, slot: str, tensors, build, extra=()):
+    """What ``build()`` (run under no_grad) returned last for ``pack_key(tensors, extra)``, kept on ``owner`` as the attribute
+    ``slot`` = (key, value).  Every packed-weight cache of the Python front is this function."""
+    key = pack_key(tensors, extra)
+    hit = getattr(owner, slot, None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        value = build()
+    setattr(owner, slot, (key, value))
+    return value
+
+
 def launch_count() -> int:
     """Kernel launches libxeq_hip.so has enqueued in this process (include/xeq.h: xeq_launch_count)."""
     return int(load().xeq_launch_count())

@@ -80,25 +80,20 @@ def _mlp_packs(seq: torch.nn.Sequential):
     if not (isinstance(act, torch.nn.SiLU) and w1.dtype == torch.float32 and lin1.bias is not None and lin2.bias is not None
             and lib.load().xeq_mlp2_supported(lib.XEQ_F32, w1.shape[1], w1.shape[0], w2.shape[0])):
         return None
-    key = (w1._version, w1.data_ptr(), lin1.bias._version, lin1.bias.data_ptr(), w2._version, w2.data_ptr(), lin2.bias._version,
-           lin2.bias.data_ptr(), lib.pack_epoch())
-    cache = getattr(seq, "_xeq_mlp_pack", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
 
     def pack(w, bias, n_out, k_in, transposed):
         out = torch.empty(lib.load().xeq_mlp_packed_floats(n_out, k_in), dtype=torch.float32, device=w.device)
         call("xeq_mlp_pack", ptr(w), ptr(bias), n_out, k_in, int(transposed), ptr(out), stream())
         return out
 
-    with torch.no_grad():
+    def build():
         h, k1 = w1.shape
         n2 = w2.shape[0]
         w1c, w2c = w1.detach().contiguous(), w2.detach().contiguous()
-        packs = (pack(w1c, lin1.bias.detach(), h, k1, False), pack(w2c, lin2.bias.detach(), n2, h, False),
-                 pack(w2c, None, h, n2, True), pack(w1c, None, k1, h, True))     # reverse: W2 as [k = n2][n = h], W1 as [k = h][n = k1]
-    seq._xeq_mlp_pack = (key, packs)
-    return packs
+        return (pack(w1c, lin1.bias.detach(), h, k1, False), pack(w2c, lin2.bias.detach(), n2, h, False),
+                pack(w2c, None, h, n2, True), pack(w1c, None, k1, h, True))     # reverse: W2 as [k = n2][n = h], W1 as [k = h][n = k1]
+
+    return lib.cached(seq, "_xeq_mlp_pack", (w1, lin1.bias, w2, lin2.bias), build)
 
 
 def _mlp_fwd(seq, x):
@@ -218,17 +213,14 @@ def _linear_pack(mod_or_key, weight: torch.Tensor, bias, transposed: bool):
     n_out, k_in = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])
     if weight.dtype != torch.float32 or not weight.is_cuda or not lib.load().xeq_linear_supported(lib.XEQ_F32, k_in, n_out):
         return None
-    key = (weight._version, weight.data_ptr(), None if bias is None else (bias._version, bias.data_ptr()), transposed, lib.pack_epoch())
-    name = "_xeq_lin_pack_t" if transposed else "_xeq_lin_pack"
-    cache = getattr(mod_or_key, name, None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    with torch.no_grad():
+
+    def build():
         out = torch.empty(lib.load().xeq_mlp_packed_floats(n_out, k_in), dtype=torch.float32, device=weight.device)
         call("xeq_mlp_pack", ptr(weight.detach().contiguous()), ptr(None if (bias is None or transposed) else bias.detach().contiguous()),
              n_out, k_in, int(transposed), ptr(out), stream())
-    setattr(mod_or_key, name, (key, out))
-    return out
+        return out
+
+    return lib.cached(mod_or_key, "_xeq_lin_pack_t" if transposed else "_xeq_lin_pack", (weight, bias), build, (transposed,))
 
 
 def _linear(x: torch.Tensor, pack: torch.Tensor, k_in: int, n_out: int, has_bias: bool, act: int = 0, row_index=None, want_pre: bool = False):
@@ -441,17 +433,15 @@ def first_block_front(module, z: torch.Tensor, rows: torch.Tensor, n: int, highe
     if rows.dtype != torch.float32 or mul[0] != F or isinstance(module.norm, torch.nn.Identity) or z.dtype not in (torch.int32, torch.int64):
         return None
     mlp = module.scalar_mlp
-    key = (rows.data_ptr(), rows._version, module.norm.weight._version, module.norm.bias._version, module.o3norm.affine_weight._version,
-           module.o3norm.affine_bias._version, mlp[0].weight._version, mlp[0].bias._version, mlp[2].weight._version, mlp[2].bias._version,
-           lib.pack_epoch())
-    cache = getattr(module, "_element_front", None)
-    if cache is None or cache[0] != key:
-        with torch.no_grad():
-            zt = rows.shape[0]
-            shat, xhat_t, _, _ = _norm_fwd(rows, torch.zeros((zt, D), dtype=rows.dtype, device=rows.device), module.norm, module.o3norm, F, mul)
-            _, h_t = _mlp_fwd(mlp, shat)
-            cache = module._element_front = (key, h_t.contiguous(), xhat_t[: zt * F].view(zt, F).contiguous())
-    _, h_t, xhat0_t = cache
+
+    def build():
+        zt = rows.shape[0]
+        shat, xhat_t, _, _ = _norm_fwd(rows, torch.zeros((zt, D), dtype=rows.dtype, device=rows.device), module.norm, module.o3norm, F, mul)
+        _, h_t = _mlp_fwd(mlp, shat)
+        return h_t.contiguous(), xhat_t[: zt * F].view(zt, F).contiguous()
+
+    h_t, xhat0_t = lib.cached(module, "_element_front", (rows, module.norm.weight, module.norm.bias, module.o3norm.affine_weight,
+                                                         module.o3norm.affine_bias, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias), build)
     H = h_t.shape[1]
     z = z.contiguous()
     s = torch.empty((n, F), dtype=rows.dtype, device=rows.device)
@@ -522,48 +512,46 @@ class MessageBlock(Function):
 
 def _packed_uv(module) -> Tuple[list, torch.Tensor]:
     """[W_U | W_V] / sqrt(mul) per l ([mul, 2 mul]) and the 0e bias pair, cached on the module."""
-    wu, wv = module.update_U.weight, module.update_V.weight
-    key = (wu._version, wv._version, wu.data_ptr(), wv.data_ptr(), module.update_U.bias._version, module.update_V.bias._version, wu.dtype,
-           lib.pack_epoch())
-    cache = getattr(module, "_uv_pack", None)
-    if cache is not None and cache[0] == key:
-        return cache[1], cache[2]
-    with torch.no_grad():
+    U, V = module.update_U, module.update_V
+    wu, wv = U.weight, V.weight
+
+    def build():
         packs, off = [], 0
         for mul, l, _, _ in module.node_irreps.blocks():
             Wu = wu[off : off + mul * mul].view(mul, mul)
             Wv = wv[off : off + mul * mul].view(mul, mul)
             packs.append((torch.cat([Wu, Wv], dim=1) / math.sqrt(mul)).contiguous())
             off += mul * mul
-        bias = torch.cat([module.update_U.bias, module.update_V.bias]) if module.update_U.bias.numel() else None
-    module._uv_pack = (key, packs, bias)
-    return packs, bias
+        return packs, (torch.cat([U.bias, V.bias]) if U.bias.numel() else None)
+
+    return lib.cached(module, "_uv_pack", (wu, wv, U.bias, V.bias), build, (wu.dtype,))
 
 
 def _packed_uv_frag(module):
     """The [W_U | W_V] / sqrt(mul) blocks in matrix-core fragment order for ``xeq_update_uv_fwd`` (one per l, None for an
-    absent block; the l = 0 pack carries the bias pair), or None when the kernel does not take the layout."""
+    absent block; the l = 0 pack carries the bias pair), or None when the kernel does not take the layout.
+    -> (forward packs, whether they carry a bias, reverse packs)."""
     mul = module.node_irreps.mul3()
-    wu = module.update_U.weight
-    if wu.dtype != torch.float32 or not lib.load().xeq_update_uv_supported(lib.XEQ_F32, module.node_dim, mul3(mul)):
+    U, V = module.update_U, module.update_V
+    if U.weight.dtype != torch.float32 or not lib.load().xeq_update_uv_supported(lib.XEQ_F32, module.node_dim, mul3(mul)):
         return None
-    packs, bias = _packed_uv(module)                     # refreshed there when a weight changes
-    cache = getattr(module, "_uv_frag", None)
-    if cache is not None and cache[0] is packs:
-        return cache[1], cache[2], cache[3]
-    frag, frag_t, it = [None, None, None], [None, None, None], iter(packs)
-    for l, m in enumerate(mul):
-        if m == 0:
-            continue
-        W = next(it)                                     # [mul, 2 mul] = [k_in][n_out]
-        out = torch.empty(lib.load().xeq_mlp_packed_floats(2 * m, m), dtype=torch.float32, device=W.device)
-        call("xeq_mlp_pack", ptr(W), ptr(bias if l == 0 else None), 2 * m, m, 1, ptr(out), stream())
-        frag[l] = out
-        out_t = torch.empty(lib.load().xeq_mlp_packed_floats(m, 2 * m), dtype=torch.float32, device=W.device)
-        call("xeq_mlp_pack", ptr(W), None, m, 2 * m, 0, ptr(out_t), stream())   # reverse: the same rows as [n_out = mul][k_in = 2 mul]
-        frag_t[l] = out_t
-    module._uv_frag = (packs, frag, bias is not None, frag_t)
-    return frag, bias is not None, frag_t
+
+    def build():
+        packs, bias = _packed_uv(module)
+        frag, frag_t, it = [None, None, None], [None, None, None], iter(packs)
+        for l, m in enumerate(mul):
+            if m == 0:
+                continue
+            W = next(it)                                     # [mul, 2 mul] = [k_in][n_out]
+            out = torch.empty(lib.load().xeq_mlp_packed_floats(2 * m, m), dtype=torch.float32, device=W.device)
+            call("xeq_mlp_pack", ptr(W), ptr(bias if l == 0 else None), 2 * m, m, 1, ptr(out), stream())
+            frag[l] = out
+            out_t = torch.empty(lib.load().xeq_mlp_packed_floats(m, 2 * m), dtype=torch.float32, device=W.device)
+            call("xeq_mlp_pack", ptr(W), None, m, 2 * m, 0, ptr(out_t), stream())   # reverse: the same rows as [n_out = mul][k_in = 2 mul]
+            frag_t[l] = out_t
+        return frag, bias is not None, frag_t
+
+    return lib.cached(module, "_uv_frag", (U.weight, V.weight, U.bias, V.bias), build)
 
 
 class NodeBlock(Function):
@@ -613,7 +601,7 @@ class NodeBlock(Function):
 # it to xeq_norm_bwd (50 KB: three per CU; 92 against 99 us at 18 k nodes).  The two forms reduce a row in different orders, so a
 # switch by node count made a node's bits depend on its batch (6e-7 in the forces between a 9 k-node batch and its 2 k-node
 # chunks, found once the last library GEMM was gone): since round 3 the split form runs at every size (0 = never fuse).
-# The C++ operator (csrc/xeq_torch.cpp) applies the same rule.
+# csrc/xeq_torch.cpp holds the same constant for the native operator and refers here for the reason.
 UV_BWD_FUSE_NORM_MAX_NODES = 0
 
 

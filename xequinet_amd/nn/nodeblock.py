@@ -15,13 +15,10 @@ from .. import lib
 from ..lib import call, mul3, ptr, stream
 
 TILE_BYTES = 3072
-pack_epoch = lib.pack_epoch   # every pack cache keys on it next to the tensors' version counters (include/xeq.h)
 
 
 def supported(update, message=None) -> bool:
     """Whether the fused node-block kernels take this update block (and, if given, the next message block's front half)."""
-    from .fused import _packed_uv
-
     if not isinstance(update.update_mlp[1], torch.nn.SiLU) or isinstance(update.norm, torch.nn.Identity):
         return False
     w = update.update_mlp[0].weight
@@ -39,47 +36,44 @@ def supported(update, message=None) -> bool:
     return True
 
 
-def _versions(*tensors):
-    return tuple((t._version, t.data_ptr()) for t in tensors if t is not None)
-
-
-def packed_fwd(update, message=None) -> torch.Tensor:
-    """The forward weight program of (update block, next message block or None), cached on the update module."""
+def _packed(update, message, with_gx: Optional[bool]) -> torch.Tensor:
+    """The weight program of (update block, next message block or None), cached on the update module.  ``with_gx`` None: the forward
+    program; else the reverse one, with or without the terms of dL/dx_out."""
     from .fused import _packed_uv
 
     m = update.update_mlp
-    ws = [m[0].weight, update.update_U.weight, update.update_V.weight, update.dot_lin.weight, m[2].weight]
-    if message is not None:
-        ws += [message.scalar_mlp[0].weight, message.scalar_mlp[2].weight]
-    key = (_versions(*ws), pack_epoch(), id(message))
-    cache = getattr(update, "_xeq_nb_fwd", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    with torch.no_grad():
+    reverse = with_gx is not None
+    w1n, w2n = (message.scalar_mlp[0].weight, message.scalar_mlp[2].weight) if message is not None else (None, None)
+
+    def build():
         uv, _ = _packed_uv(update)        # [W_U | W_V] / sqrt(mul) per l, [mul, 2 mul]
-        tiles = int(lib.load().xeq_node_block_fwd_tiles(int(message is not None)))
+        L = lib.load()
+        tiles = int(L.xeq_node_block_bwd_tiles(int(message is not None), int(with_gx)) if reverse
+                    else L.xeq_node_block_fwd_tiles(int(message is not None)))
         out = torch.empty(tiles * TILE_BYTES, dtype=torch.uint8, device=m[0].weight.device)
-        w1n = message.scalar_mlp[0].weight.detach().contiguous() if message is not None else None
-        w2n = message.scalar_mlp[2].weight.detach().contiguous() if message is not None else None
-        keep = [m[0].weight.detach().contiguous(), update.dot_lin.weight.detach().contiguous(), m[2].weight.detach().contiguous()]
-        call("xeq_node_block_pack_fwd", ptr(keep[0]), ptr(uv[0]), ptr(uv[1]), ptr(uv[2]), ptr(keep[1]), ptr(keep[2]), ptr(w1n), ptr(w2n),
-             ptr(out), stream())
-    update._xeq_nb_fwd = (key, out)
-    return out
+        keep = [None if w is None else w.detach().contiguous() for w in (m[0].weight, update.dot_lin.weight, m[2].weight, w1n, w2n)]
+        call("xeq_node_block_pack_bwd" if reverse else "xeq_node_block_pack_fwd", ptr(keep[0]), ptr(uv[0]), ptr(uv[1]), ptr(uv[2]),
+             ptr(keep[1]), ptr(keep[2]), ptr(keep[3]), ptr(keep[4]), *((int(with_gx),) if reverse else ()), ptr(out), stream())
+        return out
+
+    slot = "_xeq_nb_fwd" if not reverse else ("_xeq_nb_bwd_gx" if with_gx else "_xeq_nb_bwd")
+    return lib.cached(update, slot, (m[0].weight, update.update_U.weight, update.update_V.weight, update.dot_lin.weight, m[2].weight, w1n, w2n),
+                      build, (id(message), with_gx))
+
+
+def packed_fwd(update, message=None) -> torch.Tensor:
+    return _packed(update, message, None)
+
+
+def packed_bwd(update, message=None, with_gx: bool = True) -> torch.Tensor:
+    return _packed(update, message, bool(with_gx or message is not None))
 
 
 def _uv_bias(update) -> Optional[torch.Tensor]:
     bu, bv = update.update_U.bias, update.update_V.bias
     if bu is None or bu.numel() == 0:
         return None
-    key = (_versions(bu, bv), pack_epoch())
-    cache = getattr(update, "_xeq_nb_buv", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    with torch.no_grad():
-        b = torch.cat([bu.detach(), bv.detach()]).contiguous()
-    update._xeq_nb_buv = (key, b)
-    return b
+    return lib.cached(update, "_xeq_nb_buv", (bu, bv), lambda: torch.cat([bu.detach(), bv.detach()]).contiguous())
 
 
 def node_block_fwd(s: torch.Tensor, x: torch.Tensor, update, message=None, want_x: bool = True) -> dict:
@@ -114,35 +108,6 @@ def node_block_fwd(s: torch.Tensor, x: torch.Tensor, update, message=None, want_
          ptr(nm.scalar_mlp[2].bias if tail else None), ptr(o.get("stats2")), ptr(o.get("xhat2")), ptr(o.get("pre2")), ptr(o.get("h2")),
          stream())
     return o
-
-
-def packed_bwd(update, message=None, with_gx: bool = True) -> torch.Tensor:
-    """The reverse weight program of (update block, next message block or None), cached on the update module."""
-    from .fused import _packed_uv
-
-    m = update.update_mlp
-    ws = [m[0].weight, update.update_U.weight, update.update_V.weight, update.dot_lin.weight, m[2].weight]
-    if message is not None:
-        ws += [message.scalar_mlp[0].weight, message.scalar_mlp[2].weight]
-    with_gx = bool(with_gx or message is not None)
-    key = (_versions(*ws), pack_epoch(), id(message), with_gx)
-    cache = getattr(update, "_xeq_nb_bwd", None)
-    if cache is None:
-        cache = update._xeq_nb_bwd = {}
-    hit = cache.get(with_gx)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    with torch.no_grad():
-        uv, _ = _packed_uv(update)
-        tiles = int(lib.load().xeq_node_block_bwd_tiles(int(message is not None), int(with_gx)))
-        out = torch.empty(tiles * TILE_BYTES, dtype=torch.uint8, device=m[0].weight.device)
-        w1n = message.scalar_mlp[0].weight.detach().contiguous() if message is not None else None
-        w2n = message.scalar_mlp[2].weight.detach().contiguous() if message is not None else None
-        keep = [m[0].weight.detach().contiguous(), update.dot_lin.weight.detach().contiguous(), m[2].weight.detach().contiguous()]
-        call("xeq_node_block_pack_bwd", ptr(keep[0]), ptr(uv[0]), ptr(uv[1]), ptr(uv[2]), ptr(keep[1]), ptr(keep[2]), ptr(w1n), ptr(w2n),
-             int(with_gx), ptr(out), stream())
-    cache[with_gx] = (key, out)
-    return out
 
 
 def node_block_bwd(saved: dict, s: torch.Tensor, x: torch.Tensor, update, message, g_s_in: torch.Tensor, g_x_in: Optional[torch.Tensor],

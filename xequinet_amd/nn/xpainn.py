@@ -99,18 +99,12 @@ class XEmbedding(nn.Module):
         table, lin = self.embedding[0].embed_ten, self.embedding[1]
         if table.dtype != torch.float32 or table.stride(0) % 4 != 0:
             return None
-        key = (lin.weight._version, None if lin.bias is None else lin.bias._version, table._version, table.data_ptr(), lin.weight.data_ptr(),
-               ops.lib.pack_epoch())
-        cache = getattr(self, "_rows_cache", None)
-        if cache is not None and cache[0] == key:
-            return cache[1]
-        pack = _linear_pack(lin, lin.weight, lin.bias, False)
-        if pack is None:
-            return None
-        with torch.no_grad():
-            rows = _linear(table, pack, lin.weight.shape[1], lin.weight.shape[0], lin.bias is not None)[0]
-        self._rows_cache = (key, rows)
-        return rows
+
+        def build():   # (None where the kernel does not take the layer: a property of the weight, cached like the rows)
+            pack = _linear_pack(lin, lin.weight, lin.bias, False)
+            return None if pack is None else _linear(table, pack, lin.weight.shape[1], lin.weight.shape[0], lin.bias is not None)[0]
+
+        return ops.lib.cached(self, "_rows_cache", (lin.weight, lin.bias, table), build)
 
     def forward(self, data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         if training.active(self, data):   # parameter gradients / double backward: the differentiable form

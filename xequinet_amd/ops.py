@@ -844,8 +844,7 @@ def wq_packed_weights(w_rbf: torch.Tensor, b_rbf: torch.Tensor, num_basis: int, 
     The kernels' own staging reads W with one row per lane -- 64 cache lines per wave instruction -- between every two workgroups of
     a CU slot; from this copy it is a coalesced 16-byte copy (~11 us per launch).  The cache holds the weight tensors themselves, so an
     entry's address cannot be reused by another tensor while the entry lives (at most 32 entries)."""
-    key = (w_rbf.data_ptr(), w_rbf._version, b_rbf.data_ptr(), b_rbf._version, int(num_basis), int(node_dim), tuple(int(m) for m in mul),
-           lib.pack_epoch())
+    key = lib.pack_key((w_rbf, b_rbf), (int(num_basis), int(node_dim), tuple(int(m) for m in mul)))
     hit = _WQ_WEIGHT_PACKS.get(key)
     if hit is not None:
         return hit[0]
