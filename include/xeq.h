@@ -810,6 +810,49 @@ int xeq_node_block_bwd(int64_t n, const float* g_h, const float* g_xhat_next, co
  * accumulation, form 1: one output tile at a time; packed_scratch: 8 n_ot * 3072 bytes */
 int xeq_node_block_linear_test(const float* x, int64_t n, const float* w, int n_ot, int form, void* packed_scratch, float* y, void* stream);
 
+/* ---- PaiNN (nn/painn.py of the reference; csrc/xeq_painn.hip) -----------------------------------------------------------------------
+ * f32; node_dim F a multiple of 32 up to 256, num_basis <= 31.  Node scalars s [n, F], node vectors x [n, 3, F] Cartesian (x, y, z).
+ * Every product is the exact-f32 matrix instruction: a row's bits do not depend on the batch around it.
+ * xeq_painn_supported -> 1 / 0.  xeq_painn_few_rows_limit: node count up to which the update products launch one wave per workgroup
+ * (one workgroup per 16 nodes x 16 output columns; same bits as the four-wave form). */
+int xeq_painn_supported(int dtype, int node_dim, int num_basis);
+int64_t xeq_painn_few_rows_limit(void);
+/* packed copies (caller-owned): the filter rbf_lin (weight [3 F, B], bias [3 F]) as [32, 3 F] with the bias in row B; update_U / update_V
+ * (weights [F, F], no bias) as four matrices in operand order (forward pair, reverse pair). */
+int64_t xeq_painn_filter_packed_floats(int node_dim);
+int64_t xeq_painn_uv_packed_floats(int node_dim);
+int xeq_painn_pack_filter(const float* w, const float* b, int node_dim, int num_basis, float* out, void* stream);
+int xeq_painn_pack_uv(const float* wu, const float* wv, int node_dim, float* out, void* stream);
+/* Message block, nn/painn.py:100-117 (h [n, 3 F] = scalar_mlp(s) of :99 comes from xeq_mlp2_fwd): one wave per center walks
+ * rowptr / perm (center-sorted CSR of edge_index [2, E], perm NULL: already sorted) in chunks of 16 edges; radial basis (p0, p1 as
+ * xeq_message_fwd), envelope and unit vectors are formed per chunk on chip from vec [E, 3]; s_out = s + sum m_s,
+ * x_out[c] = x[c] + sum (x[nbr, c] gate_state + u_c gate_edge): one store per node, no atomics. */
+int xeq_painn_message_fwd(int64_t n_nodes, int64_t n_edges, const int32_t* rowptr, const int32_t* perm, const int64_t* edge_index, const float* vec,
+                          const float* h, const float* s, const float* x, const float* w_packed, const float* p0, const float* p1, int rbf_kind,
+                          int cutoff_kind, int num_basis, double cutoff, int node_dim, float* s_out, float* x_out, void* stream);
+/* Reverse of nn/painn.py:100-117: one wave per NEIGHBOUR walks n_rowptr / n_perm (the reverse-edge map of a symmetric list, or the
+ * neighbour-sorted view).  g_s [n, F], g_x [n, 3, F] or NULL (zero) are dL/ds_out, dL/dx_out.  Outputs: g_h [n, 3 F]; g_x_in [n, 3, F]
+ * (residual included) or NULL (not wanted); g_vec [E, 3] = dL/dvec through basis, envelope and u = r / d (zero subgradient at r = 0),
+ * written (accumulate_vec = 0) or added to (1: the blocks of one evaluation share the buffer that feeds xeq_edge_vectors_bwd).
+ * dL/ds is g_s + the reverse of the scalar MLP on g_h (xeq_mlp2_bwd, xeq_painn_add). */
+int xeq_painn_message_bwd(int64_t n_nodes, int64_t n_edges, const int32_t* n_rowptr, const int32_t* n_perm, const int64_t* edge_index, const float* vec,
+                          const float* h, const float* x, const float* w_packed, const float* p0, const float* p1, int rbf_kind, int cutoff_kind,
+                          int num_basis, double cutoff, int node_dim, const float* g_s, const float* g_x, float* g_h, float* g_x_in, float* g_vec,
+                          int accumulate_vec, void* stream);
+/* Update block, nn/painn.py:146-164.  uv_fwd (:149-153): U, V [n, 3, F] = x W^T, ip [n, F] = <U, V>, cat [n, 2 F] = [s | |V|] (plain
+ * Euclidean norm), the input of update_mlp (xeq_mlp2_fwd -> a [n, 3 F] = a_ss | a_vv | a_sv).  out_fwd (:156-164): s_out = s + a_sv ip
+ * + a_ss, x_out = x + a_vv U (x_out NULL: not formed).  out_bwd: g_a [n, 3 F] from g_s, g_x (NULL: zero).  uv_bwd: g_cat [n, 2 F] is
+ * xeq_mlp2_bwd of g_a; g_s_in = g_s + g_cat[:, :F]; g_x_in = g_x + dL/dU W_U + dL/dV W_V, the norm's gradient exactly 0 where |V| = 0. */
+int xeq_painn_update_uv_fwd(int64_t n, int node_dim, const float* s, const float* x, const float* uv_packed, float* U, float* V, float* ip, float* cat,
+                            void* stream);
+int xeq_painn_update_out_fwd(int64_t n, int node_dim, const float* s, const float* x, const float* a, const float* U, const float* ip, float* s_out,
+                             float* x_out, void* stream);
+int xeq_painn_update_out_bwd(int64_t n, int node_dim, const float* g_s, const float* g_x, const float* U, const float* ip, float* g_a, void* stream);
+int xeq_painn_update_uv_bwd(int64_t n, int node_dim, const float* g_s, const float* g_x, const float* a, const float* U, const float* V, const float* cat,
+                            const float* g_cat, const float* uv_packed, float* g_s_in, float* g_x_in, void* stream);
+/* out = a + b (n floats): the two paths of dL/ds behind a message block */
+int xeq_painn_add(const float* a, const float* b, int64_t n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
 from .ase_calculator import XequiCalculator
-from .md_model import XPaiNNGMX, XPaiNNLMP, resolve_jit_model
+from .md_model import PaiNNGMX, PaiNNLMP, XPaiNNGMX, XPaiNNLMP, resolve_jit_model
 
-__all__ = ["XPaiNNLMP", "XPaiNNGMX", "resolve_jit_model", "XequiCalculator"]
+__all__ = ["XPaiNNLMP", "XPaiNNGMX", "PaiNNLMP", "PaiNNGMX", "resolve_jit_model", "XequiCalculator"]

@@ -19,7 +19,7 @@ import torch
 from .. import keys, ops
 from ..data.radius_graph import single_radius_graph
 from ..nn.basic import compute_edge_data, compute_properties
-from ..nn.model import BaseModel, XPaiNN
+from ..nn.model import BaseModel, PaiNN, XPaiNN
 from ..utils import get_default_units, unit_conversion
 
 
@@ -41,6 +41,9 @@ class XPaiNNLMP(XPaiNN):
         (``xeq::xpainn_eval``, every kernel enqueued from C++: the numbers of the Python modules at a third of their host
         time; fp32, a copy of the parameters is taken at first use) -- what ``interface.scripted.XPaiNNLMPScript`` runs."""
         super().__init__(**kwargs)
+        self._init_front(unit_style, net_charge, replay, tune_gemms, native)
+
+    def _init_front(self, unit_style: str, net_charge: Optional[int], replay: bool, tune_gemms: bool, native: bool) -> None:
         lammps_units = keys.LAMMPS_UNIT_STYLE[unit_style]
         self.pos_unit_factor = unit_conversion(lammps_units[keys.POSITIONS], _default_unit(keys.POSITIONS))        # LAMMPS -> model
         self.energy_unit_factor = unit_conversion(_default_unit(keys.TOTAL_ENERGY), lammps_units[keys.TOTAL_ENERGY])  # model -> LAMMPS
@@ -51,6 +54,9 @@ class XPaiNNLMP(XPaiNN):
         self._use_replay = replay
         self._tune_gemms = tune_gemms
         self._use_native, self._native = native, None
+
+    def _core(self):
+        return _Core(self)
 
     def _evaluate(self, data, compute_forces: bool, compute_virial: bool) -> Dict[str, torch.Tensor]:
         if self._use_native and not self._use_replay and data[keys.POSITIONS].dtype == torch.float32:
@@ -77,7 +83,7 @@ class XPaiNNLMP(XPaiNN):
             from ..runtime import GraphedModel
             if (self._replay is None or self._replay.compute_forces != compute_forces
                     or self._replay.compute_virial != compute_virial):
-                self._replay = GraphedModel(_Core(self), compute_forces=compute_forces, compute_virial=compute_virial,
+                self._replay = GraphedModel(self._core(), compute_forces=compute_forces, compute_virial=compute_virial,
                                             tune_gemms=self._tune_gemms, reuse_unchanged_topology=True)
             if keys.BATCH_PTR not in data:   # one graph: [0, n], kept per (n, device) -- no host-to-device copy per step
                 n, dev = data[keys.POSITIONS].shape[0], data[keys.POSITIONS].device
@@ -90,7 +96,7 @@ class XPaiNNLMP(XPaiNN):
             fresh = {k: torch.empty_like(v) for k, v in out.items() if k not in rescaled}
             ops.copy_many([(fresh[k], out[k]) for k in fresh])      # one launch for all of them
             return {k: fresh.get(k, v) for k, v in out.items()}
-        return _Core(self)(data, compute_forces, compute_virial)
+        return self._core()(data, compute_forces, compute_virial)
 
     def _rescaled_keys(self, compute_forces: bool, compute_virial: bool) -> set:
         """Results that forward() multiplies by a unit factor other than 1 (the product is a new tensor)."""
@@ -177,6 +183,16 @@ class XPaiNNGMX(XPaiNN):
         self.net_charge = net_charge
         self._use_replay, self._tune_gemms, self._replay = replay, tune_gemms, None
 
+    def _core(self):
+        return _Core(self)
+
+    def _energy(self, data: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """The energy with its autograd graph back to ``data['pos']`` (the caller differentiates it)."""
+        data = compute_edge_data(data=data, compute_forces=True, compute_virial=False)
+        for mod in self.mods.values():
+            data = mod(data)
+        return data[keys.TOTAL_ENERGY]
+
     def forward(self, positions: torch.Tensor, atomic_numbers: torch.Tensor, box: Optional[torch.Tensor] = None,
                 pbc: Optional[torch.Tensor] = None) -> torch.Tensor:
         positions = positions * self.pos_unit_factor
@@ -193,7 +209,7 @@ class XPaiNNGMX(XPaiNN):
             if self._step_graph is None or self._step_graph.n_atoms != positions.shape[0]:
                 with torch.no_grad():     # one sized search for the capacity: a quarter more room than the first list needs
                     ei0, _ = single_radius_graph(pos=positions, cell=cell, pbc=pbc, cutoff=self.cutoff_radius)
-                self._step_graph = GraphedStepPBC(_Core(self), positions.shape[0], int(1.25 * ei0.shape[1]) + 1024,
+                self._step_graph = GraphedStepPBC(self._core(), positions.shape[0], int(1.25 * ei0.shape[1]) + 1024,
                                                   cutoff=self.cutoff_radius, compute_forces=True)
             # the capacity check reads the edge count on the host (a synchronisation): everything that follows the replay is enqueued
             # FIRST, so that the wait covers it instead of standing in front of it; a list that outgrew the capacity (rare: the step
@@ -227,21 +243,85 @@ class XPaiNNGMX(XPaiNN):
         if self._use_replay:
             from ..runtime import GraphedModel
             if self._replay is None:
-                self._replay = GraphedModel(_Core(self), compute_forces=True, compute_virial=False, tune_gemms=self._tune_gemms)
+                self._replay = GraphedModel(self._core(), compute_forces=True, compute_virial=False, tune_gemms=self._tune_gemms)
             data[keys.POSITIONS] = positions.detach()
             data[keys.BATCH_PTR] = torch.tensor([0, positions.shape[0]], dtype=torch.long, device=positions.device)
             out = self._replay(data)
             energy = _EnergyOfPositions.apply(positions, out[keys.TOTAL_ENERGY], out[keys.FORCES].clone())
             return energy * self.energy_unit_factor
-        data = compute_edge_data(data=data, compute_forces=True, compute_virial=False)
-        for mod in self.mods.values():
-            data = mod(data)
-        return data[keys.TOTAL_ENERGY] * self.energy_unit_factor
+        return self._energy(data) * self.energy_unit_factor
 
 
-def resolve_jit_model(mode: str = "lmp", unit_style: str = "metal", net_charge: Optional[int] = None, **kwargs) -> BaseModel:
-    """jit_model.py:219-236; the dipole head is outside the energy+force path."""
-    factory = {"lmp": XPaiNNLMP, "gmx": XPaiNNGMX}
+class _PaiNNCore:
+    """``PaiNN.forward`` under an MD front's own ``forward`` (the callable GraphedModel captures)."""
+
+    def __init__(self, model: PaiNN) -> None:
+        self.model = model
+
+    def __call__(self, data, compute_forces: bool = True, compute_virial: bool = False):
+        return PaiNN.forward(self.model, data, compute_forces, compute_virial)
+
+
+class PaiNNLMP(PaiNN):
+    """PaiNN behind the LAMMPS front: the data layout, unit handling and ``replay`` option of ``XPaiNNLMP`` (the reference has no
+    such class; its jit_model.py knows XPaiNN only).  An evaluation runs through the Python modules (nn/painn.py): the operator
+    ``xeq::xpainn_eval`` evaluates XPaiNN only, so ``native=True`` is refused, and PaiNN has no charge embedding to hand a
+    ``net_charge`` to."""
+
+    def __init__(self, unit_style: str = "metal", net_charge: Optional[int] = None, replay: bool = False,
+                 tune_gemms: bool = True, native: bool = False, **kwargs) -> None:
+        if native:
+            raise NotImplementedError("PaiNNLMP(native=True): xeq::xpainn_eval evaluates XPaiNN only, a PaiNN model runs through the Python modules")
+        if net_charge is not None:
+            raise ValueError("PaiNNLMP: PaiNN has no charge embedding, net_charge must be None")
+        super().__init__(**kwargs)
+        self._init_front(unit_style, None, replay, tune_gemms, False)
+
+    def _core(self):
+        return _PaiNNCore(self)
+
+    _init_front = XPaiNNLMP._init_front
+    _evaluate = XPaiNNLMP._evaluate
+    _rescaled_keys = XPaiNNLMP._rescaled_keys
+    forward = XPaiNNLMP.forward
+
+
+class PaiNNGMX(PaiNN):
+    """PaiNN behind the GROMACS NNPot front: ``forward(positions, atomic_numbers, box, pbc) -> energy`` with the units, neighbour
+    search and ``replay`` option of ``XPaiNNGMX``.  ``whole_step`` is refused (runtime.GraphedStepPBC does not take a PaiNN model)."""
+
+    def __init__(self, net_charge: Optional[int] = None, replay: bool = False, tune_gemms: bool = True, whole_step: bool = False,
+                 **kwargs) -> None:
+        if whole_step:
+            raise NotImplementedError("PaiNNGMX(whole_step=True): the whole-step capture does not take a PaiNN model, use replay=True alone")
+        if net_charge is not None:
+            raise ValueError("PaiNNGMX: PaiNN has no charge embedding, net_charge must be None")
+        kwargs.pop("unit_style", None)
+        super().__init__(**kwargs)
+        self._whole_step, self._step_graph = False, None
+        self.pos_unit_factor = unit_conversion("nm", _default_unit(keys.POSITIONS))
+        self.energy_unit_factor = unit_conversion(_default_unit(keys.TOTAL_ENERGY), "kJ/mol")
+        self.forces_unit_factor = unit_conversion(_default_unit(keys.FORCES), "kJ/(mol*nm)")
+        self.net_charge = None
+        self._use_replay, self._tune_gemms, self._replay = replay, tune_gemms, None
+
+    def _core(self):
+        return _PaiNNCore(self)
+
+    def _energy(self, data: Dict[str, torch.Tensor]) -> torch.Tensor:
+        return self.run_blocks(data, True, False)[0][keys.TOTAL_ENERGY]
+
+    forward = XPaiNNGMX.forward
+
+
+def resolve_jit_model(mode: str = "lmp", unit_style: str = "metal", net_charge: Optional[int] = None, model_name: str = "xpainn",
+                      **kwargs) -> BaseModel:
+    """jit_model.py:219-236; the dipole head is outside the energy+force path.  ``model_name`` ("xpainn" or "painn", what a
+    checkpoint's config carries) picks the model class behind the front."""
+    fronts = {"xpainn": {"lmp": XPaiNNLMP, "gmx": XPaiNNGMX}, "painn": {"lmp": PaiNNLMP, "gmx": PaiNNGMX}}
+    if model_name.lower() not in fronts:
+        raise NotImplementedError(f"Unsupported model {model_name}")
+    factory = fronts[model_name.lower()]
     if mode not in factory:
         raise NotImplementedError(f"Unsupported mode {mode}")
     return factory[mode](unit_style=unit_style, net_charge=net_charge, **kwargs)

@@ -90,8 +90,10 @@ class XPaiNNNative(nn.Module):
     def __init__(self, model) -> None:
         super().__init__()
         load_torch_library()
-        from ..nn.model import XPaiNN
+        from ..nn.model import PaiNN, XPaiNN
 
+        if isinstance(model, PaiNN):
+            raise NotImplementedError("xeq::xpainn_eval evaluates XPaiNN only: a PaiNN model runs through the Python modules (nn/painn.py)")
         if not isinstance(model, XPaiNN):
             raise TypeError("XPaiNNNative wraps an nn.XPaiNN")
         electronic = [model.mods[k] for k in ("charge_embedding", "spin_embedding") if k in model.mods]
@@ -237,6 +239,10 @@ def compile_model(model, mode: str = "lmp", unit_style: str = "metal", output_fi
     """run/jit_script.py:28-86 for a built model: script the MD front end and (with ``output_file``) save it with the
     reference's ``_extra_files`` (cutoff radius in engine units, fusion strategy, number of species, periodic table).  ``net_charge``:
     the fixed total charge the front hands to a model with a charge embedding (run/jit_script.py passes it to the fronts)."""
+    from ..nn.model import PaiNN
+
+    if isinstance(model, PaiNN):
+        raise NotImplementedError("compile_model scripts the xeq::xpainn_eval operator, which evaluates XPaiNN only: a PaiNN model is not scriptable")
     if mode == "lmp":
         front = XPaiNNLMPScript(model, unit_style=unit_style, net_charge=net_charge)
     elif mode == "gmx":

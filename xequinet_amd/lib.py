@@ -185,10 +185,25 @@ _PROTOS = {
     "xeq_node_block_pack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P],
     "xeq_node_block_bwd": [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, _P,
                            _P, _P, _P],
+    "xeq_painn_supported": [c_int, c_int, c_int],
+    "xeq_painn_few_rows_limit": [],
+    "xeq_painn_filter_packed_floats": [c_int],
+    "xeq_painn_uv_packed_floats": [c_int],
+    "xeq_painn_pack_filter": [_P, _P, c_int, c_int, _P, _P],
+    "xeq_painn_pack_uv": [_P, _P, c_int, _P, _P],
+    "xeq_painn_message_fwd": [c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, c_int, _P, _P, _P],
+    "xeq_painn_message_bwd": [c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, c_int, _P, _P, _P, _P, _P,
+                              c_int, _P],
+    "xeq_painn_update_uv_fwd": [c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+    "xeq_painn_update_out_fwd": [c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+    "xeq_painn_update_out_bwd": [c_int64, c_int, _P, _P, _P, _P, _P, _P],
+    "xeq_painn_update_uv_bwd": [c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "xeq_painn_add": [_P, _P, c_int64, _P, _P],
 }
 # entry points that return a size, not a status
 _RET_I64 = {"xeq_launch_count", "xeq_launch_names", "xeq_message_wq_packed_weight_floats", "xeq_rowptr_from_degrees_max", "xeq_csr_by_key_workspace", "xeq_message_wq_pcap", "xeq_message_wq_plan_workspace", "xeq_message_wq_win_ints",
-            "xeq_message_wq_parts_floats", "xeq_mlp_packed_floats", "xeq_exclusive_scan_i32_workspace", "xeq_node_block_fwd_tiles", "xeq_node_block_bwd_tiles", "xeq_node_block_rows", "xeq_pack_epoch", "xeq_tensor_product_wgrad_chunks", "xeq_small_rows_limit"}
+            "xeq_message_wq_parts_floats", "xeq_mlp_packed_floats", "xeq_exclusive_scan_i32_workspace", "xeq_node_block_fwd_tiles", "xeq_node_block_bwd_tiles", "xeq_node_block_rows", "xeq_pack_epoch", "xeq_tensor_product_wgrad_chunks", "xeq_small_rows_limit", "xeq_painn_few_rows_limit",
+            "xeq_painn_filter_packed_floats", "xeq_painn_uv_packed_floats"}
 EXPORTS = ["xeq_version", "xeq_last_error", *_PROTOS]
 
 _lib: Optional[ctypes.CDLL] = None

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import training
+from .. import keys as keys_
 from .basic import compute_edge_data, compute_properties
 from .electronic import ChargeEmbedding, SpinEmbedding
 from .output import resolve_output
@@ -136,8 +137,95 @@ class XPaiNN(BaseModel):
             self.mods[f"update_{action_blocks - 1}"].equivariant_output_unused = True
 
 
+class PaiNN(BaseModel):
+    """PaiNN (nn/model.py:261-307): Embedding, action_blocks x (PainnMessage, PainnUpdate), the output heads.
+
+    An inference evaluation (eval mode or frozen parameters) in f32 on the GPU runs the kernels of csrc/xeq_painn.hip with their
+    explicit reverse passes; f64, CPU tensors, widths / activations without a kernel and every training pass run the tensor form of
+    nn/painn.py, which autograd differentiates twice."""
+
+    def __init__(self, **kwargs) -> None:
+        super().__init__()
+        from .painn import Embedding, PainnMessage, PainnUpdate
+
+        node_dim: int = kwargs.get("node_dim", 128)
+        embed_basis: str = kwargs.get("embed_basis", "gfn2-xtb")
+        aux_basis: str = kwargs.get("aux_basis", "aux56")
+        num_basis: int = kwargs.get("num_basis", 20)
+        rbf_kernel: str = kwargs.get("rbf_kernel", "bessel")
+        cutoff: float = kwargs.get("cutoff", 5.0)
+        cutoff_fn: str = kwargs.get("cutoff_fn", "cosine")
+        action_blocks: int = kwargs.get("action_blocks", 3)
+        activation: str = kwargs.get("activation", "silu")
+        output_modes: Union[str, List[str]] = kwargs.get("output_modes", ["energy"])
+
+        self.cutoff_radius = cutoff
+        self.action_blocks = action_blocks
+        self.mods["embedding"] = Embedding(node_dim=node_dim, embed_basis=embed_basis, aux_basis=aux_basis, num_basis=num_basis,
+                                           rbf_kernel=rbf_kernel, cutoff=cutoff, cutoff_fn=cutoff_fn)
+        for i in range(action_blocks):
+            self.mods[f"message_{i}"] = PainnMessage(node_dim=node_dim, num_basis=num_basis, activation=activation)
+            self.mods[f"update_{i}"] = PainnUpdate(node_dim=node_dim, activation=activation)
+        if output_modes is None:
+            output_modes = ["energy"]
+        elif isinstance(output_modes, str) or not isinstance(output_modes, Iterable):
+            output_modes = [output_modes]
+        from .output import EnergyOut
+
+        for mode in output_modes:
+            output = resolve_output(mode, **kwargs)
+            if not isinstance(output, EnergyOut):   # forward evaluates the energy head alone in the tensor form (f64, CPU, training)
+                raise NotImplementedError(f"PaiNN: output mode {mode!r} is not supported, this model has the energy head only")
+            self.mods[f"output_{mode}"] = output
+            self.extra_properties.extend(output.extra_properties)
+        # the heads read the node scalars only: the last update block's vector output has no consumer and is not formed
+        if action_blocks > 0 and all(not getattr(self.mods[f"output_{m}"], "reads_equivariant", False) for m in output_modes):
+            self.mods[f"update_{action_blocks - 1}"].equivariant_output_unused = True
+
+    def tensor_form(self, data: Dict[str, torch.Tensor]) -> bool:
+        from . import painn
+
+        pos = data[keys_.POSITIONS]
+        return bool(training.wants_training_pass(self) or not pos.is_cuda or pos.dtype != torch.float32 or not painn.native_supported(self))
+
+    def run_blocks(self, data: Dict[str, torch.Tensor], compute_forces: bool, compute_virial: bool):
+        """Edge geometry, the blocks and the heads: (data with the energies still attached to autograd, whether the reverse pass
+        must itself be differentiable).  ``forward`` derives forces / virial from it; a front whose caller differentiates the energy
+        (interface/md_model.py) stops here."""
+        from . import painn
+        from .output import EnergyOut
+
+        tensor_form = self.tensor_form(data)
+        create_graph = tensor_form and training.wants_training_pass(self)
+        data[painn.TENSOR_FORM] = tensor_form
+        data[training.PARAM_GRADS] = False
+        data[training.TRAIN_PASS] = False   # (the heads' own switch: the tensor form evaluates them here)
+        if tensor_form:
+            data = painn.tensor_edge_data(data, compute_forces=compute_forces, compute_virial=compute_virial)
+        else:
+            training.active(self, data)   # (says once that an eval-mode evaluation fills no parameter gradients)
+            data = compute_edge_data(data=data, compute_forces=compute_forces, compute_virial=compute_virial)
+            # a new collector per evaluation: a reverse pass that was cut short leaves nothing behind for the next one
+            collector = painn._EdgeGrad() if (compute_forces or compute_virial) else None
+            if collector is not None:
+                collector.registered = self.action_blocks
+            data[painn.EDGE_GRAD] = collector
+            data["_xeq_painn_x_is_zero"] = True   # consumed by the first message block: its vector input is the embedding's zeros
+        for mod in self.mods.values():
+            if tensor_form and isinstance(mod, EnergyOut):
+                data = painn.tensor_energy_out(mod, data)
+            else:
+                data = mod(data)
+        return data, create_graph
+
+    def forward(self, data: Dict[str, torch.Tensor], compute_forces: bool = True, compute_virial: bool = False) -> Dict[str, torch.Tensor]:
+        data, create_graph = self.run_blocks(data, compute_forces, compute_virial)
+        return compute_properties(data=data, compute_forces=compute_forces, compute_virial=compute_virial, training=create_graph,
+                                  extra_properties=self.extra_properties)
+
+
 def resolve_model(model_name: str, **kwargs) -> BaseModel:
-    models_factory = {"xpainn": XPaiNN}
+    models_factory = {"xpainn": XPaiNN, "painn": PaiNN}
     if model_name.lower() not in models_factory:
         raise NotImplementedError(f"Unsupported model {model_name}")
     return models_factory[model_name.lower()](**kwargs)

@@ -44,7 +44,10 @@ def refuse_electronic(model, who: str) -> None:
         m = m.model
     if isinstance(m, torch.nn.Module):
         from .nn.electronic import ChargeEmbedding, SpinEmbedding
+        from .nn.model import PaiNN
 
+        if isinstance(m, PaiNN):   # the capacity-sized edge lists of the whole-step classes are not wired to the PaiNN kernels
+            raise NotImplementedError(f"{who} does not take a PaiNN model: use GraphedModel (per-signature capture) or the eager model")
         if any(isinstance(x, (ChargeEmbedding, SpinEmbedding)) for x in m.modules()):
             raise ValueError(f"{who} takes no charge / spin input: a model with a charge or spin embedding is refused "
                              "(use GraphedModel, which captures data['charge'] / data['spin'], or the eager model)")
