@@ -4,7 +4,8 @@ plain torch operations, for the fixture checks (tests/test_painn_host.py) and as
 Functional on a reference-layout state dict ``p``: ``embedding.embedding.1.weight`` (or ``embedding.embedding.weight`` for the
 one-hot table), ``embedding.rbf.freq``, ``message_i.scalar_mlp.{0,2}.*``, ``message_i.rbf_lin.*``, ``update_i.update_{U,V}.weight``,
 ``update_i.update_mlp.{0,2}.*``; autograd runs through all of them.  Node vectors are Cartesian [N, 3, F] in x, y, z order.
-Bessel basis and cosine envelope only (the defaults of the model)."""
+Bessel basis and cosine envelope only (the defaults of the model); the other radial kinds and the polynomial envelope, with ``h``
+and ``a`` as inputs, are restated in tests/painn_kernel_cases.py (pinned to ``message`` / ``update`` here for Bessel + cosine)."""
 import math
 
 import numpy as np
