@@ -68,7 +68,12 @@ constexpr int wq_tail_values(int num_basis) { return (num_basis > 16 ? num_basis
 constexpr int wq_ks(int num_basis) {
   return wq_tail_values(num_basis) <= 1 ? 1 : (wq_tail_values(num_basis) <= 5 ? 3 : ((wq_tail_values(num_basis) + 1) / 2 < 4 ? 4 : (wq_tail_values(num_basis) + 1) / 2));
 }
+// xeq_edge_basis_wq lays the records out for wq_ks(num_basis) itself; the kernels that read them are instantiated for KS in {1, 3, 4, 8}
+// only (wq_ks_template: 5, 6, 7 run as 8 on zero-filled tail positions).  Both must mean the same record for every step count.
+static_assert(wq_tailw(5) == wq_tailw(8) && wq_tailw(6) == wq_tailw(8) && wq_tailw(7) == wq_tailw(8) && !wq_bftail(5) && !wq_bftail(8),
+              "records written for 5, 6 or 7 tail steps are read by the KS = 8 kernels");
 constexpr int WQ_REC_MAX = 48;
+static_assert(wq_recf(8) == WQ_REC_MAX && wq_recf(4) == 40 && wq_recf(1) == wq_recf(4) && wq_recf(3) == wq_recf(4), "record widths of include/xeq.h");
 __device__ __forceinline__ uint32_t wq_bf16_rne(float x) {
   const uint32_t u = __float_as_uint(x);
   return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
@@ -1796,7 +1801,7 @@ static int wq_check(const char* who, int64_t n_nodes, int64_t n_edges, int n_ran
   XEQ_CHECK_ARG(n_nodes >= 0 && n_edges >= 0 && n_edges < (1ll << 31) && n_nodes < (1ll << 30), "%s: bad sizes", who);
   XEQ_CHECK_ARG(n_ranges >= 1, "%s: the stream table must cover every node (n_ranges >= 1)", who);
   if (!wq_supported(num_basis, node_dim, mul)) {
-    xeq::set_error("%s: the wave / quad form needs node_dim == mul[0], multiplicities in multiples of 32 and num_basis <= 23", who);
+    xeq::set_error("%s: the wave / quad form needs node_dim == mul[0], multiplicities in multiples of 32 and num_basis <= 31", who);
     return XEQ_ERR_UNSUPPORTED;
   }
   XEQ_CHECK_ARG(wq_fits(n_nodes, n_edges, node_dim, mul), "%s: tensors too large for 32-bit byte offsets (shard the batch)", who);
