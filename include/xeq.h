@@ -853,6 +853,31 @@ int xeq_painn_update_uv_bwd(int64_t n, int node_dim, const float* g_s, const flo
 /* out = a + b (n floats): the two paths of dL/ds behind a message block */
 int xeq_painn_add(const float* a, const float* b, int64_t n, float* out, void* stream);
 
+/* Property heads of XPaiNN (nn/output.py:28-76 ScalarOut, :131-179 AtomicChargesOut, :245-326 PolarOut), f32 inference,
+ * csrc/xeq_heads.hip.  The scalar and charge MLPs run on the energy head's kernels (xeq_head_fwd / xeq_linear_fwd + xeq_head_dot).
+ * xeq_head_polar_nodes: PolarOut per node in one launch over tiles of 32 nodes,
+ *   t[n] = (a0 t0, a2 t2[0..5), 0, 0),  (a0, a2) = scalar_out_mlp(s_n),  (t0, t2) = equi_out_mlp(x_n) (o3.Linear - Gate - o3.Linear;
+ *   the gate is sigmoid(sqrt(sum_m h^2 + eps^2) - eps) per channel; the 1o block of x is not read).
+ * s [n, lds], x [n, ldx] with the 0e block at column 0 and the 2e block at column off2 (strides and off2 multiples of 4, buffers
+ * 16-byte aligned); rows past n are neither read nor written.  The three hidden products are exact-f32 matrix-core tiles:
+ * ws1_packed = xeq_mlp_pack(scalar_out_mlp.0.weight, bias) with hidden_dim rounded up to a multiple of 32 by zero rows,
+ * w0_packed / w2_packed the same for the 0e / 2e blocks of equi_out_mlp.0.weight, transposed to [mul_out, mul_in] and scaled by
+ * 1 / sqrt(mul_in) (the 0e copy carries the o3 bias, the 2e copy none).  ws2 [2, hidden_dim], bs2 [2], wb [hid0 + hid2] (flat
+ * equi_out_mlp.2.weight), bb [1].  t [n, 8]: six values and two zeros.
+ * xeq_head_polar_supported (1 / 0, not a status): f32 (SiLU is the only activation); node_dim, mul0 multiples of 32, <= 256; mul2 a
+ * multiple of 8, <= 64; hidden_dim, hid0 multiples of 4, <= 128; hid2 a multiple of 4, <= 32; the tile's LDS within 160 KB.
+ * xeq_head_graph_reduce: per graph g the sum of `width` (<= 8) columns of src rows ptr[g] .. ptr[g + 1] - 1, one wave per graph, lane
+ * l adding rows ptr[g] + l, + 64, ... and a fixed butterfly -- no atomics, the order depends on the atom's index in its graph alone,
+ * so a graph's result is bit-identical alone, in a batch and in a shard.  mode 0: out [G, width] = sum; 1: mean; 2 (width 6): out
+ * [G, 9] = z I + A of nn/output.py:301-320 and iso [G] = tr / 3 when iso is given; 3 (width 1): src[i] += (total[g] - sum) / n_g
+ * over the graph's rows (total NULL: zero).  An empty graph gives zeros and divides nothing.  Neither entry has a reverse pass. */
+int xeq_head_polar_supported(int dtype, int node_dim, int mul0, int mul2, int hidden_dim, int hid0, int hid2);
+int xeq_head_polar_nodes(const void* s, int64_t lds, const void* x, int64_t ldx, int64_t n, int node_dim, int mul0, int mul2, int off2,
+                         int hidden_dim, int hid0, int hid2, const void* ws1_packed, const void* w0_packed, const void* w2_packed,
+                         const void* ws2, const void* bs2, const void* wb, const void* bb, double eps, void* t, void* stream);
+int xeq_head_graph_reduce(int mode, void* src, int64_t ld, int width, const int64_t* ptr, int64_t n_graphs, const void* total, void* out,
+                          void* iso, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from .. import keys, ops
 from ..data.radius_graph import single_radius_graph
 from ..nn.basic import compute_edge_data, compute_properties
 from ..nn.model import BaseModel, PaiNN, XPaiNN
+from ..nn.output import refuse_extra_heads
 from ..utils import get_default_units, unit_conversion
 
 
@@ -41,6 +42,7 @@ class XPaiNNLMP(XPaiNN):
         (``xeq::xpainn_eval``, every kernel enqueued from C++: the numbers of the Python modules at a third of their host
         time; fp32, a copy of the parameters is taken at first use) -- what ``interface.scripted.XPaiNNLMPScript`` runs."""
         super().__init__(**kwargs)
+        refuse_extra_heads(self, "XPaiNNLMP")   # an MD engine takes the energy and its derivatives
         self._init_front(unit_style, net_charge, replay, tune_gemms, native)
 
     def _init_front(self, unit_style: str, net_charge: Optional[int], replay: bool, tune_gemms: bool, native: bool) -> None:
@@ -176,6 +178,7 @@ class XPaiNNGMX(XPaiNN):
         read back in front of the model, no re-capture when the count moves -- what a trajectory wants."""
         kwargs.pop("unit_style", None)
         super().__init__(**kwargs)
+        refuse_extra_heads(self, "XPaiNNGMX")
         self._whole_step, self._step_graph = bool(whole_step), None
         self.pos_unit_factor = unit_conversion("nm", _default_unit(keys.POSITIONS))
         self.energy_unit_factor = unit_conversion(_default_unit(keys.TOTAL_ENERGY), "kJ/mol")

@@ -96,6 +96,9 @@ class XPaiNNNative(nn.Module):
             raise NotImplementedError("xeq::xpainn_eval evaluates XPaiNN only: a PaiNN model runs through the Python modules (nn/painn.py)")
         if not isinstance(model, XPaiNN):
             raise TypeError("XPaiNNNative wraps an nn.XPaiNN")
+        from ..nn.output import refuse_extra_heads
+
+        refuse_extra_heads(model, "XPaiNNNative (xeq::xpainn_eval)")
         electronic = [model.mods[k] for k in ("charge_embedding", "spin_embedding") if k in model.mods]
         for e in electronic:
             if not (isinstance(e.residual.mlp[1], nn.SiLU) and isinstance(e.residual.mlp[3], nn.SiLU)
@@ -243,6 +246,9 @@ def compile_model(model, mode: str = "lmp", unit_style: str = "metal", output_fi
 
     if isinstance(model, PaiNN):
         raise NotImplementedError("compile_model scripts the xeq::xpainn_eval operator, which evaluates XPaiNN only: a PaiNN model is not scriptable")
+    from ..nn.output import refuse_extra_heads
+
+    refuse_extra_heads(model, "compile_model")
     if mode == "lmp":
         front = XPaiNNLMPScript(model, unit_style=unit_style, net_charge=net_charge)
     elif mode == "gmx":

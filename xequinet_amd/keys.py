@@ -36,6 +36,11 @@ ENERGY_PER_ATOM: Final[str] = "energy/atom"     # loss-only property (utils/loss
 
 TOTAL_CHARGE: Final[str] = "charge"
 TOTAL_SPIN: Final[str] = "spin"
+# outputs of the property heads (keys.py:42-83 of the reference)
+ATOMIC_CHARGES: Final[str] = "atomic_charges"
+POLARIZABILITY: Final[str] = "polarizability"
+ISO_POLARIZABILITY: Final[str] = "iso_polarizability"
+SCALAR_OUTPUT: Final[str] = "scalar_output"
 
 GRAD_PROPERTIES: Final[Set[str]] = {FORCES, VIRIAL}
 

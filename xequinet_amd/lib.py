@@ -199,6 +199,10 @@ _PROTOS = {
     "xeq_painn_update_out_bwd": [c_int64, c_int, _P, _P, _P, _P, _P, _P],
     "xeq_painn_update_uv_bwd": [c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "xeq_painn_add": [_P, _P, c_int64, _P, _P],
+    "xeq_head_polar_supported": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
+    "xeq_head_polar_nodes": [_P, c_int64, _P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
+                             c_double, _P, _P],
+    "xeq_head_graph_reduce": [c_int, _P, c_int64, c_int, _P, c_int64, _P, _P, _P, _P],
 }
 # entry points that return a size, not a status
 _RET_I64 = {"xeq_launch_count", "xeq_launch_names", "xeq_message_wq_packed_weight_floats", "xeq_rowptr_from_degrees_max", "xeq_csr_by_key_workspace", "xeq_message_wq_pcap", "xeq_message_wq_plan_workspace", "xeq_message_wq_win_ints",

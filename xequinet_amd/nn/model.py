@@ -12,7 +12,7 @@ from . import training
 from .. import keys as keys_
 from .basic import compute_edge_data, compute_properties
 from .electronic import ChargeEmbedding, SpinEmbedding
-from .output import resolve_output
+from .output import EnergyOut, resolve_output
 from .xpainn import XEmbedding, XPainnMessage, XPainnUpdate
 
 # e3nn bookkeeping entries of reference checkpoints that have no counterpart here
@@ -39,6 +39,9 @@ class BaseModel(nn.Module):
         # in its differentiable form so that the force evaluation can itself be differentiated (create_graph=training,
         # nn/basic.py:143-159); with energies only (no second order) the blocks stay on the fused kernels and return their
         # parameter gradients themselves (nn/fused.py); everything else is the fused inference path
+        if (compute_forces or compute_virial) and not any(isinstance(m, EnergyOut) for m in self.mods.values()):
+            raise KeyError(f"forces / virial are derivatives of {keys_.TOTAL_ENERGY!r}: this model has no \"energy\" output head "
+                           f"(heads: {[k for k in self.mods if k.startswith('output_')]}); call it with compute_forces=False")
         train_pass = training.wants_training_pass(self)
         native = train_pass and not compute_forces and not compute_virial and self.native_training and training.native_pass_supported(self)
         data[training.PARAM_GRADS] = native

@@ -34,6 +34,41 @@ class Invariant(nn.Module):
         return torch.sqrt(out + self.eps**2) - self.eps
 
 
+class Gate(nn.Module):
+    """nn/o3layer.py:47-75: every channel scaled by activation(Invariant) of its own irrep; ``activation`` is taken with
+    ``devide_x`` (SiLU -> sigmoid).  Without ``refine`` the module has no parameters.  ``forward`` is the tensor form (differentiable
+    device tensor operations); PolarOut's inference kernel applies the same gate inside its launch (csrc/xeq_heads.hip)."""
+
+    def __init__(self, irreps_in: Iterable, activation: str = "silu", refine: bool = False) -> None:
+        super().__init__()
+        from .basic import resolve_activation
+
+        irreps_in = o3.Irreps(irreps_in).simplify()
+        self.irreps_in = irreps_in
+        self.invariant = Invariant(irreps_in)
+        if refine:
+            self.activation = nn.Sequential(
+                nn.Linear(irreps_in.num_irreps, irreps_in.num_irreps),
+                resolve_activation(activation, devide_x=True),
+                nn.Linear(irreps_in.num_irreps, irreps_in.num_irreps),
+            )
+            nn.init.zeros_(self.activation[0].bias)
+            nn.init.zeros_(self.activation[2].bias)
+        else:
+            self.activation = resolve_activation(activation, devide_x=True)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        n, eps = x.shape[0], self.invariant.eps
+        parts = [x[:, off : off + mul * (2 * l + 1)].reshape(n, mul, 2 * l + 1) for mul, l, off, _ in self.irreps_in.blocks()]
+        inv = torch.cat([torch.sqrt((p * p).sum(-1) + eps**2) - eps for p in parts], dim=-1)
+        act = self.activation(inv)
+        out, ch = [], 0
+        for p in parts:
+            out.append((p * act[:, ch : ch + p.shape[1]].unsqueeze(-1)).reshape(n, -1))
+            ch += p.shape[1]
+        return torch.cat(out, dim=-1)
+
+
 class EquivariantDot(nn.Module):
     """nn/o3layer.py:79-109"""
 

@@ -46,9 +46,12 @@ def native_pass_supported(model: torch.nn.Module) -> bool:
     """Every block of the model has the fused form with parameter gradients (the blocks of this package with ``fused`` on)."""
     # (the parameter-gradient kernels of the radial filter take the Bessel and Gaussian bases: xeq_message_param_grad)
     # (the charge / spin embeddings have no parameter-gradient kernels: a model with one takes the differentiable form)
+    # (nor have the property heads: ScalarOut, AtomicChargesOut, PolarOut -- nn/output.py)
     from .electronic import ChargeEmbedding, SpinEmbedding
+    from .output import EnergyOut, OutputModule
 
     return (all(getattr(m, "fused", True) for m in model.modules())
+            and not any(isinstance(m, OutputModule) and not isinstance(m, EnergyOut) for m in model.modules())
             and not any(isinstance(m, (ChargeEmbedding, SpinEmbedding)) for m in model.modules())
             and all(getattr(m, "kind", "bessel") in ("bessel", "gaussian") for m in model.modules() if hasattr(m, "params") and hasattr(m, "num_basis")))
 

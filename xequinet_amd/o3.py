@@ -194,24 +194,63 @@ class TensorProduct(nn.Module):
 
 
 class Linear(nn.Module):
-    """``e3nn.o3.Linear(irreps_in, irreps_out, biases=True)`` for equal in/out irreps
-    (nn/xpainn.py:186-187): out[w,m] = mul^-1/2 sum_u W_l[u,w] x[u,m]; flat weight =
-    concat of row-major [mul, mul] blocks, ~N(0,1); bias (zeros) on 0e only."""
+    """``e3nn.o3.Linear(irreps_in, irreps_out, biases=True)``: out[w,m] = mul_in^-1/2 sum_u W_l[u,w] x[u,m], one path per irrep
+    that both sides hold; flat weight = concat of row-major [mul_in, mul_out] blocks in the order of the input irreps, ~N(0,1); bias
+    (zeros) on the 0e output only.  Equal in/out irreps (nn/xpainn.py:186-187) run library GEMMs on contiguous copies; the rectangular
+    form (the output heads, nn/output.py:277-281: input blocks without a partner are unread) is written on differentiable tensor
+    operations -- PolarOut's inference kernel reads the same parameters (csrc/xeq_heads.hip)."""
 
     def __init__(self, irreps_in, irreps_out, biases: bool = False) -> None:
         super().__init__()
         self.irreps_in = Irreps(irreps_in)
         self.irreps_out = Irreps(irreps_out)
-        if self.irreps_in != self.irreps_out:
-            raise NotImplementedError("only irreps_in == irreps_out is on the XPaiNN path")
-        self._mul = self.irreps_in.mul3()
-        n_w = sum(mul * mul for mul, _ in self.irreps_in)
+        self.square = self.irreps_in == self.irreps_out
+        if self.square:
+            self._mul = self.irreps_in.mul3()
+            n_w = sum(mul * mul for mul, _ in self.irreps_in)
+        else:
+            for irreps in (self.irreps_in, self.irreps_out):
+                if len({ir for _, ir in irreps}) != len(irreps):
+                    raise NotImplementedError(f"o3.Linear: irreps {irreps} hold an irrep twice")
+            n_w = sum(m_in * m_out for m_in, ir_in in self.irreps_in for m_out, ir_out in self.irreps_out if ir_in == ir_out)
         self.weight = nn.Parameter(torch.randn(n_w))
-        n_b = sum(mul for mul, ir in self.irreps_in if ir.l == 0 and ir.p == 1) if biases else 0
+        n_b = sum(mul for mul, ir in self.irreps_out if ir.l == 0 and ir.p == 1) if biases else 0
         self.bias = nn.Parameter(torch.zeros(n_b))
+
+    def paths(self):
+        """(mul_in, mul_out, l, offset of the input block, offset of the weight block, is 0e) per output block, in the order of the
+        output irreps; mul_in = 0 for an output block without a partner (it is zero)."""
+        off, table = 0, {}
+        for (m_in, ir_in), (_, _, x_off, _) in zip(self.irreps_in, self.irreps_in.blocks()):
+            for m_out, ir_out in self.irreps_out:
+                if ir_in == ir_out:
+                    table[ir_in] = (m_in, x_off, off)
+                    off += m_in * m_out
+        out = []
+        for m_out, ir in self.irreps_out:
+            m_in, x_off, w_off = table.get(ir, (0, 0, 0))
+            out.append((m_in, m_out, ir.l, x_off, w_off, ir.l == 0 and ir.p == 1))
+        return out
+
+    def _rectangular(self, x: torch.Tensor) -> torch.Tensor:
+        n, parts, b_off = x.shape[0], [], 0
+        for m_in, m_out, l, x_off, w_off, scalar in self.paths():
+            d = 2 * l + 1
+            if m_in == 0:
+                ob = x.new_zeros((n, m_out, d))
+            else:
+                W = self.weight[w_off : w_off + m_in * m_out].view(m_in, m_out)
+                ob = torch.einsum("uw,num->nwm", W, x[:, x_off : x_off + m_in * d].reshape(n, m_in, d)) * (1.0 / math.sqrt(m_in))
+            if scalar and self.bias.numel() > 0:
+                ob = ob + self.bias[b_off : b_off + m_out].view(1, m_out, 1)
+                b_off += m_out
+            parts.append(ob.reshape(n, m_out * d))
+        return torch.cat(parts, dim=-1)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         ops.lib.require_hip(x)
+        if not self.square:
+            return self._rectangular(x)
         n = x.shape[0]
         parts = []
         woff = 0

@@ -48,6 +48,9 @@ def refuse_electronic(model, who: str) -> None:
 
         if isinstance(m, PaiNN):   # the capacity-sized edge lists of the whole-step classes are not wired to the PaiNN kernels
             raise NotImplementedError(f"{who} does not take a PaiNN model: use GraphedModel (per-signature capture) or the eager model")
+        from .nn.output import refuse_extra_heads
+
+        refuse_extra_heads(m, who)   # these classes return the energy and its derivatives only (nn/output.py)
         if any(isinstance(x, (ChargeEmbedding, SpinEmbedding)) for x in m.modules()):
             raise ValueError(f"{who} takes no charge / spin input: a model with a charge or spin embedding is refused "
                              "(use GraphedModel, which captures data['charge'] / data['spin'], or the eager model)")
