@@ -678,7 +678,7 @@ int xeq_update_out_bwd(int dtype, const void* g_s_out, const void* g_x_out, cons
                        const void* ip, int64_t n, int node_dim, const int32_t mul[3], void* g_a, void* g_ip,
                        void* g_uv_bt, void* stream);
 
-/* ---- two-layer scalar MLPs on the matrix cores (f32, hidden width 128) ----------------------------
+/* ---- two-layer scalar MLPs on the matrix cores (f32; hidden width 128: xeq_mlp2_*, 32 .. 256: xeq_mlp2h_*) ----
  * Replace nn.Sequential(Linear, SiLU, Linear) of XPainnMessage.scalar_mlp (nn/xpainn.py:103-107) and
  * XPainnUpdate.update_mlp (nn/xpainn.py:177-181) and their input gradients: one launch each, the hidden
  * activations stay on chip.  Weights are read from a packed copy in matrix-core fragment order with the bias as one
@@ -702,10 +702,23 @@ int xeq_mlp2_fwd(const float* x, int64_t ldx, int64_t n, int k1, const float* w1
 /* gx[n, n2] = ((g[n, k1] W2) * silu'(pre)) W1 with k1 = the forward's n2 and n2 = the forward's k1. */
 int xeq_mlp2_bwd(const float* g, int64_t ldg, int64_t n, int k1, const float* w2t_packed, const float* pre,
                  const float* w1t_packed, int n2, float* gx, int64_t ldgx, void* stream);
+/* The same two products with the hidden width given at the call: `hidden` = 32, 64, ..., 256 (the node_dim the message, PaiNN,
+ * electronic and head kernels take), k1 % 32 == 0, n2 % 32 == 0, f32 (`dtype` is checked, not dispatched on), row strides % 4 == 0.
+ * xeq_mlp2h_supported answers 1 exactly there; outside it _fwd / _bwd return XEQ_ERR_INVALID_ARGUMENT with a message and launch
+ * nothing.  The packed copies are those above with 128 replaced by `hidden`; pre is [n, hidden].  hidden == 128 IS xeq_mlp2_fwd /
+ * _bwd (same kernels, launch name and bits).  The other widths run one 32-row kernel at every row count (few rows are shared among
+ * workgroups by output tile), recorded as xeq_mlp2h_fwd / xeq_mlp2h_bwd: a row's bits depend on neither the row count nor the
+ * workgroup that computed it, and per element the sums are taken in the order of the 128-wide kernels. */
+int xeq_mlp2h_supported(int dtype, int k1, int hidden, int n2);
+int xeq_mlp2h_fwd(int dtype, const float* x, int64_t ldx, int64_t n, int k1, int hidden, const float* w1_packed, const float* w2_packed, int n2,
+                  float* pre, float* y, int64_t ldy, void* stream);
+int xeq_mlp2h_bwd(int dtype, const float* g, int64_t ldg, int64_t n, int k1, int hidden, const float* w2t_packed, const float* pre,
+                  const float* w1t_packed, int n2, float* gx, int64_t ldgx, void* stream);
 /* XPainnUpdate's two independent products side by side (reference nn/xpainn.py:219-223: a = update_mlp([shat | v]) and dot_lin(<U, V>);
  * reverse = 1: their input gradients): xeq_mlp2_fwd (reverse: xeq_mlp2_bwd with stage1_packed = w2t_packed, stage2_packed = w1t_packed)
  * and xeq_linear_fwd without bias / activation / row gather on the same n rows.  One launch when n takes the few-row forms
- * (XEQ_SMALL_ROWS, csrc/xeq_common.h), else the two launches in this order.  The same bits as the separate entry points. */
+ * (XEQ_SMALL_ROWS, csrc/xeq_common.h), else the two launches in this order.  The same bits as the separate entry points.  Hidden width 128 only: at the other
+ * widths the callers issue xeq_mlp2h_fwd / _bwd and xeq_linear_fwd themselves. */
 int xeq_mlp2_and_linear(int reverse, const float* x, int64_t ldx, int64_t n, int k1, const float* stage1_packed, const float* stage2_packed,
                         int n2, float* pre, float* y, int64_t ldy, const float* lin_x, int64_t lin_ldx, int lin_k,
                         const float* lin_w_packed, int lin_n_out, float* lin_y, int64_t lin_ldy, void* stream);

@@ -1,7 +1,8 @@
 // Two-layer scalar MLPs of XPainnMessage / XPainnUpdate on the matrix cores, one launch each:
 //   forward   Y  = silu(X W1^T + b1) W2^T + b2          (nn/xpainn.py:103-107 scalar_mlp, :177-181 update_mlp)
 //   reverse   GX = ((G W2) * silu'(pre)) W1              (input gradients only: force evaluation, nn/basic.py:143-159)
-// Both are T = E(X B1 + c1), Y = T B2 + c2 with a 128-wide hidden T that never leaves the chip.
+// Both are T = E(X B1 + c1), Y = T B2 + c2 with a hidden T that never leaves the chip: 128 wide in k_mlp2 / k_mlp2_r64 / k_mlp2_s
+// (node_dim of the default model), any multiple of 32 up to 256 in k_mlp2h below (the other node_dim the rest of the path takes).
 //
 // Work split: a workgroup (4 waves) owns 32 consecutive rows (nodes); few tiles, or the tiles of a short last round, are shared
 // by several workgroups (TileSplit, xeq_common.h).  Exact-f32 v_mfma_f32_32x32x2_f32 tiles D[column][row]: the WEIGHT fragment is
@@ -543,6 +544,172 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
   }
 }
 
+// ---- run-time hidden width (xeq_mlp2h_fwd / _bwd) -----------------------------------------------------------------------------------
+// k_mlp2 for a hidden width H = 32 nh, nh = 1 .. 8, known at launch: the same 32 rows per workgroup, the same packed weights, the same
+// chain per element (stage 1: even / odd accumulators over the k slots (x, z) / (y, w) of every group, the bias on the even one, then
+// their sum; stage 2: one chain in k order, the bias last).  Stage 1 runs in ceil(nh / 4) PASSES: in pass p wave w forms hidden tile
+// w + 4 p (none: it only helps staging) from the X chunks, which are staged again per pass (32 rows x K1 out of L2; the MFMA work per
+// hidden tile is what it was, and one pass keeps the registers of k_mlp2: three waves per SIMD).  The hidden tile [32][H + 4] sits in
+// LDS (dynamic: 17 KB of X chunks + 4.6 .. 33 KB), stage 2 walks output tiles w + 4 part, + 4 parts, ... one at a time, its weights
+// fetched a quarter (4 k-groups) ahead.  One row form for every row count (few rows: TileSplit shares a row tile among workgroups), so
+// a row's bits depend on nothing but the row.  Why no 64-row or 16-row form: DESIGN section 4.
+constexpr int MLP_HMAX = 256;
+
+template <bool REVERSE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) k_mlp2h(MlpArgs a, int H) {
+  extern __shared__ __attribute__((aligned(16))) float mlp_h_lds[];
+  float* Xs = mlp_h_lds;                            // [2][32][MLP_XLD]
+  float* Ts = mlp_h_lds + 2 * MLP_ROWS * MLP_XLD;   // [32][H + 4]
+  const int TLD = H + 4, nh = H >> 5;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int i = lane & 31, kh = lane >> 5;
+  int tile_, part_, parts_;
+  a.ts.decode((int)blockIdx.x, tile_, part_, parts_);
+  const int64_t row0 = (int64_t)tile_ * MLP_ROWS;
+  const int n_chunks = (a.K1 + MLP_CK - 1) / MLP_CK;
+  const int g1 = a.K1 / 8;
+  const int sr = tid >> 4, sc = (tid & 15) * 4;
+  // loads as in k_mlp2: unconditional, from clamped addresses; rows / columns out of range become zeros on their way into LDS
+  const int rows_here = (int)min((int64_t)MLP_ROWS, a.n - row0);
+  const float* __restrict__ xb = a.X + row0 * a.ldx;
+  float* __restrict__ preb = a.pre + row0 * H;
+  float* __restrict__ yo = a.Y + row0 * a.ldy;
+  const unsigned ldx32 = (unsigned)a.ldx, ldy32 = (unsigned)a.ldy;
+  const unsigned r0c = (unsigned)min(sr, rows_here - 1) * ldx32, r1c = (unsigned)min(sr + 16, rows_here - 1) * ldx32;
+  const bool r0ok = sr < rows_here, r1ok = sr + 16 < rows_here;
+  const bool row_ok = i < rows_here;
+  const unsigned ic = (unsigned)min(i, rows_here - 1);
+  auto fetch = [&](int c, float4& v0, float4& v1) {
+    const int colc = min(MLP_CK * c + sc, a.K1 - 4);
+    v0 = *reinterpret_cast<const float4*>(xb + (r0c + (unsigned)colc));
+    v1 = *reinterpret_cast<const float4*>(xb + (r1c + (unsigned)colc));
+  };
+  auto stash = [&](int c, const float4& v0, const float4& v1) {
+    const bool cok = MLP_CK * c + sc < a.K1;
+    float* xd = Xs + (c & 1) * (MLP_ROWS * MLP_XLD);
+    *reinterpret_cast<float4*>(&xd[sr * MLP_XLD + sc]) = keep4(r0ok && cok, v0);
+    *reinterpret_cast<float4*>(&xd[(sr + 16) * MLP_XLD + sc]) = keep4(r1ok && cok, v1);
+  };
+  const float one_k0 = kh == 0 ? 1.f : 0.f;
+  float4 x0, x1, B0[4], B1[4];
+
+  // ---- stage 1: T[32, H] = X[32, K1] B1 + c1, hidden tile wave + 4 p in pass p --------------------------------------------------------
+  for (int p = 0; 4 * p < nh; ++p) {
+    const bool mine = wave + 4 * p < nh;               // wave-uniform
+    const int ht = mine ? wave + 4 * p : 0;            // (a tile that exists, for the addresses of a wave without one)
+    const float4* w1 = reinterpret_cast<const float4*>(a.W1p) + (int64_t)ht * (g1 + 1) * 64;
+    auto fetch_w = [&](float4 (&b)[4], int g0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) b[q] = w1[min(g0 + q, g1 - 1) * 64 + lane];   // past K1: any finite weight, the staged rows are zero there
+    };
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc0[r] = 0.f;
+      acc1[r] = 0.f;
+    }
+    float bias_a = 0.f;
+    if (a.bias1) bias_a = reinterpret_cast<const float*>(w1 + (int64_t)g1 * 64 + lane)[0];
+    float4 pv[4];
+    if (REVERSE) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) pv[g] = *reinterpret_cast<const float4*>(preb + (ic * (unsigned)H + (unsigned)(32 * ht + 8 * g + 4 * kh)));
+    }
+    fetch(0, x0, x1);
+    fetch_w(B0, 0);
+    stash(0, x0, x1);   // (every wave is past the last chunk of the pass before: the barrier that ends its loop)
+    MLP_LDS_BARRIER();
+    for (int c = 0; c < n_chunks; ++c) {
+      const bool more = c + 1 < n_chunks;
+      if (more) fetch(c + 1, x0, x1);
+      const float* xs = Xs + (c & 1) * (MLP_ROWS * MLP_XLD) + i * MLP_XLD + 4 * kh;
+      auto half = [&](const float4 (&b)[4], int h) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 xv = *reinterpret_cast<const float4*>(xs + 8 * (4 * h + q));
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[q].x, xv.x, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[q].y, xv.y, acc1, 0, 0, 0);
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[q].z, xv.z, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b[q].w, xv.w, acc1, 0, 0, 0);
+        }
+      };
+      fetch_w(B1, 8 * c + 4);
+      MLP_SB();
+      if (mine) half(B0, 0);
+      MLP_SB();
+      fetch_w(B0, 8 * c + 8);
+      MLP_SB();
+      if (mine) half(B1, 1);
+      MLP_SB();
+      if (more) stash(c + 1, x0, x1);
+      MLP_LDS_BARRIER();
+    }
+    if (mine) {
+      if (a.bias1) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, one_k0, acc0, 0, 0, 0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int col = 32 * ht + 8 * g + 4 * kh;
+        const float4 t = make_float4(acc0[4 * g] + acc1[4 * g], acc0[4 * g + 1] + acc1[4 * g + 1], acc0[4 * g + 2] + acc1[4 * g + 2],
+                                     acc0[4 * g + 3] + acc1[4 * g + 3]);
+        float4 v;
+        if (!REVERSE) {
+          if (row_ok && part_ == 0) *reinterpret_cast<float4*>(preb + ((unsigned)i * (unsigned)H + (unsigned)col)) = t;
+          v = make_float4(silu_f(t.x), silu_f(t.y), silu_f(t.z), silu_f(t.w));
+        } else {
+          v = make_float4(t.x * silu_grad_f(pv[g].x), t.y * silu_grad_f(pv[g].y), t.z * silu_grad_f(pv[g].z), t.w * silu_grad_f(pv[g].w));
+        }
+        *reinterpret_cast<float4*>(&Ts[i * TLD + col]) = v;
+      }
+    }
+  }
+
+  // ---- stage 2: Y[32, N2] = T B2 + c2, output tiles wave + 4 part, + 4 parts, ... ------------------------------------------------------
+  const int nt2 = a.N2 / 32;
+  const int G2 = H >> 3;   // 4 nh k-groups
+  const float4* w2 = reinterpret_cast<const float4*>(a.W2p);
+  const int parts = __builtin_amdgcn_readfirstlane(parts_), part = __builtin_amdgcn_readfirstlane(part_);
+  auto fetch_q = [&](float4 (&b)[4], int t, int qq) {   // t: clamped to a tile that exists (what a wave past its last tile asks for is dropped)
+    const float4* wa = w2 + ((int64_t)min(t, nt2 - 1) * (G2 + 1) + 4 * qq) * 64;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) b[q] = wa[q * 64 + lane];
+  };
+  int t0 = wave + 4 * part;
+  fetch_q(B0, t0, 0);
+  MLP_LDS_BARRIER();   // the hidden tile is whole
+  const float* ts = &Ts[i * TLD + 4 * kh];
+  for (; t0 < nt2; t0 += 4 * parts) {
+    f32x16 ya;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ya[r] = 0.f;
+    float bias_ya = 0.f;
+    if (a.bias2) bias_ya = reinterpret_cast<const float*>(w2 + ((int64_t)t0 * (G2 + 1) + G2) * 64 + lane)[0];
+    for (int qq = 0; qq < nh; ++qq) {
+      const bool last = qq + 1 == nh;
+      fetch_q(B1, last ? t0 + 4 * parts : t0, last ? 0 : qq + 1);
+      MLP_SB();
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 tv = *reinterpret_cast<const float4*>(ts + 8 * (4 * qq + q));
+        ya = __builtin_amdgcn_mfma_f32_32x32x2f32(B0[q].x, tv.x, ya, 0, 0, 0);
+        ya = __builtin_amdgcn_mfma_f32_32x32x2f32(B0[q].y, tv.y, ya, 0, 0, 0);
+        ya = __builtin_amdgcn_mfma_f32_32x32x2f32(B0[q].z, tv.z, ya, 0, 0, 0);
+        ya = __builtin_amdgcn_mfma_f32_32x32x2f32(B0[q].w, tv.w, ya, 0, 0, 0);
+      }
+      MLP_SB();
+#pragma unroll
+      for (int q = 0; q < 4; ++q) B0[q] = B1[q];
+    }
+    if (a.bias2) ya = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_ya, one_k0, ya, 0, 0, 0);
+    if (row_ok) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<float4*>(yo + ((unsigned)i * ldy32 + (unsigned)(32 * t0 + 8 * g + 4 * kh))) =
+            make_float4(ya[4 * g], ya[4 * g + 1], ya[4 * g + 2], ya[4 * g + 3]);
+    }
+  }
+}
+
 // ---- few rows (MD-sized systems) ------------------------------------------------------------------------------------------------
 // 16 x 16 exact-f32 tiles (v_mfma_f32_16x16x4_f32): the same fused-multiply-add chain per output element as the 32-row form -- the
 // instruction rounds like a sequential fmaf chain in k order whatever its shape (xeq_linear.hip, scratch/mfma_order) -- so the results
@@ -713,6 +880,16 @@ static int mlp_check(const char* name, int64_t n, int k1, int n2, int64_t ldx, i
   return XEQ_OK;
 }
 
+template <bool REVERSE>
+static void mlp2h_launch(const float* x, int64_t ldx, int64_t n, int k1, int hidden, const float* s1p, const float* s2p, int n2, float* pre, float* y,
+                         int64_t ldy, hipStream_t stream) {
+  const int64_t tiles = (n + MLP_ROWS - 1) / MLP_ROWS;
+  const int b = REVERSE ? 0 : 1;
+  MlpArgs a{x, ldx, n, k1, n2, s1p, s2p, b, b, pre, y, ldy, tile_split(tiles, (n2 / 32 + 3) / 4)};
+  const size_t shmem = sizeof(float) * ((size_t)2 * MLP_ROWS * MLP_XLD + (size_t)MLP_ROWS * (hidden + 4));
+  hipLaunchKernelGGL(k_mlp2h<REVERSE>, dim3(a.ts.grid(tiles)), dim3(256), shmem, stream, a, hidden);
+}
+
 }  // namespace xeq
 
 using namespace xeq;
@@ -784,6 +961,41 @@ int xeq_mlp2_bwd(const float* g, int64_t ldg, int64_t n, int k1, const float* w2
   else if (r64) hipLaunchKernelGGL(k_mlp2_r64<true>, dim3(a.ts.grid(tiles)), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_mlp2<true>, dim3(a.ts.grid(tiles)), dim3(256), 0, (hipStream_t)stream, a);
   XEQ_CHECK_LAUNCH("xeq_mlp2_bwd");
+  return XEQ_OK;
+}
+
+/* The same two products for a hidden width given at the call (32, 64, ..., 256).  128 is xeq_mlp2_fwd / _bwd itself (every row form
+ * of it, the same launch name and bits); the other widths run k_mlp2h. */
+int xeq_mlp2h_supported(int dtype, int k1, int hidden, int n2) {
+  return dtype == XEQ_F32 && hidden >= 32 && hidden <= MLP_HMAX && hidden % 32 == 0 && k1 > 0 && k1 % 32 == 0 && n2 > 0 && n2 % 32 == 0;
+}
+
+#define MLP2H_CHECK(name)                                                                                                                   \
+  XEQ_CHECK_ARG(xeq_mlp2h_supported(dtype, k1, hidden, n2),                                                                                 \
+                name ": needs f32, hidden %% 32 == 0 in [32, %d], k1 %% 32 == 0 and n2 %% 32 == 0 (got dtype %d, k1 %d, hidden %d, n2 %d)", \
+                MLP_HMAX, dtype, k1, hidden, n2)
+
+int xeq_mlp2h_fwd(int dtype, const float* x, int64_t ldx, int64_t n, int k1, int hidden, const float* w1p, const float* w2p, int n2, float* pre,
+                  float* y, int64_t ldy, void* stream) {
+  MLP2H_CHECK("xeq_mlp2h_fwd");
+  if (hidden == MLP_H) return xeq_mlp2_fwd(x, ldx, n, k1, w1p, w2p, n2, pre, y, ldy, stream);
+  if (int rc = mlp_check("xeq_mlp2h_fwd", n, k1, n2, ldx, ldy)) return rc;
+  XEQ_CHECK_ARG(n == 0 || (x && w1p && w2p && pre && y), "xeq_mlp2h_fwd: null buffer");
+  if (n == 0) return XEQ_OK;
+  mlp2h_launch<false>(x, ldx, n, k1, hidden, w1p, w2p, n2, pre, y, ldy, (hipStream_t)stream);
+  XEQ_CHECK_LAUNCH("xeq_mlp2h_fwd");
+  return XEQ_OK;
+}
+
+int xeq_mlp2h_bwd(int dtype, const float* g, int64_t ldg, int64_t n, int k1, int hidden, const float* w2tp, const float* pre, const float* w1tp,
+                  int n2, float* gx, int64_t ldgx, void* stream) {
+  MLP2H_CHECK("xeq_mlp2h_bwd");
+  if (hidden == MLP_H) return xeq_mlp2_bwd(g, ldg, n, k1, w2tp, pre, w1tp, n2, gx, ldgx, stream);
+  if (int rc = mlp_check("xeq_mlp2h_bwd", n, k1, n2, ldg, ldgx)) return rc;
+  XEQ_CHECK_ARG(n == 0 || (g && w2tp && w1tp && pre && gx), "xeq_mlp2h_bwd: null buffer");
+  if (n == 0) return XEQ_OK;
+  mlp2h_launch<true>(g, ldg, n, k1, hidden, w2tp, w1tp, n2, const_cast<float*>(pre), gx, ldgx, (hipStream_t)stream);
+  XEQ_CHECK_LAUNCH("xeq_mlp2h_bwd");
   return XEQ_OK;
 }
 

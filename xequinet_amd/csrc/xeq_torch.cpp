@@ -123,12 +123,13 @@ Entry& packed(const void* slot_key, std::initializer_list<const Tensor*> tensors
 }
 
 // ---------------------------------------------------------------------------------------------- two-layer MLPs
-// Linear-SiLU-Linear on the matrix cores (xeq_mlp2_fwd / _bwd, csrc/xeq_mlp.hip) from fragment-order weight copies;
-// Python: nn/fused.py::_mlp_packs / _mlp_fwd / _mlp_bwd.
+// Linear-SiLU-Linear on the matrix cores (hidden width 128: xeq_mlp2_fwd / _bwd, 32 .. 256: xeq_mlp2h_fwd / _bwd, csrc/xeq_mlp.hip)
+// from fragment-order weight copies; Python: nn/fused.py::_mlp_packs / _mlp_fwd / _mlp_bwd.
+constexpr int64_t MLP_H = 128;   // the hidden width of xeq_mlp2_fwd / _bwd / xeq_mlp2_and_linear
 struct MlpPacks { Tensor w1p, w2p, w2tp, w1tp; };
 const MlpPacks* mlp_packs(const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2) {
   if (w1.scalar_type() != at::kFloat || b1.numel() == 0 || b2.numel() == 0 ||
-      !xeq_mlp2_supported(XEQ_F32, (int)w1.size(1), (int)w1.size(0), (int)w2.size(0)))
+      !xeq_mlp2h_supported(XEQ_F32, (int)w1.size(1), (int)w1.size(0), (int)w2.size(0)))
     return nullptr;
   return &packed<MlpPacks>(w1.data_ptr(), {&w1, &b1, &w2, &b2}, 0, [&](MlpPacks& e) {
     const int h = (int)w1.size(0), k1 = (int)w1.size(1), n2 = (int)w2.size(0);
@@ -168,8 +169,12 @@ void mlp_fwd(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& 
   const int64_t n = x.size(0);
   pre = at::empty({n, w1.size(0)}, x.options());
   y = at::empty({n, w2.size(0)}, x.options());
-  XCALL(xeq_mlp2_fwd((const float*)x.data_ptr(), x.stride(0), n, (int)w1.size(1), (const float*)pk->w1p.data_ptr(),
-                     (const float*)pk->w2p.data_ptr(), (int)w2.size(0), (float*)pre.data_ptr(), (float*)y.data_ptr(), w2.size(0), cur_stream()));
+  if (w1.size(0) == MLP_H)
+    XCALL(xeq_mlp2_fwd((const float*)x.data_ptr(), x.stride(0), n, (int)w1.size(1), (const float*)pk->w1p.data_ptr(),
+                       (const float*)pk->w2p.data_ptr(), (int)w2.size(0), (float*)pre.data_ptr(), (float*)y.data_ptr(), w2.size(0), cur_stream()));
+  else
+    XCALL(xeq_mlp2h_fwd(XEQ_F32, (const float*)x.data_ptr(), x.stride(0), n, (int)w1.size(1), (int)w1.size(0), (const float*)pk->w1p.data_ptr(),
+                        (const float*)pk->w2p.data_ptr(), (int)w2.size(0), (float*)pre.data_ptr(), (float*)y.data_ptr(), w2.size(0), cur_stream()));
 }
 Tensor mlp_bwd(const Tensor& g_y, const Tensor& pre, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2) {
   const MlpPacks* pk = mlp_packs(w1, b1, w2, b2);
@@ -177,8 +182,13 @@ Tensor mlp_bwd(const Tensor& g_y, const Tensor& pre, const Tensor& w1, const Ten
   const Tensor g = g_y.contiguous();
   const int64_t n = g.size(0);
   Tensor g_x = at::empty({n, w1.size(1)}, g.options());
-  XCALL(xeq_mlp2_bwd((const float*)g.data_ptr(), g.size(1), n, (int)g.size(1), (const float*)pk->w2tp.data_ptr(), (const float*)pre.data_ptr(),
-                     (const float*)pk->w1tp.data_ptr(), (int)w1.size(1), (float*)g_x.data_ptr(), w1.size(1), cur_stream()));
+  if (w1.size(0) == MLP_H)
+    XCALL(xeq_mlp2_bwd((const float*)g.data_ptr(), g.size(1), n, (int)g.size(1), (const float*)pk->w2tp.data_ptr(), (const float*)pre.data_ptr(),
+                       (const float*)pk->w1tp.data_ptr(), (int)w1.size(1), (float*)g_x.data_ptr(), w1.size(1), cur_stream()));
+  else
+    XCALL(xeq_mlp2h_bwd(XEQ_F32, (const float*)g.data_ptr(), g.size(1), n, (int)g.size(1), (int)w1.size(0), (const float*)pk->w2tp.data_ptr(),
+                        (const float*)pre.data_ptr(), (const float*)pk->w1tp.data_ptr(), (int)w1.size(1), (float*)g_x.data_ptr(), w1.size(1),
+                        cur_stream()));
   return g_x;
 }
 
@@ -234,7 +244,7 @@ void mlp_and_linear_fwd(const Tensor& x, const Tensor& w1, const Tensor& b1, con
                         Tensor& pre, Tensor& y, Tensor& ip) {
   const MlpPacks* pk = (x.stride(1) == 1 && x.stride(0) % 4 == 0) ? mlp_packs(w1, b1, w2, b2) : nullptr;
   const LinPack* lp = (p.dim() == 2 && p.stride(1) == 1 && p.stride(0) % 4 == 0) ? lin_pack(wl, Tensor()) : nullptr;
-  if (!pk || !lp) {
+  if (!pk || !lp || w1.size(0) != MLP_H) {   // (another hidden width: always the two launches, the MLP's first)
     mlp_fwd(x, w1, b1, w2, b2, pre, y);
     ip = linear_fwd(p, wl, Tensor());
     return;
@@ -252,9 +262,9 @@ void mlp_and_linear_bwd(const Tensor& g_y, const Tensor& pre, const Tensor& w1, 
                         const Tensor& g_lin_in, const Tensor& wl, Tensor& g_x, Tensor& g_p) {
   const MlpPacks* pk = mlp_packs(w1, b1, w2, b2);
   const LinPack* lp = lin_pack(wl, Tensor());
-  if (!pk || !lp || !lp->bwd.defined()) {
-    g_p = linear_bwd(g_lin_in, wl, Tensor());
+  if (!pk || !lp || !lp->bwd.defined() || w1.size(0) != MLP_H) {
     g_x = mlp_bwd(g_y, pre, w1, b1, w2, b2);
+    g_p = linear_bwd(g_lin_in, wl, Tensor());
     return;
   }
   const Tensor g = g_y.contiguous(), gl = g_lin_in.contiguous();

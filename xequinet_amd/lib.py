@@ -167,6 +167,9 @@ _PROTOS = {
     "xeq_mlp_pack": [_P, _P, c_int, c_int, c_int, _P, _P],
     "xeq_mlp2_fwd": [_P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, c_int64, _P],
     "xeq_mlp2_bwd": [_P, c_int64, c_int64, c_int, _P, _P, _P, c_int, _P, c_int64, _P],
+    "xeq_mlp2h_supported": [c_int, c_int, c_int, c_int],
+    "xeq_mlp2h_fwd": [c_int, _P, c_int64, c_int64, c_int, c_int, _P, _P, c_int, _P, _P, c_int64, _P],
+    "xeq_mlp2h_bwd": [c_int, _P, c_int64, c_int64, c_int, c_int, _P, _P, _P, c_int, _P, c_int64, _P],
     "xeq_mlp2_and_linear": [c_int, _P, c_int64, c_int64, c_int, _P, _P, c_int, _P, _P, c_int64, _P, c_int64, c_int, _P, c_int, _P, c_int64, _P],
     "xeq_pack_epoch": [],
     "xeq_pack_epoch_bump": [],

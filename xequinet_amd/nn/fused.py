@@ -71,14 +71,18 @@ def _silu_bwd(g, pre, act):
     return out
 
 
+MLP_H = 128   # the hidden width of xeq_mlp2_fwd / _bwd / xeq_mlp2_and_linear; the other widths take xeq_mlp2h_fwd / _bwd
+
+
 def _mlp_packs(seq: torch.nn.Sequential):
-    """Matrix-core fragment-order copies of a Linear-SiLU-Linear stack for ``xeq_mlp2_fwd / _bwd`` (forward pair with the
-    biases folded in, transposed pair for the input gradients), cached on the module and refreshed when a weight changes.
+    """Matrix-core fragment-order copies of a Linear-SiLU-Linear stack for ``xeq_mlp2_fwd / _bwd`` (hidden width 128) and
+    ``xeq_mlp2h_fwd / _bwd`` (32 .. 256): forward pair with the biases folded in, transposed pair for the input gradients, cached on
+    the module and refreshed when a weight changes.
     None when the kernels do not take the stack (other activation, f64, widths): the caller then runs the library GEMMs."""
     lin1, act, lin2 = seq[0], seq[1], seq[2]
     w1, w2 = lin1.weight, lin2.weight
     if not (isinstance(act, torch.nn.SiLU) and w1.dtype == torch.float32 and lin1.bias is not None and lin2.bias is not None
-            and lib.load().xeq_mlp2_supported(lib.XEQ_F32, w1.shape[1], w1.shape[0], w2.shape[0])):
+            and lib.load().xeq_mlp2h_supported(lib.XEQ_F32, w1.shape[1], w1.shape[0], w2.shape[0])):
         return None
 
     def pack(w, bias, n_out, k_in, transposed):
@@ -107,7 +111,11 @@ def _mlp_fwd(seq, x):
     n2 = lin2.weight.shape[0]
     pre = torch.empty((n, lin1.weight.shape[0]), dtype=x.dtype, device=x.device)
     y = torch.empty((n, n2), dtype=x.dtype, device=x.device)
-    call("xeq_mlp2_fwd", ptr(x), x.stride(0), n, k1, ptr(packs[0]), ptr(packs[1]), n2, ptr(pre), ptr(y), n2, stream())
+    h = lin1.weight.shape[0]
+    if h == MLP_H:
+        call("xeq_mlp2_fwd", ptr(x), x.stride(0), n, k1, ptr(packs[0]), ptr(packs[1]), n2, ptr(pre), ptr(y), n2, stream())
+    else:
+        call("xeq_mlp2h_fwd", lib.XEQ_F32, ptr(x), x.stride(0), n, k1, h, ptr(packs[0]), ptr(packs[1]), n2, ptr(pre), ptr(y), n2, stream())
     return pre, y
 
 
@@ -121,7 +129,11 @@ def _mlp_bwd(seq, g_y, pre):
     n, n2 = g_y.shape
     k1 = lin1.weight.shape[1]
     g_x = torch.empty((n, k1), dtype=g_y.dtype, device=g_y.device)
-    call("xeq_mlp2_bwd", ptr(g_y), n2, n, n2, ptr(packs[2]), ptr(pre), ptr(packs[3]), k1, ptr(g_x), k1, stream())
+    h = lin1.weight.shape[0]
+    if h == MLP_H:
+        call("xeq_mlp2_bwd", ptr(g_y), n2, n, n2, ptr(packs[2]), ptr(pre), ptr(packs[3]), k1, ptr(g_x), k1, stream())
+    else:
+        call("xeq_mlp2h_bwd", lib.XEQ_F32, ptr(g_y), n2, n, n2, h, ptr(packs[2]), ptr(pre), ptr(packs[3]), k1, ptr(g_x), k1, stream())
     return g_x
 
 
@@ -251,10 +263,11 @@ def linear_module_bwd(lin: torch.nn.Linear, g: torch.Tensor) -> torch.Tensor:
 
 def mlp_and_linear_fwd(seq, x, lin: torch.nn.Linear, p: torch.Tensor):
     """(pre, y) of Linear-SiLU-Linear on rows of x and lin(p), two INDEPENDENT products of XPainnUpdate.forward (nn/xpainn.py:219-223),
-    through ``xeq_mlp2_and_linear``: one launch for MD-sized systems, the two launches otherwise -- the same bits either way."""
+    through ``xeq_mlp2_and_linear``: one launch for MD-sized systems, the two launches otherwise -- the same bits either way.
+    (A hidden width other than 128: always the two launches, the MLP's first.)"""
     packs = _mlp_packs(seq) if x.is_cuda and x.stride(1) == 1 and x.stride(0) % 4 == 0 else None
     lpack = _linear_pack(lin, lin.weight, lin.bias, False) if (lin.bias is None and p.is_cuda and p.dim() == 2 and p.stride(1) == 1 and p.stride(0) % 4 == 0) else None
-    if packs is None or lpack is None:
+    if packs is None or lpack is None or seq[0].weight.shape[0] != MLP_H:
         pre, y = _mlp_fwd(seq, x)
         return pre, y, linear_module_fwd(lin, p)
     n, k1 = x.shape
@@ -272,7 +285,7 @@ def mlp_and_linear_bwd(seq, g_y, pre, lin: torch.nn.Linear, g_lin: torch.Tensor)
     packs = _mlp_packs(seq) if g_y.is_cuda else None
     g_lin = g_lin.contiguous()
     lpack = _linear_pack(lin, lin.weight, None, True) if g_lin.is_cuda else None
-    if packs is None or lpack is None:
+    if packs is None or lpack is None or seq[0].weight.shape[0] != MLP_H:
         return _mlp_bwd(seq, g_y, pre), linear_module_bwd(lin, g_lin)
     g_y = g_y.contiguous()
     n, n2 = g_y.shape

@@ -115,7 +115,7 @@ def native_supported(model_or_block: nn.Module, dtype=torch.float32) -> bool:
             seq = m.scalar_mlp if isinstance(m, PainnMessage) else m.update_mlp
             nb = m.num_basis if isinstance(m, PainnMessage) else 1
             if not (dtype == torch.float32 and isinstance(seq[1], nn.SiLU) and L.xeq_painn_supported(lib.XEQ_F32, m.node_dim, nb)
-                    and L.xeq_mlp2_supported(lib.XEQ_F32, seq[0].weight.shape[1], seq[0].weight.shape[0], seq[2].weight.shape[0])):
+                    and L.xeq_mlp2h_supported(lib.XEQ_F32, seq[0].weight.shape[1], seq[0].weight.shape[0], seq[2].weight.shape[0])):
                 return False
     return True
 
