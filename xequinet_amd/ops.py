@@ -268,10 +268,11 @@ def _use_cell_list(n_atoms: int, n_graphs: int) -> bool:
     return n_atoms >= _CELL_LIST_MIN_ATOMS * max(1, n_graphs)
 
 
-def _radius_graph_cell_list(pos, ptr_, cutoff):
-    """Open-boundary neighbour list through a per-graph bin grid (xeq_radius_graph_*_cl): O(N) instead of O(n_g^2)."""
+def _box_grid(pos, ptr_, cutoff):
+    """The bin grid of the open-boundary cell list, per graph: (lo [G, 3], bins [G, 3] int32, inverse bin width [G, 3]) over the
+    bounding box, bin width >= cutoff."""
     N, G = pos.shape[0], ptr_.numel() - 1
-    dev, dt = pos.device, dtype_code(pos)
+    dev = pos.device
     counts = ptr_[1:] - ptr_[:-1]
     gidx = torch.repeat_interleave(torch.arange(G, device=dev), counts, output_size=N).unsqueeze(1).expand(N, 3)
     lo = torch.full((G, 3), float("inf"), dtype=pos.dtype, device=dev).scatter_reduce_(0, gidx, pos, "amin", include_self=True)
@@ -280,11 +281,18 @@ def _radius_graph_cell_list(pos, ptr_, cutoff):
     lo = lo.nan_to_num_(nan=0.0, posinf=0.0, neginf=0.0)
     nb = torch.floor(ext / (cutoff * (1.0 + 1e-4))).clamp_(1, _CELL_LIST_MAX_BINS).to(torch.int32)   # bin width >= cutoff
     inv_w = (nb.to(pos.dtype) / ext.clamp(min=1e-30)).contiguous()
+    return lo.contiguous(), nb.contiguous(), inv_w
+
+
+def _radius_graph_cell_list(pos, ptr_, cutoff):
+    """Open-boundary neighbour list through a per-graph bin grid (xeq_radius_graph_*_cl): O(N) instead of O(n_g^2)."""
+    N, G = pos.shape[0], ptr_.numel() - 1
+    dev, dt = pos.device, dtype_code(pos)
+    lo, nb, inv_w = _box_grid(pos, ptr_, cutoff)
     bin_base = torch.zeros(G + 1, dtype=torch.int32, device=dev)
     bin_base[1:] = torch.cumsum(nb.prod(dim=1), 0)
     n_bins = int(bin_base[-1].item())
     keys_ = torch.empty(N, dtype=torch.int64, device=dev)
-    lo, nb = lo.contiguous(), nb.contiguous()
     call("xeq_radius_graph_bin_ids", dt, ptr(pos), ptr(ptr_), G, N, ptr(lo), ptr(inv_w), ptr(nb), ptr(bin_base), ptr(keys_), stream())
     bin_start, bin_atom = csr_by_key(keys_, n_bins)
     deg = torch.empty(N, dtype=torch.int32, device=dev)
