@@ -891,6 +891,42 @@ int xeq_head_polar_nodes(const void* s, int64_t lds, const void* x, int64_t ldx,
 int xeq_head_graph_reduce(int mode, void* src, int64_t ld, int width, const int64_t* ptr, int64_t n_graphs, const void* total, void* out,
                           void* iso, void* stream);
 
+/* Ewald message passing (nn/ewald.py:141-212 EwaldBlock behind the geometry of :60-138), f32 inference with an explicit reverse pass,
+ * csrc/xeq_ewald.hip.  Atom n of graph g (ptr [G + 1], ptr[0] = 0, ptr[G] = n) at pos [n, 3]; kvec [G, K, 3] with kvec_gstride floats
+ * between two graphs' tables (0: one [K, 3] table for every graph); theta_nk = <kvec[g, k], pos_n>, computed in the kernels in f32 with
+ * the accurate sincosf; damp [n] the per-atom damping d_n (NULL: 1).  Every contraction runs on the exact-f32 matrix instruction.  No
+ * float atomics: a graph is cut into chunks of xeq_ewald_chunk() atoms counted from its first atom and the chunk partials are added in
+ * chunk order, so a graph's results are bit-identical alone, inside any batch, in a shard and on repeat.  K is padded to the tile
+ * inside the kernels; empty graphs give zeros.
+ * xeq_ewald_supported (1 / 0, not a status): f32; node_dim a multiple of 32, <= 256; 1 <= n_k <= 192.
+ * xeq_ewald_structure_factor: s_r[g, k, f] = sum_{n in g} d_n cos(theta_nk) x[n, f], s_i with sin ([G, K, node_dim], every entry
+ *   written).  x [n, ldx] (ldx a multiple of 4, 16-byte aligned); parts: workspace of xeq_ewald_parts_floats(n, G, n_k, node_dim) floats
+ *   (0 when no graph can exceed one chunk: parts may be NULL).
+ * xeq_ewald_apply: out[n, f] = d_n sum_k kf[k, f] (cos(theta_nk) s_r[g, k, f] + sin(theta_nk) s_i[g, k, f]); kf [n_k, node_dim], out
+ *   [n, ldo].  The operator x -> out of the two entries in sequence is symmetric: applied to dL/dout it gives dL/dx.
+ * xeq_ewald_phase_grad: with (s_r, s_i) the structure factors of h and (p_r, p_i) those of gm = dL/dout,
+ *   T1[n, k] = sum_f kf[k, f] (gm[n, f] s_r[g, k, f] + h[n, f] p_r[g, k, f]), T2 with the imaginary parts,
+ *   g_theta[n, k] = d_n (-sin T1 + cos T2) ([n, n_k], optional), g_damp[n] = sum_k (cos T1 + sin T2) (optional),
+ *   g_pos[n, :] = sum_k g_theta[n, k] kvec[g, k, :] + g_damp[n] ddamp[n, :] (ddamp [n, 3] = dd_n / dpos_n, NULL: no such term).
+ *   dL/dkf and dL/dkvec are not formed (inference).
+ * Row kernels of the block's glue: xeq_ewald_damping: damp[n] = prod_i sinc(scale pos[n, i] + eps) (torch.sinc) and ddamp [n, 3]
+ * (optional); xeq_ewald_layernorm_fwd / _bwd: LayerNorm over node_dim (<= 256) on contiguous rows, stats [n, 2] = (mean, rstd);
+ * xeq_ewald_combine: out = (sa a + sb b) [* silu'(pre)] over `count` floats (b, pre optional). */
+int xeq_ewald_supported(int dtype, int node_dim, int n_k);
+int64_t xeq_ewald_chunk(void);
+int64_t xeq_ewald_parts_floats(int64_t n, int64_t n_graphs, int n_k, int node_dim);
+int xeq_ewald_structure_factor(const void* x, int64_t ldx, int64_t n, int node_dim, const void* pos, const void* kvec, int64_t kvec_gstride, int n_k,
+                               const void* damp, const int64_t* ptr, int64_t n_graphs, void* parts, void* s_r, void* s_i, void* stream);
+int xeq_ewald_apply(const void* s_r, const void* s_i, const void* kf, int64_t n, int node_dim, const void* pos, const void* kvec, int64_t kvec_gstride,
+                    int n_k, const void* damp, const int64_t* ptr, int64_t n_graphs, void* out, int64_t ldo, void* stream);
+int xeq_ewald_phase_grad(const void* gm, int64_t ldg, const void* h, int64_t ldh, const void* s_r, const void* s_i, const void* p_r, const void* p_i,
+                         const void* kf, int64_t n, int node_dim, const void* pos, const void* kvec, int64_t kvec_gstride, int n_k, const void* damp,
+                         const void* ddamp, const int64_t* ptr, int64_t n_graphs, void* g_theta, void* g_damp, void* g_pos, void* stream);
+int xeq_ewald_damping(const void* pos, int64_t n, double scale, double eps, void* damp, void* ddamp, void* stream);
+int xeq_ewald_layernorm_fwd(const void* x, int64_t n, int node_dim, const void* weight, const void* bias, double eps, void* y, void* stats, void* stream);
+int xeq_ewald_layernorm_bwd(const void* g, const void* x, const void* stats, const void* weight, int64_t n, int node_dim, void* g_x, void* stream);
+int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const void* pre, int64_t count, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libxeq_hip.so")
-SOURCES = ["xeq_graph.hip", "xeq_ops.hip", "xeq_message.hip", "xeq_message_sb.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.hip", "xeq_node.hip", "xeq_mlp.hip", "xeq_linear.hip", "xeq_update.hip", "xeq_nodeblock.hip", "xeq_tp.hip", "xeq_train.hip", "xeq_train_node.hip", "xeq_electronic.hip", "xeq_painn.hip", "xeq_heads.hip"]
+SOURCES = ["xeq_graph.hip", "xeq_ops.hip", "xeq_message.hip", "xeq_message_sb.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.hip", "xeq_node.hip", "xeq_mlp.hip", "xeq_linear.hip", "xeq_update.hip", "xeq_nodeblock.hip", "xeq_tp.hip", "xeq_train.hip", "xeq_train_node.hip", "xeq_electronic.hip", "xeq_painn.hip", "xeq_heads.hip", "xeq_ewald.hip"]
 HEADERS = ["xeq_common.h", "xeq_linear_s.h", os.path.join("..", "..", "include", "xeq.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # per-source extras.  The matrix-core message kernels: LLVM's max-ILP machine scheduler instead of the default (measured in round 1 on
@@ -25,7 +25,7 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=f
 # profiles/r05_no_packed.txt), so every object with v_mfma in it is built without them and `check_no_packed` fails the build if the
 # flag is ever dropped by a toolchain update.
 NO_PACKED = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-MFMA_SOURCES = ["xeq_nodeblock.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.hip", "xeq_update.hip", "xeq_mlp.hip", "xeq_linear.hip", "xeq_train.hip", "xeq_electronic.hip", "xeq_painn.hip", "xeq_heads.hip"]
+MFMA_SOURCES = ["xeq_nodeblock.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.hip", "xeq_update.hip", "xeq_mlp.hip", "xeq_linear.hip", "xeq_train.hip", "xeq_electronic.hip", "xeq_painn.hip", "xeq_heads.hip", "xeq_ewald.hip"]
 EXTRA_FLAGS = {"xeq_nodeblock.hip": [],
                # wq: explicit fma chains only (its window / global instantiations must round alike)
                "xeq_message_wq.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"],

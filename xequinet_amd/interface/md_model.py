@@ -322,6 +322,9 @@ def resolve_jit_model(mode: str = "lmp", unit_style: str = "metal", net_charge: 
     """jit_model.py:219-236; the dipole head is outside the energy+force path.  ``model_name`` ("xpainn" or "painn", what a
     checkpoint's config carries) picks the model class behind the front."""
     fronts = {"xpainn": {"lmp": XPaiNNLMP, "gmx": XPaiNNGMX}, "painn": {"lmp": PaiNNLMP, "gmx": PaiNNGMX}}
+    if model_name.lower() == "xpainn-ewald":   # the MD fronts walk the energy chain of XPaiNN alone (nn/output.py::refuse_ewald)
+        raise ValueError("resolve_jit_model: an XPaiNNEwald model (\"xpainn-ewald\") is refused, the MD fronts would skip its Ewald "
+                         "modules; evaluate it with the eager model")
     if model_name.lower() not in fronts:
         raise NotImplementedError(f"Unsupported model {model_name}")
     factory = fronts[model_name.lower()]

@@ -89,6 +89,9 @@ class XPaiNNNative(nn.Module):
 
     def __init__(self, model) -> None:
         super().__init__()
+        from ..nn.output import refuse_ewald
+
+        refuse_ewald(model, "XPaiNNNative (xeq::xpainn_eval)")   # before the operator library is loaded: the refusal needs no GPU
         load_torch_library()
         from ..nn.model import PaiNN, XPaiNN
 

@@ -26,6 +26,10 @@ ENVELOPE_FUNCTION: Final[str] = "envelope_function"
 SPHERICAL_HARMONICS: Final[str] = "spherical_harmonics"
 NODE_INVARIANT: Final[str] = "node_invariant"
 NODE_EQUIVARIANT: Final[str] = "node_equivariant"
+# Ewald message passing (keys.py:29-31 of the reference)
+K_DOT_R: Final[str] = "k_dot_r"
+SINC_DAMPING: Final[str] = "sinc_damping"
+DOWN_PROJECTION: Final[str] = "down_projection"
 
 # properties
 ATOMIC_ENERGIES: Final[str] = "atomic_energies"

@@ -206,11 +206,21 @@ _PROTOS = {
     "xeq_head_polar_nodes": [_P, c_int64, _P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P,
                              c_double, _P, _P],
     "xeq_head_graph_reduce": [c_int, _P, c_int64, c_int, _P, c_int64, _P, _P, _P, _P],
+    "xeq_ewald_supported": [c_int, c_int, c_int],
+    "xeq_ewald_chunk": [],
+    "xeq_ewald_parts_floats": [c_int64, c_int64, c_int, c_int],
+    "xeq_ewald_structure_factor": [_P, c_int64, c_int64, c_int, _P, _P, c_int64, c_int, _P, _P, c_int64, _P, _P, _P, _P],
+    "xeq_ewald_apply": [_P, _P, _P, c_int64, c_int, _P, _P, c_int64, c_int, _P, _P, c_int64, _P, c_int64, _P],
+    "xeq_ewald_phase_grad": [_P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P, c_int64, c_int, _P, _P, _P, c_int64, _P, _P, _P, _P],
+    "xeq_ewald_damping": [_P, c_int64, c_double, c_double, _P, _P, _P],
+    "xeq_ewald_layernorm_fwd": [_P, c_int64, c_int, _P, _P, c_double, _P, _P, _P],
+    "xeq_ewald_layernorm_bwd": [_P, _P, _P, _P, c_int64, c_int, _P, _P],
+    "xeq_ewald_combine": [_P, c_double, _P, c_double, _P, c_int64, _P, _P],
 }
 # entry points that return a size, not a status
 _RET_I64 = {"xeq_launch_count", "xeq_launch_names", "xeq_message_wq_packed_weight_floats", "xeq_rowptr_from_degrees_max", "xeq_csr_by_key_workspace", "xeq_message_wq_pcap", "xeq_message_wq_plan_workspace", "xeq_message_wq_win_ints",
             "xeq_message_wq_parts_floats", "xeq_mlp_packed_floats", "xeq_exclusive_scan_i32_workspace", "xeq_node_block_fwd_tiles", "xeq_node_block_bwd_tiles", "xeq_node_block_rows", "xeq_pack_epoch", "xeq_tensor_product_wgrad_chunks", "xeq_small_rows_limit", "xeq_painn_few_rows_limit",
-            "xeq_painn_filter_packed_floats", "xeq_painn_uv_packed_floats"}
+            "xeq_painn_filter_packed_floats", "xeq_painn_uv_packed_floats", "xeq_ewald_chunk", "xeq_ewald_parts_floats"}
 EXPORTS = ["xeq_version", "xeq_last_error", *_PROTOS]
 
 _lib: Optional[ctypes.CDLL] = None

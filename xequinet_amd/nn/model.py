@@ -1,6 +1,6 @@
 """Model assembly -- mirror of ``xequinet/nn/model.py`` for the XPaiNN energy path:
 ``BaseModel.forward(data, compute_forces, compute_virial)`` (nn/model.py:26-46),
-``XPaiNN`` (:49-122), ``resolve_model`` (:310-318), ``load_model`` (:321-351)."""
+``XPaiNN`` (:49-122), ``XPaiNNEwald`` (:125-176), ``PaiNN`` (:261-307), ``resolve_model`` (:310-318), ``load_model`` (:321-351)."""
 from __future__ import annotations
 
 from typing import Dict, Iterable, List, Optional, Union
@@ -140,6 +140,59 @@ class XPaiNN(BaseModel):
             self.mods[f"update_{action_blocks - 1}"].equivariant_output_unused = True
 
 
+class XPaiNNEwald(XPaiNN):
+    """XPaiNN with Ewald message passing (nn/model.py:125-176): behind every XPaiNN module, the output heads included, come
+    ``ewald_initial``, ``ewald_0`` ... and a second set of heads ``ewald_output_<mode>``; the second energy head adds to the atomic
+    energies of the first.  The eager model evaluates it (nn/ewald.py: kernels in f32 inference, the tensor form otherwise); the
+    fronts that evaluate the energy chain alone refuse it (nn/output.py::refuse_ewald)."""
+
+    def __init__(self, **kwargs) -> None:
+        super().__init__(**kwargs)
+        from .ewald import EwaldBlock, EwaldInitialNonPBC, EwaldInitialPBC
+
+        node_dim: int = kwargs.get("node_dim", 128)
+        activation: str = kwargs.get("activation", "silu")
+        layer_norm: bool = kwargs.get("layer_norm", True)
+        use_pbc: bool = kwargs.get("use_pbc", True)
+        projection_dim: int = kwargs.get("projection_dim", 8)
+        ewald_blocks: int = kwargs.get("ewald_blocks", 1)
+        ewald_output_modes: Union[str, List[str]] = kwargs.get("ewald_output_mode", ["energy"])
+
+        if use_pbc:
+            num_k_points: List[int] = kwargs.get("num_k_points", [3, 3, 3])
+            ewald_initial = EwaldInitialPBC(num_k_points=num_k_points, projection_dim=projection_dim)
+        else:
+            ewald_initial = EwaldInitialNonPBC(
+                k_cutoff=kwargs.get("k_cutoff", 0.4), delta_k=kwargs.get("delta_k", 0.2), num_k_basis=kwargs.get("num_k_basis", 20),
+                k_offset=kwargs.get("k_offset", None), projection_dim=projection_dim,
+            )
+        self.mods["ewald_initial"] = ewald_initial
+        for i in range(ewald_blocks):
+            self.mods[f"ewald_{i}"] = EwaldBlock(node_dim=node_dim, projection_dim=projection_dim, activation=activation, layer_norm=layer_norm)
+        # the kernel form is all blocks or none: the initial module writes either the kernel geometry or the tensor form's tensors
+        ewald_initial.kernel_consumers = all(self.mods[f"ewald_{i}"].kernel_shape_ok() for i in range(ewald_blocks))
+        from .ewald import KERNEL_MAX_K
+
+        n_k = (ewald_initial.k_index_product_set if use_pbc else ewald_initial.k_grid).shape[0]
+        if n_k > KERNEL_MAX_K:   # say so once, here: the tensor form materialises the reference's [n_atoms, K, node_dim] tensors
+            import warnings
+
+            ewald_initial.kernel_consumers = False
+            warnings.warn(f"XPaiNNEwald: {n_k} k-points exceed the Ewald kernels' cap of {KERNEL_MAX_K}; every evaluation takes the tensor form, "
+                          f"which forms several [n_atoms, {n_k}, {node_dim}] tensors per block", stacklevel=2)
+        if ewald_output_modes is None:
+            ewald_output_modes = ["energy"]
+        elif isinstance(ewald_output_modes, str) or not isinstance(ewald_output_modes, Iterable):   # a plain string is one mode
+            ewald_output_modes = [ewald_output_modes]
+        for mode in ewald_output_modes:
+            output = resolve_output(mode, **kwargs)
+            self.mods[f"ewald_output_{mode}"] = output
+            self.extra_properties.extend(output.extra_properties)
+        action_blocks: int = kwargs.get("action_blocks", 3)
+        if action_blocks > 0 and any(getattr(self.mods[f"ewald_output_{m}"], "reads_equivariant", False) for m in ewald_output_modes):
+            self.mods[f"update_{action_blocks - 1}"].equivariant_output_unused = False
+
+
 class PaiNN(BaseModel):
     """PaiNN (nn/model.py:261-307): Embedding, action_blocks x (PainnMessage, PainnUpdate), the output heads.
 
@@ -228,7 +281,7 @@ class PaiNN(BaseModel):
 
 
 def resolve_model(model_name: str, **kwargs) -> BaseModel:
-    models_factory = {"xpainn": XPaiNN, "painn": PaiNN}
+    models_factory = {"xpainn": XPaiNN, "xpainn-ewald": XPaiNNEwald, "painn": PaiNN}
     if model_name.lower() not in models_factory:
         raise NotImplementedError(f"Unsupported model {model_name}")
     return models_factory[model_name.lower()](**kwargs)

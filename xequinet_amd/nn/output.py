@@ -6,7 +6,8 @@ The three property heads follow the dispatch of nn/electronic.py: inference in f
 the scalar and charge MLPs, csrc/xeq_heads.hip for PolarOut's node pass and for every per-graph reduction: no atomics, a graph's
 result is bit-identical alone, in a batch and in a shard); a training pass, f64 and widths / activations without a kernel run the
 reference's op sequence on differentiable device tensor operations.  The kernel form has no reverse pass: in inference only the
-energy is differentiated and these heads do not feed it.  ``dipole``, ``spatial`` and ``cartesian`` are not built."""
+energy is differentiated and these heads do not feed it.  ``dipole``, ``spatial`` and ``cartesian`` are not built.
+The second set of heads of XPaiNNEwald (``ewald_output_<mode>``, nn/model.py) is built by the same factory."""
 from __future__ import annotations
 
 import math
@@ -380,6 +381,22 @@ def refuse_extra_heads(model, who: str) -> None:
         if extra:
             raise ValueError(f"{who} evaluates the energy output head alone: a model with another output head ({', '.join(extra)}) is "
                              "refused (use GraphedModel or the eager model)")
+    refuse_ewald(model, who)
+
+
+def refuse_ewald(model, who: str) -> None:
+    """The same fronts walk the energy chain embedding - message / update blocks - energy head themselves: they would skip the
+    Ewald modules of an XPaiNNEwald and return the short-range energy alone, so that model is refused there (the eager model
+    evaluates it)."""
+    m = model
+    while not isinstance(m, nn.Module) and hasattr(m, "model"):
+        m = m.model
+    if isinstance(m, nn.Module):
+        from .ewald import EwaldBlock, _EwaldInitial
+
+        if any(isinstance(x, (EwaldBlock, _EwaldInitial)) for x in m.modules()):
+            raise ValueError(f"{who} evaluates the energy chain of XPaiNN alone: an XPaiNNEwald model (\"xpainn-ewald\", "
+                             f"{type(m).__name__} with Ewald modules) is refused; evaluate it with the eager model")
 
 
 _NOT_BUILT = {

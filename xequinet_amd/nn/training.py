@@ -47,10 +47,12 @@ def native_pass_supported(model: torch.nn.Module) -> bool:
     # (the parameter-gradient kernels of the radial filter take the Bessel and Gaussian bases: xeq_message_param_grad)
     # (the charge / spin embeddings have no parameter-gradient kernels: a model with one takes the differentiable form)
     # (nor have the property heads: ScalarOut, AtomicChargesOut, PolarOut -- nn/output.py)
+    # (nor have the Ewald modules: nn/ewald.py)
     from .electronic import ChargeEmbedding, SpinEmbedding
+    from .ewald import EwaldBlock, _EwaldInitial
     from .output import EnergyOut, OutputModule
 
-    return (all(getattr(m, "fused", True) for m in model.modules())
+    return (not any(isinstance(m, (EwaldBlock, _EwaldInitial)) for m in model.modules()) and all(getattr(m, "fused", True) for m in model.modules())
             and not any(isinstance(m, OutputModule) and not isinstance(m, EnergyOut) for m in model.modules())
             and not any(isinstance(m, (ChargeEmbedding, SpinEmbedding)) for m in model.modules())
             and all(getattr(m, "kind", "bessel") in ("bessel", "gaussian") for m in model.modules() if hasattr(m, "params") and hasattr(m, "num_basis")))

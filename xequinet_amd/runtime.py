@@ -73,6 +73,9 @@ class GraphedModel:
         (``tuning.enable_gemm_autotune``; PyTorch TunableOp, a process-wide switch).  The libraries' default picks
         for few-hundred-row operands are tiles of 128-256 rows on one or two workgroups (35 us per GEMM at 192
         atoms); the timed picks take ~5 us, which halves the replay time of MD-sized systems."""
+        from .nn.output import refuse_ewald
+
+        refuse_ewald(model, "GraphedModel")   # the k-vector table and the per-graph chunk walk are not captured here (DESIGN.md section 8)
         self.model = model
         self.tune_gemms = tune_gemms
         # MD engines hand over a neighbour list every step that is, for small systems, the same list for many steps (every atom
