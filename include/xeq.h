@@ -262,7 +262,8 @@ int xeq_scatter_add(int dtype, const void* src, const int64_t* index, int64_t n,
  * 128-139: s = Linear(table[Z]), x = 0), so they are evaluated once per table row (rows_s [Zmax + 1, node_dim], rows_h [., hidden_dim],
  * rows_x0 [., node_dim]) and gathered by atomic number: s_out [n, node_dim], h_out [n, hidden_dim], xhat_out [n * irreps_dim] in BT
  * layout with every l > 0 block zero.  z: int32 or int64 atomic numbers; one outside [0, n_rows) reads row 0.  Replaces three ATen
- * gathers and a fill. */
+ * gathers and a fill.  hidden_dim == 0 / irreps_dim == 0: h_out / xhat_out are not written (the table form of the wq message kernels,
+ * xeq_message_fwd_wq_table below, reads the table rows themselves: only s is gathered per node). */
 int xeq_first_block_front(const void* z, int z_is_int64, int64_t n, int64_t n_rows, const void* rows_s, const void* rows_h, const void* rows_x0,
                           int node_dim, int hidden_dim, int64_t irreps_dim, void* s_out, void* h_out, void* xhat_out, void* stream);
 
@@ -617,6 +618,37 @@ int xeq_message_bwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int
                        const void* dbasis, const void* h, const void* xhat, const void* grad_s, const void* grad_x,
                        const void* w_rbf, const void* b_rbf, int num_basis, int node_dim, const int32_t mul[3], void* grad_h,
                        void* grad_xhat, void* parts, int xhat_layout, void* stream);
+/* TABLE FORM of the model's first message block.  Behind XEmbedding a node's h = scalar_mlp(norm(s)) and the 0e block of its xhat are
+ * functions of its element alone: rows of the element table that xeq_first_block_front gathers from (h_table [T, H], xhat0_table
+ * [T, F]; row = atomic number, a number outside the table reads row 0).  The _table entries read those rows instead of the per-node
+ * copies, with the results of xeq_message_fwd_wq / _bwd_wq under XEQ_XHAT_HIGHER_L_ZERO bit for bit:
+ *   xeq_edge_basis_wq_table: xeq_edge_basis_wq, whose launch also writes the table rows the message kernels index by -- slot_rows[P]:
+ *     row of the node every padded slot gathers from; quad_rows[P / 4]: row of every quad's owner (pgath, qinfo: the plan's; z: the
+ *     atomic numbers [N], int32 or int64).  Sequential loads next to the plan's arrays: no load through the node id inside a tile.
+ *   xeq_message_fwd_wq_table: every workgroup copies its unit's columns of the whole table into LDS once; a gathered row is an LDS read
+ *     at the slot's table row: no window, no staging and no barrier per step.  slot_rows takes pgath's place.
+ *   xeq_message_bwd_wq_table: the first block of a force evaluation (no node gradients: only `parts`); the owners' rows are read from the
+ *     table -- the few cache-resident rows of the species present -- at quad_rows; the gradient window is per node and stays.
+ * xhat_layout: 1 | XEQ_XHAT_HIGHER_L_ZERO (| XEQ_WQ_MIRROR_WALK | XEQ_WQ_PACKED_WEIGHTS).  T <= xeq_message_wq_table_max_rows().
+ * xeq_message_wq_first_table (host only; 1 / 0) is the ONE statement of when a front takes these entries: the block runs the wq family
+ * (family == XEQ_FAMILY_WQ), its front half comes from the element table with T rows that fit (1 <= T <= max_rows; not behind a charge /
+ * spin embedding: per_node_front), nothing wants parameter gradients (training), and XEQ_WQ_FIRST_TABLE is not "0". */
+int xeq_message_wq_table_max_rows(void);
+int xeq_message_wq_first_table(int family, int64_t table_rows, int training, int per_node_front);
+int xeq_edge_basis_wq_table(const void* vec, int64_t n_nodes, int64_t n_edges, const int32_t* qptr, const int32_t* peid,
+                            int rbf_kind, int cutoff_kind, int num_basis, double cutoff, const void* p0, const void* p1,
+                            void* basis, void* dbasis, const int32_t* pgath, const int32_t* qinfo, const void* z, int z_is_int64,
+                            int64_t table_rows, int32_t* slot_rows, int32_t* quad_rows, void* stream);
+int xeq_message_fwd_wq_table(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                             const int32_t* c_rowptr, const int32_t* slot_rows, const int32_t* qinfo, const void* basis,
+                             const void* h_table, const void* xhat0_table, int64_t table_rows, const void* s_in, const void* x_in,
+                             const void* w_rbf, const void* b_rbf, int num_basis, int node_dim, const int32_t mul[3], void* s_out,
+                             void* x_out, int xhat_layout, void* stream);
+int xeq_message_bwd_wq_table(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                             const int32_t* n_rowptr, const int32_t* pgath, const int32_t* qinfo, const int32_t* quad_rows,
+                             const void* basis, const void* dbasis, const void* h_table, const void* xhat0_table, int64_t table_rows,
+                             const void* grad_s, const void* grad_x, const void* w_rbf, const void* b_rbf, int num_basis, int node_dim,
+                             const int32_t mul[3], void* parts, int xhat_layout, void* stream);
 int xeq_message_wq_edge_grad(const void* vec, int64_t n_nodes, int64_t n_edges, const int32_t* qptr, const int32_t* peid,
                              const int32_t* mirror, const int32_t mul[3], const void* parts, void* grad_vec, void* stream);
 /* The same for the partials of SEVERAL message blocks of one evaluation (all walked on the same plan): parts[0 .. n_sets) are summed

@@ -332,10 +332,24 @@ __device__ __forceinline__ void wq_record_piece(const float* __restrict__ vec, c
 // (the pieces are 16-48 bytes at a stride of 160: stored directly they kept the kernel at 2.6 TB/s of writes).  48.5 -> 42 us with the
 // wave-uniform kinds alone; the same values bit for bit.
 constexpr int WQ_REC_SLOTS = 32;
+struct WqTableIndex {
+  const void* z;            // [N] atomic numbers = rows of the element table (NULL: no table rows wanted)
+  int z_is_int64;
+  int64_t rows;
+  const int32_t* pgath;     // the plan's gathered node per slot / owner per quad
+  const uint32_t* qinfo;
+  int32_t* ptab;            // [P] out
+  int32_t* qtab;            // [P / 4] out
+  // (a number outside the table reads row 0, the table's all-zero padding row, as xeq_first_block_front does)
+  __device__ __forceinline__ int32_t row(int32_t node) const {
+    const int64_t v = z_is_int64 ? ((const int64_t*)z)[node] : (int64_t)((const int32_t*)z)[node];
+    return v >= 0 && v < rows ? (int32_t)v : 0;
+  }
+};
 __global__ void __launch_bounds__(256) k_wq_records(const float* __restrict__ vec, const int32_t* __restrict__ peid,
                              const int32_t* __restrict__ qptr, int64_t N, int64_t pcap, RadialSpec rs,
                              const float* __restrict__ p0, const float* __restrict__ p1, float* __restrict__ rec,
-                             float* __restrict__ drec, int recf, int tailw, int bftail) {
+                             float* __restrict__ drec, int recf, int tailw, int bftail, const WqTableIndex ti) {
   __shared__ __attribute__((aligned(16))) float stage[2][WQ_REC_SLOTS * 48];
   const int64_t limit = min(pcap, 4 * (int64_t)qptr[N]);
   const int64_t first = (int64_t)blockIdx.x * WQ_REC_SLOTS;
@@ -344,6 +358,17 @@ __global__ void __launch_bounds__(256) k_wq_records(const float* __restrict__ ve
   const int64_t p = first + slot;
   if (kind < 3 && p < limit)
     wq_record_piece(vec, peid, p, 2 * kind + (r & 1), rs, p0, p1, stage[0] + slot * recf, drec ? stage[1] + slot * recf : nullptr, tailw, bftail != 0);
+  // the fourth wave has no piece to compute: it writes the element-table rows of the first block's table form (xeq_edge_basis_wq_table),
+  // per padded slot the row of the gathered node and per quad the row of its owner, so that the message kernels find them by sequential
+  // loads next to pgath / qinfo instead of through the node id
+  if (kind == 3 && ti.z) {
+    if (r < WQ_REC_SLOTS) {
+      if (first + r < limit) ti.ptab[first + r] = ti.row(ti.pgath[first + r]);
+    } else if (r < WQ_REC_SLOTS + WQ_REC_SLOTS / 4) {
+      const int64_t q = first / 4 + (r - WQ_REC_SLOTS);
+      if (4 * q < limit) ti.qtab[q] = ti.row((int32_t)(ti.qinfo[q] & WQ_OWNER));
+    }
+  }
   __syncthreads();
   const int n4 = (int)min((int64_t)WQ_REC_SLOTS, limit - first) * recf / 4;
   const f32x4* s0 = reinterpret_cast<const f32x4*>(stage[0]);
@@ -384,6 +409,10 @@ struct WqArgs {
   int mirror;              // reverse pass over the FORWARD plan of a symmetric list: every slot stands for its mirror edge (Y_1 negated)
   int packed_w;            // w_rbf points at xeq_message_wq_pack_weights' output (XEQ_WQ_PACKED_WEIGHTS): staging is a coalesced copy
   int nu[3];               // 32-channel units per l
+  // table form of the first block (TAB below): h / xhat of a node are rows of the element table.  Forward: pgath points at the table
+  // row of every slot's gathered node; reverse: qtab holds the table row of every quad's owner
+  const int32_t* qtab;     // [Q]
+  int tab_rows;            // rows of the table (T)
 };
 
 struct WqUnit {
@@ -479,6 +508,8 @@ __device__ __forceinline__ void wq_decode(const WqArgs& a, int nunits, int& s0, 
 #define XEQ_WQ_WIN_FLOATS 12288
 #endif
 constexpr int WQ_WIN_FLOATS = XEQ_WQ_WIN_FLOATS;   // 48 KB per workgroup: two workgroups per CU
+// rows of the element table the forward table form can hold next to nothing else in the window's LDS (its l = 0 rows: 512 bytes)
+constexpr int WQ_TAB_MAX_ROWS = WQ_WIN_FLOATS * 4 / 512 < 128 ? WQ_WIN_FLOATS * 4 / 512 : 128;
 
 // rbf_lin rows of the unit as the B operands, per kind (0: gate_state, 1: gate_edge, 2: scalar message) WQ_WK<KS> floats:
 //   [split][lane][4]   bf16 packs of W[row][8 kh + j], j = 0..7 (lane: j = lane & 31 -> channel row, kh = lane >> 5); 3 x 64 x 4
@@ -592,7 +623,8 @@ __device__ __forceinline__ void wq_st(float* __restrict__ base, uint32_t byte_of
 //   [T_QOWN + c]                owner node of the quad
 //   [T_QKEEP + c]               0 where the quad starts a segment (running sums restart), else 1
 //   [T_QLAST + c]               1 where the quad ends a segment (the node's sums are stored)
-enum { T_G0 = 0, T_G1 = 32, T_Y = 64, T_QOWN = 320, T_QKEEP = 328, T_QLAST = 336, T_SIZE = 344 };
+//   [T_QTAB + c]                table form of the reverse pass: the owner's row of the element table
+enum { T_G0 = 0, T_G1 = 32, T_Y = 64, T_QOWN = 320, T_QKEEP = 328, T_QLAST = 336, T_QTAB = 344, T_SIZE = 352 };
 
 // what a lane loads for the MFMA row it owns: i = lane & 31 -> half hr = (i >> 2) & 1, register v = 4 (i >> 3) + (i & 3)
 template <int KS, int NREC, bool WITH_Y>
@@ -601,6 +633,7 @@ struct WqRow {
   f32x4 ya, yb;
   int g;
   uint32_t qi;
+  int qt;   // (QTAB only)
 };
 struct WqStreams {
   int q0, q1, q2, ntiles;
@@ -623,7 +656,7 @@ __device__ __forceinline__ void wq_load_rec(const float* __restrict__ rec, uint3
       if (s < (wq_bftail(KS) ? 4 : KS)) R.f[s] = tl[s - 4 * c];
   }
 }
-template <int KS, int NREC, bool WITH_Y>
+template <int KS, int NREC, bool WITH_Y, bool QTAB = false>
 __device__ __forceinline__ void wq_row(const WqArgs& a, const WqStreams& st, int lane, int t, const float* __restrict__ rec,
                                        const float* __restrict__ drec, WqRow<KS, NREC, WITH_Y>& w, int g_default = 0) {
   const int i = lane & 31, kh = lane >> 5, hr = (i >> 2) & 1, g = i >> 3;
@@ -637,6 +670,7 @@ __device__ __forceinline__ void wq_row(const WqArgs& a, const WqStreams& st, int
   const uint32_t qv = a.qinfo[valid ? q : 0];
   w.g = valid ? gv : g_default;
   w.qi = valid ? qv : 0u;
+  if constexpr (QTAB) w.qt = a.qtab[valid ? q : 0];   // (an invalid row's quad is never multiplied into a stored sum: any row of the table will do)
   wq_load_rec<KS>(rec, ps, kh, valid, w.R[0]);
   if constexpr (NREC > 1) wq_load_rec<KS>(drec, ps, kh, valid, w.R[1]);
   if constexpr (WITH_Y) {
@@ -651,7 +685,7 @@ __device__ __forceinline__ void wq_row(const WqArgs& a, const WqStreams& st, int
     }
   }
 }
-template <int KS, int NREC, bool WITH_Y>
+template <int KS, int NREC, bool WITH_Y, bool QTAB = false>
 __device__ __forceinline__ void wq_publish(int lane, const WqRow<KS, NREC, WITH_Y>& w, uint32_t stride0, uint32_t stride1,
                                            int* tbl, uint32_t gbase = 0u) {
   // EVERY lane writes, without a branch (round 6).  Lanes l and l + 32 hold the same row (wq_row: i = lane & 31) and the four lanes of
@@ -679,6 +713,7 @@ __device__ __forceinline__ void wq_publish(int lane, const WqRow<KS, NREC, WITH_
   tbl[T_QOWN + c] = (int)(w.qi & WQ_OWNER);
   tbl[T_QKEEP + c] = (w.qi & WQ_FIRST) ? 0 : 1;
   tbl[T_QLAST + c] = (w.qi & WQ_LAST) ? 1 : 0;
+  if constexpr (QTAB) tbl[T_QTAB + c] = w.qt;
 }
 template <typename T>
 __device__ __forceinline__ void wq_tread4(const int* tbl, int idx, T (&out)[4]) {
@@ -816,9 +851,33 @@ __device__ __forceinline__ void wq_stage_fwd(const WqArgs& a, const WqUnit& un, 
   }
 }
 
+// Table form of the first block (TAB): behind the embedding h and the 0e block of xhat are functions of the element, so what the
+// forward pass gathers per edge is one of the T rows of the element table (h_table [T, H], xhat0_table [T, F]: what
+// xeq_first_block_front gathers from).  The workgroup copies its unit's columns of the WHOLE table into the window's LDS once, behind
+// its weights, in the window's row layout -- l = 0: [gate_state | gate_edge | scalar message | xhat_0] (512 bytes per row); l > 0, where
+// xhat is zero: [gate_edge] (128 bytes) -- and every step reads it as a window that starts at row 0 and is indexed by the slot's TABLE
+// row (a.pgath points at xeq_edge_basis_wq_table's per-slot rows): no window staging, no barrier per step, and the same LDS reads
+// feeding the same arithmetic as the window form.
+constexpr int wq_tab_row_bytes(int NM) { return NM == 1 ? 512 : 128; }
+template <int NM>
+__device__ __forceinline__ void wq_stage_table_fwd(const WqArgs& a, const WqUnit& un, const float* __restrict__ h_tab,
+                                                   const float* __restrict__ x0_tab, float* win) {
+  constexpr int NP = NM == 1 ? 4 : 1;   // 128-byte pieces per row
+  const int total = a.tab_rows * NP * 8;   // 16-byte chunks
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int piece = idx >> 3, chunk = idx & 7;
+    const int row = piece / NP, sl = piece - row * NP;
+    const float* src = NM > 1 ? h_tab + (int64_t)row * a.H + a.C + un.u0
+                              : (sl < 3 ? h_tab + (int64_t)row * a.H + (sl == 0 ? un.u0 : (sl == 1 ? a.C + un.u0 : 2 * a.C + 32 * un.cb))
+                                        : x0_tab + (int64_t)row * a.F + un.u0);
+    *reinterpret_cast<f32x4*>(win + piece * 32 + 4 * chunk) = *reinterpret_cast<const f32x4*>(src + 4 * chunk);
+  }
+}
+
 //   x_c += xhat[n] (h_state[n] phi_state) + Y (h_edge[n] phi_edge);   s_c += h_msg[n] phi_msg   (l = 0)
 // WIN: the gathered rows of this step are in the LDS window (first node w0); otherwise they are read from global memory
-template <int NM, int KS, bool WIN, bool XZ, bool FENCED>
+// TAB (with WIN): the "window" is the element table (above)
+template <int NM, int KS, bool WIN, bool XZ, bool FENCED, bool TAB = false>
 __device__ __forceinline__ void wq_fwd_body(const WqArgs& a, int range, const WqUnit un, const WqCols& wc,
                                             const float* __restrict__ rec, const float* __restrict__ h,
                                             const float* __restrict__ xhat_, const float* __restrict__ s_in,
@@ -828,7 +887,9 @@ __device__ __forceinline__ void wq_fwd_body(const WqArgs& a, int range, const Wq
   constexpr bool HAS_S = NM == 1;
   constexpr bool NO_STATE = XZ && NM > 1;   // xhat = 0 on these columns: the gate_state term vanishes with its filter and gathers
   constexpr int YOFF = NM == 3 ? 0 : 3;
-  constexpr int NH = NM == 1 ? 3 : 2, ROWB = (NH + NM) * 128;
+  static_assert(!TAB || (WIN && (XZ || NM == 1)), "the table form is a window form of the first block");
+  constexpr int NH = NM == 1 ? 3 : 2, ROWB = TAB ? wq_tab_row_bytes(NM) : (NH + NM) * 128;
+  constexpr uint32_t HE_OFF = TAB && NM > 1 ? 0u : 128u;   // the gate_edge piece inside a row
   const int lane = threadIdx.x & 63, j = lane & 31, hh = lane >> 5;
   const uint32_t row_s = 4u * (uint32_t)a.F, row_x = 4u * (uint32_t)a.D;
   wq_for_isolated(a, range, lane, [&](int m) {   // s_out = s_in, x_out = x_in on the unit's columns
@@ -952,7 +1013,7 @@ __device__ __forceinline__ void wq_fwd_body(const WqArgs& a, int range, const Wq
         if constexpr (WIN) {
           const uint32_t oh = g0[v] + 4u * (uint32_t)j;
           if constexpr (!NO_STATE) hs[u] = wq_lds(win, oh);
-          he[u] = wq_lds(win, oh + 128u);
+          he[u] = wq_lds(win, oh + HE_OFF);
           if constexpr (HAS_S) hm[u] = wq_lds(win, oh + 256u);
           if constexpr (!NO_STATE) {
 #pragma unroll
@@ -1039,7 +1100,7 @@ __device__ __forceinline__ void wq_fwd_body(const WqArgs& a, int range, const Wq
 
 
 // one role of the forward kernel: the workgroup's steps, each with its window staged first when it fits
-template <int NM, int KS, bool XZ, bool FENCED>
+template <int NM, int KS, bool XZ, bool FENCED, bool TAB = false>
 __device__ __forceinline__ void wq_fwd_role(const WqArgs& a, int s_beg, int s_end, const WqUnit un, const float* __restrict__ rec,
                                             const float* __restrict__ h, const float* __restrict__ xhat,
                                             const float* __restrict__ s_in, const float* __restrict__ x_in, const float* wl,
@@ -1053,6 +1114,13 @@ __device__ __forceinline__ void wq_fwd_role(const WqArgs& a, int s_beg, int s_en
   // the workgroup's chunk [s_beg, s_end) counts UNITS of a.mlong short steps = one long step: the steps of this unit's class in it
   const WqClass cl = wq_class(a, un.l);
   const int c_beg = cl.m == a.mlong ? s_beg : s_beg * a.mlong, c_end = min(cl.m == a.mlong ? s_end : s_end * a.mlong, cl.n_steps);
+  if constexpr (TAB) {   // the table is staged (kernel top): the waves walk their ranges of the chunk's steps without meeting again
+    for (int step = c_beg; step < c_end; ++step) {
+      const int range = step * WQ_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      if (range < cl.n_ranges) wq_fwd_body<NM, KS, true, XZ, FENCED, true>(a, range, un, wc, rec, h, xhat, s_in, x_in, wl, s_out, x_out, tbl, win, 0, st_, last_);
+    }
+    return;
+  }
   for (int step = c_beg; step < c_end; ++step) {
     const int w0 = cl.win[2 * step], nrows = cl.win[2 * step + 1];
 #ifdef XEQ_WQ_NO_WINDOW
@@ -1097,7 +1165,8 @@ __global__ void __launch_bounds__(256) k_wq_pack_weights(WqArgs a, const float* 
 
 // XZ: xhat is zero on every l > 0 column (the model's first message block: XEmbedding hands over x = 0, and the
 // equivariant layer norm of zero is zero there); the l = 0 role is the general one
-template <int KS, bool XZ>
+// TAB (with XZ): h / xhat point at the element table's rows and a.pgath at the slots' table rows (table form, above)
+template <int KS, bool XZ, bool TAB = false>
 __global__ void __launch_bounds__(64 * WQ_WAVES) __attribute__((amdgpu_waves_per_eu(XEQ_WQ_FWD_WPE)))
 k_message_fwd_wq(WqArgs a, const float* __restrict__ rec, const float* __restrict__ h, const float* __restrict__ xhat,
                  const float* __restrict__ s_in, const float* __restrict__ x_in, const float* __restrict__ w_rbf,
@@ -1110,6 +1179,11 @@ k_message_fwd_wq(WqArgs a, const float* __restrict__ rec, const float* __restric
   if (s_beg >= s_end) return;   // padding block of the grid / empty chunk of a short region (workgroup-uniform)
   const WqUnit un = wq_unit(a, unit);
   wq_stage_weights<KS>(a, un, w_rbf, b_rbf, wl);
+  if constexpr (TAB) {
+    static_assert(XZ, "the table form is a first-block form");
+    if (un.l == 0) wq_stage_table_fwd<1>(a, un, h, xhat, win);
+    else wq_stage_table_fwd<3>(a, un, h, xhat, win);   // (l = 1 and l = 2 alike: the unit's gate_edge columns)
+  }
   __syncthreads();
   int* tbl = tbl_all[threadIdx.x >> 6];
 #ifdef XEQ_WQ_ONLY_L   // development: register budget of one role
@@ -1120,9 +1194,9 @@ k_message_fwd_wq(WqArgs a, const float* __restrict__ rec, const float* __restric
   unsigned long long rr0_;
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rr0_)::"memory");
 #endif
-  if (un.l == 0) wq_fwd_role<1, KS, false, !XZ>(a, s_beg, s_end, un, rec, h, xhat, s_in, x_in, wl, s_out, x_out, tbl, win);
-  else if (un.l == 1) wq_fwd_role<3, KS, XZ, !XZ>(a, s_beg, s_end, un, rec, h, xhat, s_in, x_in, wl, s_out, x_out, tbl, win);
-  else wq_fwd_role<5, KS, XZ, !XZ>(a, s_beg, s_end, un, rec, h, xhat, s_in, x_in, wl, s_out, x_out, tbl, win);
+  if (un.l == 0) wq_fwd_role<1, KS, false, !XZ, TAB>(a, s_beg, s_end, un, rec, h, xhat, s_in, x_in, wl, s_out, x_out, tbl, win);
+  else if (un.l == 1) wq_fwd_role<3, KS, XZ, !XZ, TAB>(a, s_beg, s_end, un, rec, h, xhat, s_in, x_in, wl, s_out, x_out, tbl, win);
+  else wq_fwd_role<5, KS, XZ, !XZ, TAB>(a, s_beg, s_end, un, rec, h, xhat, s_in, x_in, wl, s_out, x_out, tbl, win);
 #ifdef XEQ_WQ_ROLE_TIME_FWD
   if (threadIdx.x == 0 && blockIdx.x < 8192) {
     unsigned long long rr1_;
@@ -1207,7 +1281,12 @@ __device__ __forceinline__ void wq_stage_bwd(const WqArgs& a, const WqUnit& un, 
   }
 }
 
-template <int NM, int KS, bool WIN, bool FIRST>
+// TAB (with FIRST): the table form of the first block -- the owners' rows are rows of the element table (h, xhat_ point at h_table
+// [T, H] and xhat0_table [T, F]; the quad's table row comes with its record: a.qtab, T_QTAB), read from the few cache-resident rows
+// of the species present instead of from a per-node copy; the gathered gradients are per node and keep their window.
+// (MEASURED AND NOT KEPT: a 24 KB window and amdgpu_waves_per_eu(3) for this form -- 165 registers, no spill, three workgroups per CU --
+// ran the launch in 190 instead of 134 us on QM9-1024: the l > 0 units' steps no longer fit the window; profiles/first_block_table_timing.txt)
+template <int NM, int KS, bool WIN, bool FIRST, bool TAB = false>
 __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit, const WqUnit un, const WqCols& wc,
                                             const float* __restrict__ rec, const float* __restrict__ drec,
                                             const float* __restrict__ h, const float* __restrict__ xhat_,
@@ -1215,6 +1294,7 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
                                             float* __restrict__ grad_h, float* __restrict__ grad_xhat_, const WqParts parts,
                                             int* tbl, const float* win, int w0, unsigned long long* st_,
                                             unsigned long long& last_) {
+  static_assert(!TAB || FIRST, "the table form is a first-block form");
   constexpr bool HAS_S = NM == 1;
   constexpr int YOFF = NM == 3 ? 0 : 3;
   constexpr int ROWB = (NM + (HAS_S ? 1 : 0)) * 128;
@@ -1254,8 +1334,8 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
 
   using Row = WqRow<KS, 2, (NM > 1)>;
   Row row;
-  wq_row<KS, 2, (NM > 1)>(a, st, lane, 0, rec, drec, row, (int)gbase);
-  wq_publish<KS, 2, (NM > 1)>(lane, row, stride0, stride1, tbl, gbase);
+  wq_row<KS, 2, (NM > 1), TAB>(a, st, lane, 0, rec, drec, row, (int)gbase);
+  wq_publish<KS, 2, (NM > 1), TAB>(lane, row, stride0, stride1, tbl, gbase);
   __builtin_amdgcn_wave_barrier();
 
   // The owners' rows (h_state, h_edge, h_msg, xhat of the unit's columns) of a tile's four quads.  They come from GLOBAL memory (the
@@ -1277,13 +1357,17 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
     Owners o;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const uint32_t own = (uint32_t)tb_[T_QOWN + 4 * hh + g];
+      const uint32_t own = (uint32_t)tb_[(TAB ? T_QTAB : T_QOWN) + 4 * hh + g];
       o.he[g] = wq_ld(h, own * row_h + wc.b_hs + he_off);
       if constexpr (HAS_S) o.hm[g] = wq_ld(h, own * row_h + wc.b_hm);
       if constexpr (!FIRST || HAS_S) {
         o.hs[g] = wq_ld(h, own * row_h + wc.b_hs);
+        if constexpr (TAB) {   // (FIRST: l = 0 only) row `own` of xhat0_table [T, F]
+          o.x[g][0] = wq_ld(xhat_, own * (4u * (uint32_t)a.F) + wc.b_hs);
+        } else {
 #pragma unroll
-        for (int m = 0; m < NM; ++m) o.x[g][m] = wq_ld(xhat, own * wc.xnode_b + wc.b_x + m * wc.xcomp_b);
+          for (int m = 0; m < NM; ++m) o.x[g][m] = wq_ld(xhat, own * wc.xnode_b + wc.b_x + m * wc.xcomp_b);
+        }
       }
     }
     return o;
@@ -1395,7 +1479,7 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
     // that is published from them, instead of behind the last matrix chain (the stamps show 8 % of a wave's cycles at the publish and
     // 6 % at the next tile's top; 34 registers).  Measured on the whole step: no change (profiles/r06_small_experiments.txt item 7).
 #ifndef XEQ_WQ_NO_ROW_EARLY
-    if constexpr (ROW_EARLY) wq_row<KS, 2, (NM > 1)>(a, st, lane, t + 1, rec, drec, row, (int)gbase);
+    if constexpr (ROW_EARLY) wq_row<KS, 2, (NM > 1), TAB>(a, st, lane, t + 1, rec, drec, row, (int)gbase);
 #endif
     WQ_STAMP(5);   // tile top: gathers issued
     // l > 0: the gathered rows are read one component at a time (four rows x one m), used and dropped: out of the LDS
@@ -1554,7 +1638,7 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
       }
     }
     XEQ_WQ_RSB();
-    if constexpr (!HAS_S && !ROW_EARLY) wq_row<KS, 2, (NM > 1)>(a, st, lane, t + 1, rec, drec, row, (int)gbase);   // next tile's records
+    if constexpr (!HAS_S && !ROW_EARLY) wq_row<KS, 2, (NM > 1), TAB>(a, st, lane, t + 1, rec, drec, row, (int)gbase);   // next tile's records
     WQ_STAMP(8);   // rows of pass E (+ dL/dY sums)
     if constexpr (HAS_S) {  // ---- pass M
       float gsv[16];          // the centers' grad_s rows: only this pass reads them; they land under its MFMAs
@@ -1568,7 +1652,7 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
       const f32x16 dm = (OVL && HAS_S) ? dm_h : wq_filter<KS>(R, Wm, lane), qm = (OVL && HAS_S) ? qm_h : wq_filter<KS>(Rd, Wm, lane);
       if constexpr (!ROW_EARLY) {
         XEQ_WQ_RSB();
-        wq_row<KS, 2, (NM > 1)>(a, st, lane, t + 1, rec, drec, row, (int)gbase);   // last MFMAs issued: next tile's records
+        wq_row<KS, 2, (NM > 1), TAB>(a, st, lane, t + 1, rec, drec, row, (int)gbase);   // last MFMAs issued: next tile's records
         XEQ_WQ_RSB();
       }
       WQ_STAMP(6);
@@ -1607,7 +1691,7 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
       } else if (keeper) parts.pd[(int64_t)unit * parts.P + my_slot] = tot;
     }
     WQ_STAMP(11);  // dL/dd channel sums
-    wq_publish<KS, 2, (NM > 1)>(lane, row, stride0, stride1, tnext, gbase);
+    wq_publish<KS, 2, (NM > 1), TAB>(lane, row, stride0, stride1, tnext, gbase);
     __builtin_amdgcn_wave_barrier();
     if constexpr (OWN_AHEAD) own_next = load_owners(tnext);   // the next tile's owners are known: their rows fly under the back edge
     WQ_STAMP(12);  // next table published
@@ -1615,7 +1699,7 @@ __device__ __forceinline__ void wq_bwd_body(const WqArgs& a, int range, int unit
   if constexpr (DEFER) flush_parts();   // the last tile's
 }
 
-template <int NM, int KS, bool FIRST>
+template <int NM, int KS, bool FIRST, bool TAB = false>
 __device__ __forceinline__ void wq_bwd_role(const WqArgs& a, int s_beg, int s_end, int unit, const WqUnit un, const float* __restrict__ rec,
                                             const float* __restrict__ drec, const float* __restrict__ h,
                                             const float* __restrict__ xhat, const float* __restrict__ grad_s,
@@ -1643,8 +1727,8 @@ __device__ __forceinline__ void wq_bwd_role(const WqArgs& a, int s_beg, int s_en
     WQ_STAMP(2);
     const int range = step * WQ_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform: the stream bounds become scalar loads)
     if (range < cl.n_ranges) {
-      if (use_win) wq_bwd_body<NM, KS, true, FIRST>(a, range, unit, un, wc, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win, w0, st_, last_);
-      else wq_bwd_body<NM, KS, false, FIRST>(a, range, unit, un, wc, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win, 0, st_, last_);
+      if (use_win) wq_bwd_body<NM, KS, true, FIRST, TAB>(a, range, unit, un, wc, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win, w0, st_, last_);
+      else wq_bwd_body<NM, KS, false, FIRST, TAB>(a, range, unit, un, wc, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win, 0, st_, last_);
     }
     WQ_STAMP(3);
     __syncthreads();
@@ -1663,7 +1747,7 @@ __device__ __forceinline__ void wq_bwd_role(const WqArgs& a, int s_beg, int s_en
 
 // FIRST: the model's first message block in a force evaluation -- no node gradients are wanted (grad_h, grad_xhat NULL)
 // and xhat is zero on every l > 0 column
-template <int KS, bool FIRST>
+template <int KS, bool FIRST, bool TAB = false>
 __global__ void __launch_bounds__(64 * WQ_WAVES) __attribute__((amdgpu_waves_per_eu(XEQ_WQ_BWD_WPE)))
 k_message_bwd_wq(WqArgs a, const float* __restrict__ rec, const float* __restrict__ drec, const float* __restrict__ h,
                  const float* __restrict__ xhat, const float* __restrict__ grad_s, const float* __restrict__ grad_x,
@@ -1688,9 +1772,9 @@ k_message_bwd_wq(WqArgs a, const float* __restrict__ rec, const float* __restric
   unsigned long long rr0_;
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rr0_)::"memory");
 #endif
-  if (un.l == 0) wq_bwd_role<1, KS, FIRST>(a, s_beg, s_end, unit, un, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win);
-  else if (un.l == 1) wq_bwd_role<3, KS, FIRST>(a, s_beg, s_end, unit, un, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win);
-  else wq_bwd_role<5, KS, FIRST>(a, s_beg, s_end, unit, un, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win);
+  if (un.l == 0) wq_bwd_role<1, KS, FIRST, TAB>(a, s_beg, s_end, unit, un, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win);
+  else if (un.l == 1) wq_bwd_role<3, KS, FIRST, TAB>(a, s_beg, s_end, unit, un, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win);
+  else wq_bwd_role<5, KS, FIRST, TAB>(a, s_beg, s_end, unit, un, rec, drec, h, xhat, grad_s, grad_x, wl, grad_h, grad_xhat, parts, tbl, win);
 #ifdef XEQ_WQ_ROLE_TIME
   if (threadIdx.x == 0 && blockIdx.x < 8192) {
     unsigned long long rr1_;
@@ -1878,9 +1962,29 @@ using namespace xeq;
     else XEQ_WQ_DISPATCH_KS(KERNEL, false, __VA_ARGS__);     \
   } while (0)
 
+// the table form of the first block: KERNEL<KS, true, true>
+#define XEQ_WQ_DISPATCH_TAB(KERNEL, ...)                                                                                    \
+  do {                                                                                                                      \
+    const int ks = wq_ks(num_basis);                                                                                        \
+    if (ks <= 1) hipLaunchKernelGGL((KERNEL<1, true, true>), grid, dim3(64 * WQ_WAVES), 0, (hipStream_t)stream, __VA_ARGS__);      \
+    else if (ks <= 3) hipLaunchKernelGGL((KERNEL<3, true, true>), grid, dim3(64 * WQ_WAVES), 0, (hipStream_t)stream, __VA_ARGS__); \
+    else if (ks <= 4) hipLaunchKernelGGL((KERNEL<4, true, true>), grid, dim3(64 * WQ_WAVES), 0, (hipStream_t)stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<8, true, true>), grid, dim3(64 * WQ_WAVES), 0, (hipStream_t)stream, __VA_ARGS__);              \
+  } while (0)
+// what the table entry points ask of their arguments (include/xeq.h: the callers ask xeq_message_wq_first_table first)
+#define XEQ_WQ_CHECK_TABLE(who, rows, tab, hint)                                                                                  \
+  do {                                                                                                                            \
+    XEQ_CHECK_ARG((rows) >= 1 && (rows) <= WQ_TAB_MAX_ROWS, who ": the element table has %lld rows, the table form takes 1 .. %d", \
+                  (long long)(rows), WQ_TAB_MAX_ROWS);                                                                            \
+    XEQ_CHECK_ARG((tab) != nullptr && h_table != nullptr && xhat0_table != nullptr, who ": NULL table argument");                 \
+    XEQ_CHECK_ARG(((hint) & 1) && ((hint) & XEQ_XHAT_HIGHER_L_ZERO), who ": the table form is the first block's (BT layout, XEQ_XHAT_HIGHER_L_ZERO)"); \
+  } while (0)
+
 extern "C" {
 
 #ifndef XEQ_WQ_PART_BWD
+int xeq_message_wq_table_max_rows(void) { return WQ_TAB_MAX_ROWS; }
+
 int xeq_message_wq_supported(int num_basis, int node_dim, const int32_t mul[3]) { return wq_supported(num_basis, node_dim, mul) ? 1 : 0; }
 
 int xeq_message_wq_fits(int64_t n_nodes, int64_t n_edges, int num_basis, int node_dim, const int32_t mul[3]) {
@@ -1953,9 +2057,9 @@ int64_t xeq_message_wq_win_ints(int n_ranges) {   /* ints of the plan's window t
   return 2 * ((int64_t)wq_class_steps(n_ranges, 1) + (int64_t)wq_class_steps(n_ranges, 2) + 1);
 }
 
-int xeq_edge_basis_wq(const void* vec, int64_t n_nodes, int64_t n_edges, const int32_t* qptr, const int32_t* peid,
-                      int rbf_kind, int cutoff_kind, int num_basis, double cutoff, const void* p0, const void* p1,
-                      void* basis, void* dbasis, void* stream) {
+static int wq_edge_basis(const void* vec, int64_t n_nodes, int64_t n_edges, const int32_t* qptr, const int32_t* peid,
+                         int rbf_kind, int cutoff_kind, int num_basis, double cutoff, const void* p0, const void* p1,
+                         void* basis, void* dbasis, const WqTableIndex& ti, void* stream) {
   XEQ_CHECK_ARG(n_edges >= 0 && n_nodes >= 0 && num_basis >= 1 && num_basis <= 31 && cutoff > 0, "xeq_edge_basis_wq: bad sizes");
   XEQ_CHECK_ARG(rbf_kind >= XEQ_RBF_BESSEL && rbf_kind <= XEQ_RBF_EXPNORM, "xeq_edge_basis_wq: rbf kernel %d is not implemented", rbf_kind);
   XEQ_CHECK_ARG(rbf_kind == XEQ_RBF_BESSEL || p1 != nullptr, "xeq_edge_basis_wq: this radial basis needs its second parameter array (std / logc / mu)");
@@ -1966,9 +2070,22 @@ int xeq_edge_basis_wq(const void* vec, int64_t n_nodes, int64_t n_edges, const i
   XEQ_CHECK_ARG(pcap * wq_recf(ks) < (1ll << 31) * 2, "xeq_edge_basis_wq: too many edges for 32-bit record offsets (shard the batch)");
   RadialSpec rs{rbf_kind, cutoff_kind, num_basis, cutoff};
   hipLaunchKernelGGL(k_wq_records, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)vec,
-                     peid, qptr, n_nodes, pcap, rs, (const float*)p0, (const float*)p1, (float*)basis, (float*)dbasis, wq_recf(ks), wq_tailw(ks), wq_bftail(ks) ? 1 : 0);
+                     peid, qptr, n_nodes, pcap, rs, (const float*)p0, (const float*)p1, (float*)basis, (float*)dbasis, wq_recf(ks), wq_tailw(ks), wq_bftail(ks) ? 1 : 0, ti);
   XEQ_CHECK_LAUNCH("xeq_edge_basis_wq");
   return XEQ_OK;
+}
+int xeq_edge_basis_wq(const void* vec, int64_t n_nodes, int64_t n_edges, const int32_t* qptr, const int32_t* peid,
+                      int rbf_kind, int cutoff_kind, int num_basis, double cutoff, const void* p0, const void* p1,
+                      void* basis, void* dbasis, void* stream) {
+  return wq_edge_basis(vec, n_nodes, n_edges, qptr, peid, rbf_kind, cutoff_kind, num_basis, cutoff, p0, p1, basis, dbasis, WqTableIndex{}, stream);
+}
+int xeq_edge_basis_wq_table(const void* vec, int64_t n_nodes, int64_t n_edges, const int32_t* qptr, const int32_t* peid,
+                            int rbf_kind, int cutoff_kind, int num_basis, double cutoff, const void* p0, const void* p1,
+                            void* basis, void* dbasis, const int32_t* pgath, const int32_t* qinfo, const void* z, int z_is_int64,
+                            int64_t table_rows, int32_t* slot_rows, int32_t* quad_rows, void* stream) {
+  XEQ_CHECK_ARG(pgath && qinfo && z && slot_rows && quad_rows && table_rows >= 1, "xeq_edge_basis_wq_table: NULL argument / empty table");
+  const WqTableIndex ti{z, z_is_int64, table_rows, pgath, (const uint32_t*)qinfo, slot_rows, quad_rows};
+  return wq_edge_basis(vec, n_nodes, n_edges, qptr, peid, rbf_kind, cutoff_kind, num_basis, cutoff, p0, p1, basis, dbasis, ti, stream);
 }
 
 static int wq_ks_template(int num_basis) {   // the KS the dispatch macros instantiate for this basis width
@@ -1999,11 +2116,12 @@ int xeq_message_wq_pack_weights(const void* w_rbf, const void* b_rbf, int num_ba
   return XEQ_OK;
 }
 
-int xeq_message_fwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
-                       const int32_t* c_rowptr, const int32_t* pgath, const int32_t* qinfo, const void* basis, const void* h,
-                       const void* xhat, const void* s_in, const void* x_in, const void* w_rbf, const void* b_rbf,
-                       int num_basis, int node_dim, const int32_t mul[3], void* s_out, void* x_out, int xhat_layout,
-                       void* stream) {
+// slot_rows != NULL: the table form (h / xhat are then the element table's rows)
+static int wq_message_fwd(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                          const int32_t* c_rowptr, const int32_t* pgath, const int32_t* qinfo, const void* basis, const void* h,
+                          const void* xhat, const void* s_in, const void* x_in, const void* w_rbf, const void* b_rbf,
+                          int num_basis, int node_dim, const int32_t mul[3], void* s_out, void* x_out, int xhat_layout,
+                          const int32_t* slot_rows, int64_t table_rows, void* stream) {
   WqArgs a{};
   int rcode = wq_check("xeq_message_fwd_wq", n_nodes, n_edges, n_ranges, num_basis, node_dim, mul, a);
   if (rcode != XEQ_OK) return rcode;
@@ -2011,7 +2129,8 @@ int xeq_message_fwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int
   a.sq = sq;
   a.sn = sn;
   a.rowptr = c_rowptr;
-  a.pgath = pgath;
+  a.pgath = slot_rows ? slot_rows : pgath;
+  a.tab_rows = (int)table_rows;
   a.qinfo = (const uint32_t*)qinfo;
   a.xl = xhat_layout & 1;
   a.packed_w = (xhat_layout & XEQ_WQ_PACKED_WEIGHTS) ? 1 : 0;
@@ -2021,10 +2140,31 @@ int xeq_message_fwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int
   unsigned nblocks;
   wq_geometry(a, nunits, nblocks);
   dim3 grid(nblocks);
-  XEQ_WQ_DISPATCH(k_message_fwd_wq, x_zero, a, (const float*)basis, (const float*)h, (const float*)xhat, (const float*)s_in,
-                  (const float*)x_in, (const float*)w_rbf, (const float*)b_rbf, (float*)s_out, (float*)x_out);
-  XEQ_CHECK_LAUNCH("xeq_message_fwd_wq");
+  if (slot_rows)
+    XEQ_WQ_DISPATCH_TAB(k_message_fwd_wq, a, (const float*)basis, (const float*)h, (const float*)xhat, (const float*)s_in,
+                        (const float*)x_in, (const float*)w_rbf, (const float*)b_rbf, (float*)s_out, (float*)x_out);
+  else
+    XEQ_WQ_DISPATCH(k_message_fwd_wq, x_zero, a, (const float*)basis, (const float*)h, (const float*)xhat, (const float*)s_in,
+                    (const float*)x_in, (const float*)w_rbf, (const float*)b_rbf, (float*)s_out, (float*)x_out);
+  XEQ_CHECK_LAUNCH(slot_rows ? "xeq_message_fwd_wq_table" : "xeq_message_fwd_wq");
   return XEQ_OK;
+}
+int xeq_message_fwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                       const int32_t* c_rowptr, const int32_t* pgath, const int32_t* qinfo, const void* basis, const void* h,
+                       const void* xhat, const void* s_in, const void* x_in, const void* w_rbf, const void* b_rbf,
+                       int num_basis, int node_dim, const int32_t mul[3], void* s_out, void* x_out, int xhat_layout,
+                       void* stream) {
+  return wq_message_fwd(n_nodes, n_edges, n_ranges, sq, sn, win, c_rowptr, pgath, qinfo, basis, h, xhat, s_in, x_in, w_rbf, b_rbf, num_basis,
+                        node_dim, mul, s_out, x_out, xhat_layout, nullptr, 0, stream);
+}
+int xeq_message_fwd_wq_table(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                             const int32_t* c_rowptr, const int32_t* slot_rows, const int32_t* qinfo, const void* basis,
+                             const void* h_table, const void* xhat0_table, int64_t table_rows, const void* s_in, const void* x_in,
+                             const void* w_rbf, const void* b_rbf, int num_basis, int node_dim, const int32_t mul[3], void* s_out,
+                             void* x_out, int xhat_layout, void* stream) {
+  XEQ_WQ_CHECK_TABLE("xeq_message_fwd_wq_table", table_rows, slot_rows, xhat_layout);
+  return wq_message_fwd(n_nodes, n_edges, n_ranges, sq, sn, win, c_rowptr, nullptr, qinfo, basis, h_table, xhat0_table, s_in, x_in, w_rbf, b_rbf,
+                        num_basis, node_dim, mul, s_out, x_out, xhat_layout, slot_rows, table_rows, stream);
 }
 
 #endif
@@ -2033,11 +2173,12 @@ int64_t xeq_message_wq_parts_floats(int64_t n_nodes, int64_t n_edges, const int3
   return wq_pcap(n_nodes, n_edges) * (int64_t)(mul[0] / 32 + mul[1] / 32 + mul[2] / 32 + 3 * (mul[1] / 32) + 5 * (mul[2] / 32));
 }
 
-int xeq_message_bwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
-                       const int32_t* n_rowptr, const int32_t* pgath, const int32_t* qinfo, const void* basis,
-                       const void* dbasis, const void* h, const void* xhat, const void* grad_s, const void* grad_x,
-                       const void* w_rbf, const void* b_rbf, int num_basis, int node_dim, const int32_t mul[3], void* grad_h,
-                       void* grad_xhat, void* parts, int xhat_layout, void* stream) {
+// quad_rows != NULL: the table form (h / xhat are then the element table's rows; no node gradients)
+static int wq_message_bwd(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                          const int32_t* n_rowptr, const int32_t* pgath, const int32_t* qinfo, const void* basis,
+                          const void* dbasis, const void* h, const void* xhat, const void* grad_s, const void* grad_x,
+                          const void* w_rbf, const void* b_rbf, int num_basis, int node_dim, const int32_t mul[3], void* grad_h,
+                          void* grad_xhat, void* parts, int xhat_layout, const int32_t* quad_rows, int64_t table_rows, void* stream) {
   WqArgs a{};
   int rcode = wq_check("xeq_message_bwd_wq", n_nodes, n_edges, n_ranges, num_basis, node_dim, mul, a);
   if (rcode != XEQ_OK) return rcode;
@@ -2047,6 +2188,8 @@ int xeq_message_bwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int
   a.rowptr = n_rowptr;
   a.pgath = pgath;
   a.qinfo = (const uint32_t*)qinfo;
+  a.qtab = quad_rows;
+  a.tab_rows = (int)table_rows;
   a.xl = xhat_layout & 1;
   a.mirror = (xhat_layout & XEQ_WQ_MIRROR_WALK) ? 1 : 0;
   a.packed_w = (xhat_layout & XEQ_WQ_PACKED_WEIGHTS) ? 1 : 0;
@@ -2061,11 +2204,33 @@ int xeq_message_bwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int
   unsigned nblocks;
   wq_geometry(a, nunits, nblocks);
   dim3 grid(nblocks);
-  XEQ_WQ_DISPATCH(k_message_bwd_wq, first, a, (const float*)basis, (const float*)dbasis, (const float*)h, (const float*)xhat,
-                  (const float*)grad_s, (const float*)grad_x, (const float*)w_rbf, (const float*)b_rbf, (float*)grad_h,
-                  (float*)grad_xhat, pr);
-  XEQ_CHECK_LAUNCH("xeq_message_bwd_wq");
+  if (quad_rows)
+    XEQ_WQ_DISPATCH_TAB(k_message_bwd_wq, a, (const float*)basis, (const float*)dbasis, (const float*)h, (const float*)xhat,
+                        (const float*)grad_s, (const float*)grad_x, (const float*)w_rbf, (const float*)b_rbf, (float*)nullptr,
+                        (float*)nullptr, pr);
+  else
+    XEQ_WQ_DISPATCH(k_message_bwd_wq, first, a, (const float*)basis, (const float*)dbasis, (const float*)h, (const float*)xhat,
+                    (const float*)grad_s, (const float*)grad_x, (const float*)w_rbf, (const float*)b_rbf, (float*)grad_h,
+                    (float*)grad_xhat, pr);
+  XEQ_CHECK_LAUNCH(quad_rows ? "xeq_message_bwd_wq_table" : "xeq_message_bwd_wq");
   return XEQ_OK;
+}
+int xeq_message_bwd_wq(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                       const int32_t* n_rowptr, const int32_t* pgath, const int32_t* qinfo, const void* basis,
+                       const void* dbasis, const void* h, const void* xhat, const void* grad_s, const void* grad_x,
+                       const void* w_rbf, const void* b_rbf, int num_basis, int node_dim, const int32_t mul[3], void* grad_h,
+                       void* grad_xhat, void* parts, int xhat_layout, void* stream) {
+  return wq_message_bwd(n_nodes, n_edges, n_ranges, sq, sn, win, n_rowptr, pgath, qinfo, basis, dbasis, h, xhat, grad_s, grad_x, w_rbf, b_rbf,
+                        num_basis, node_dim, mul, grad_h, grad_xhat, parts, xhat_layout, nullptr, 0, stream);
+}
+int xeq_message_bwd_wq_table(int64_t n_nodes, int64_t n_edges, int n_ranges, const int32_t* sq, const int32_t* sn, const int32_t* win,
+                             const int32_t* n_rowptr, const int32_t* pgath, const int32_t* qinfo, const int32_t* quad_rows,
+                             const void* basis, const void* dbasis, const void* h_table, const void* xhat0_table, int64_t table_rows,
+                             const void* grad_s, const void* grad_x, const void* w_rbf, const void* b_rbf, int num_basis, int node_dim,
+                             const int32_t mul[3], void* parts, int xhat_layout, void* stream) {
+  XEQ_WQ_CHECK_TABLE("xeq_message_bwd_wq_table", table_rows, quad_rows, xhat_layout);
+  return wq_message_bwd(n_nodes, n_edges, n_ranges, sq, sn, win, n_rowptr, pgath, qinfo, basis, dbasis, h_table, xhat0_table, grad_s, grad_x, w_rbf,
+                        b_rbf, num_basis, node_dim, mul, nullptr, nullptr, parts, xhat_layout, quad_rows, table_rows, stream);
 }
 
 #endif

@@ -397,6 +397,16 @@ int xeq_message_auto_family(int dtype, int64_t n_nodes, int64_t n_edges, int num
   return XEQ_FAMILY_GENERIC;
 }
 
+/* whether the model's first message block takes the table form of the wq kernels (include/xeq.h, xeq_message_fwd_wq_table): every front
+ * asks here.  Anything else -- a block whose front half ran per node (behind a charge / spin embedding), a pass that wants parameter
+ * gradients, a table that does not fit the kernels' LDS, another kernel family -- runs the forms it ran before. */
+int xeq_message_wq_first_table(int family, int64_t table_rows, int training, int per_node_front) {
+  const char* env = getenv("XEQ_WQ_FIRST_TABLE");
+  if (env && env[0] == '0' && env[1] == 0) return 0;
+  if (family != XEQ_FAMILY_WQ || training || per_node_front) return 0;
+  return table_rows >= 1 && table_rows <= 128 && table_rows <= xeq_message_wq_table_max_rows() ? 1 : 0;
+}
+
 /* rows up to which the node-side products take their few-row forms (16 x 16 exact-f32 tiles, bit-equal to the 32-row forms;
  * csrc/xeq_linear_s.h): 3 584 unless XEQ_SMALL_ROWS says otherwise (0: never).  Host only. */
 int64_t xeq_small_rows_limit(void) { return xeq_small_rows(); }
@@ -713,9 +723,11 @@ __global__ void k_first_block_front(const Z* __restrict__ z, int64_t n, int64_t 
 
 extern "C" int xeq_first_block_front(const void* z, int z_is_int64, int64_t n, int64_t n_rows, const void* rows_s, const void* rows_h, const void* rows_x0,
                                      int node_dim, int hidden_dim, int64_t irreps_dim, void* s_out, void* h_out, void* xhat_out, void* stream) {
-  XEQ_CHECK_ARG(n >= 0 && node_dim > 0 && node_dim % 4 == 0 && hidden_dim % 4 == 0 && irreps_dim % 4 == 0 && irreps_dim >= node_dim,
-                "xeq_first_block_front: widths must be multiples of four floats");
-  XEQ_CHECK_ARG(z && rows_s && rows_h && rows_x0 && s_out && h_out && xhat_out && n_rows >= 1, "xeq_first_block_front: NULL argument / empty table");
+  // hidden_dim == 0 / irreps_dim == 0: h / xhat are not gathered (the wq kernels' table form reads the table rows themselves)
+  XEQ_CHECK_ARG(n >= 0 && node_dim > 0 && node_dim % 4 == 0 && hidden_dim >= 0 && hidden_dim % 4 == 0 && irreps_dim % 4 == 0 &&
+                (irreps_dim == 0 || irreps_dim >= node_dim), "xeq_first_block_front: widths must be multiples of four floats");
+  XEQ_CHECK_ARG(z && rows_s && s_out && (hidden_dim == 0 || (rows_h && h_out)) && (irreps_dim == 0 || (rows_x0 && xhat_out)) && n_rows >= 1,
+                "xeq_first_block_front: NULL argument / empty table");
   if (n == 0) return XEQ_OK;
   const int64_t total = n * ((node_dim + hidden_dim + irreps_dim) / 4);
   const dim3 grid((unsigned)((total + 255) / 256));

@@ -333,6 +333,7 @@ struct WqPlan {
   int n_ranges = 0;
   int64_t pcap = 0;
   Tensor qptr, pgath, peid, qinfo, sq, sn, win, rowptr, work, basis, dbasis;
+  Tensor slot_rows, quad_rows;   // table form of the first block: element-table row per padded slot / per quad's owner (xeq_edge_basis_wq_table)
 };
 struct Graph {
   int64_t N = 0, E = 0;
@@ -340,6 +341,8 @@ struct Graph {
   Tensor ei, c_rowptr, c_perm, n_rowptr, n_perm;   // c_perm undefined: edges already center-sorted.  n_*: the neighbor-sorted view (sorted_view)
   Tensor mirror_map;     // position of every edge's mirror edge (-1: none), for a list with `mirror`; an open list's is a permutation (= n_perm)
   WqPlan fwd, rev;
+  Tensor table_z;        // the first block runs its table form: the atomic numbers its record launches index the element table by ...
+  int64_t table_rows = 0;   // ... and the table's row count (ops.EdgeGraph.first_table)
   Tensor sb_basis, sb_dbasis;
   void sorted_view();    // builds n_rowptr / n_perm by a stable sort when nobody has yet (a periodic mirror map is not a permutation)
   // the edges by neighbor for a kernel that only sums over them (xeq_edge_vectors_bwd): the mirror map over the center rows, else the sorted view
@@ -544,6 +547,7 @@ Tensor minus_one(const at::TensorOptions& fopt) {
 // the block's outputs; g_s / g_x: their gradients, replaced likewise (an undefined g_x is zero).
 struct MsgSaved {   // what a message block keeps for the reverse pass
   Tensor s, x, stats, pre, h, xhat;
+  Tensor tab_z, tab_h, tab_x0;   // first block in its table form (nn/fused.py::first_block_table): atomic numbers, h_table, xhat0_table
 };
 struct UpdSaved {   // ... and an update block
   Tensor s, x, stats, uv, pre, a, ip;
@@ -585,12 +589,19 @@ Tensor embed_and_first_front(const Hyper& hy, const std::vector<Tensor>& prm, co
     Tensor s = at::empty({N, (int64_t)F}, fopt);
     m0.h = at::empty({N, (int64_t)H}, fopt);
     m0.xhat = at::empty({N * (int64_t)D}, fopt);
+    // the wq kernels' table form reads h and xhat from the table rows themselves (nn/fused.py::first_block_table): only s is gathered
+    const bool table = xeq_message_wq_first_table(wq ? XEQ_FAMILY_WQ : XEQ_FAMILY_SB, ef->rows_h.size(0), 0, 0) != 0;
     // the wq kernels never read xhat's l > 0 blocks behind the embedding (XEQ_XHAT_HIGHER_L_ZERO): those are then not even written
     XCALL(xeq_first_block_front(z.data_ptr(), z.scalar_type() == at::kLong, N, ef->rows_s.size(0), ef->rows_s.data_ptr(),
-                                ef->rows_h.data_ptr(), ef->rows_x0.data_ptr(), F, H, wq ? F : D, s.data_ptr(), m0.h.data_ptr(),
-                                m0.xhat.data_ptr(), cur_stream()));
+                                ef->rows_h.data_ptr(), ef->rows_x0.data_ptr(), F, table ? 0 : H, table ? 0 : (wq ? F : D), s.data_ptr(),
+                                m0.h.data_ptr(), m0.xhat.data_ptr(), cur_stream()));
     m0.s = s;
     m0.x = x;
+    if (table) {
+      m0.tab_z = z;
+      m0.tab_h = ef->rows_h;
+      m0.tab_x0 = ef->rows_x0;
+    }
     return s;
   }
   if (hy.embed_kind == 0) {
@@ -634,9 +645,19 @@ void edge_basis(const Hyper& hy, Graph& g, const Tensor& vec, const Tensor& p0, 
     build_wq_plan(g, reverse, w);
     w.basis = at::empty({w.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
     if (want_d) w.dbasis = at::empty({w.pcap, xeq_message_wq_record_floats_for(hy.B)}, fopt);
-    XCALL(xeq_edge_basis_wq(vec.data_ptr(), g.N, g.E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
-                            hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1), w.basis.data_ptr(),
-                            w.dbasis.defined() ? w.dbasis.data_ptr() : nullptr, cur_stream()));
+    if (g.table_z.defined()) {   // the first block's table form: the launch also writes the table rows of the plan's slots and quads
+      w.slot_rows = i32(w.pcap, g.ei);
+      w.quad_rows = i32(w.pcap / 4, g.ei);
+      XCALL(xeq_edge_basis_wq_table(vec.data_ptr(), g.N, g.E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
+                                    hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1), w.basis.data_ptr(),
+                                    w.dbasis.defined() ? w.dbasis.data_ptr() : nullptr, (const int32_t*)w.pgath.data_ptr(),
+                                    (const int32_t*)w.qinfo.data_ptr(), g.table_z.data_ptr(), g.table_z.scalar_type() == at::kLong,
+                                    g.table_rows, (int32_t*)w.slot_rows.data_ptr(), (int32_t*)w.quad_rows.data_ptr(), cur_stream()));
+    } else {
+      XCALL(xeq_edge_basis_wq(vec.data_ptr(), g.N, g.E, (const int32_t*)w.qptr.data_ptr(), (const int32_t*)w.peid.data_ptr(),
+                              hy.rbf_kind, hy.cutoff_kind, hy.B, hy.cutoff, p0.data_ptr(), OP(p1), w.basis.data_ptr(),
+                              w.dbasis.defined() ? w.dbasis.data_ptr() : nullptr, cur_stream()));
+    }
   } else {
     const int w = xeq_edge_basis_width(hy.B);
     g.sb_basis = at::empty({g.E, w}, fopt);
@@ -669,7 +690,14 @@ void message_front_bwd(const Hyper& hy, const Tensor* q, const MsgSaved& m, cons
 void message_block_fwd(const Hyper& hy, Graph& g, const Tensor* q, bool wq, bool first, MsgSaved& m, Tensor& s, Tensor& x) {
   if (!m.h.defined()) message_front_fwd(hy, q, s, x, m);
   Tensor s_out = at::empty_like(s), x_out = at::empty_like(x);
-  if (wq) {
+  if (wq && first && m.tab_h.defined()) {   // the table form: h and xhat from the element table's rows
+    XCALL(xeq_message_fwd_wq_table(g.N, g.E, g.fwd.n_ranges, (const int32_t*)g.fwd.sq.data_ptr(), (const int32_t*)g.fwd.sn.data_ptr(),
+                                   (const int32_t*)g.fwd.win.data_ptr(), (const int32_t*)g.fwd.rowptr.data_ptr(),
+                                   (const int32_t*)g.fwd.slot_rows.data_ptr(), (const int32_t*)g.fwd.qinfo.data_ptr(), g.fwd.basis.data_ptr(),
+                                   m.tab_h.data_ptr(), m.tab_x0.data_ptr(), m.tab_h.size(0), s.data_ptr(), x.data_ptr(), wq_weights(hy, q),
+                                   nullptr, hy.B, hy.F, hy.mul, s_out.data_ptr(), x_out.data_ptr(),
+                                   1 | XEQ_XHAT_HIGHER_L_ZERO | XEQ_WQ_PACKED_WEIGHTS, cur_stream()));
+  } else if (wq) {
     XCALL(xeq_message_fwd_wq(g.N, g.E, g.fwd.n_ranges, (const int32_t*)g.fwd.sq.data_ptr(), (const int32_t*)g.fwd.sn.data_ptr(),
                              (const int32_t*)g.fwd.win.data_ptr(), (const int32_t*)g.fwd.rowptr.data_ptr(),
                              (const int32_t*)g.fwd.pgath.data_ptr(), (const int32_t*)g.fwd.qinfo.data_ptr(), g.fwd.basis.data_ptr(),
@@ -700,6 +728,14 @@ void message_block_bwd(const Hyper& hy, Graph& g, const Tensor* q, bool wq, bool
     Tensor parts = at::empty({std::max<int64_t>(1, xeq_message_wq_parts_floats(N, E, hy.mul))}, vec.options());
     const WqPlan& w = g.mirror ? g.fwd : g.rev;
     const int xl_bwd = (first ? (1 | XEQ_XHAT_HIGHER_L_ZERO) : 1) | (g.mirror ? XEQ_WQ_MIRROR_WALK : 0);
+    if (first && m.tab_h.defined())
+      XCALL(xeq_message_bwd_wq_table(N, E, w.n_ranges, (const int32_t*)w.sq.data_ptr(), (const int32_t*)w.sn.data_ptr(),
+                                     (const int32_t*)w.win.data_ptr(), (const int32_t*)w.rowptr.data_ptr(),
+                                     (const int32_t*)w.pgath.data_ptr(), (const int32_t*)w.qinfo.data_ptr(),
+                                     (const int32_t*)w.quad_rows.data_ptr(), w.basis.data_ptr(), w.dbasis.data_ptr(), m.tab_h.data_ptr(),
+                                     m.tab_x0.data_ptr(), m.tab_h.size(0), g_s.data_ptr(), g_x.data_ptr(), wq_weights(hy, q), nullptr, hy.B,
+                                     hy.F, hy.mul, parts.data_ptr(), xl_bwd | XEQ_WQ_PACKED_WEIGHTS, st));
+    else
     XCALL(xeq_message_bwd_wq(N, E, w.n_ranges, (const int32_t*)w.sq.data_ptr(), (const int32_t*)w.sn.data_ptr(),
                              (const int32_t*)w.win.data_ptr(), (const int32_t*)w.rowptr.data_ptr(),
                              (const int32_t*)w.pgath.data_ptr(), (const int32_t*)w.qinfo.data_ptr(),
@@ -1037,6 +1073,10 @@ std::vector<Tensor> xpainn_eval_impl(const Tensor& pos_in, const Tensor& atomic_
     s = electronic_fwd(hy, &prm[P_BLOCK0 + P_PER_BLOCK * hy.blocks + 4], has, total, s, ptr64);
   }
   if (hy.blocks > 0 && !msv[0].h.defined()) message_front_fwd(hy, Q(0), s, x, msv[0]);
+  if (msv[0].tab_z.defined()) {   // the first block's table form: every record launch of the evaluation writes the plans' table rows
+    g.table_z = msv[0].tab_z;
+    g.table_rows = msv[0].tab_h.size(0);
+  }
   // (wq, mirror walk: the reverse pass runs over the same plan, its derivative records come out of the same launch)
   edge_basis(hy, g, vec, prm[3], prm[4], wq, false, g.mirror && want_bwd);
 

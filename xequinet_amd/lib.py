@@ -144,6 +144,13 @@ _PROTOS = {
     "xeq_edge_basis_wq": [_P, c_int64, c_int64, _P, _P, c_int, c_int, c_int, c_double, _P, _P, _P, _P, _P],
     "xeq_message_fwd_wq": [c_int64, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _I3,
                            _P, _P, c_int, _P],
+    "xeq_message_wq_table_max_rows": [],
+    "xeq_message_wq_first_table": [c_int, c_int64, c_int, c_int],
+    "xeq_edge_basis_wq_table": [_P, c_int64, c_int64, _P, _P, c_int, c_int, c_int, c_double, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, _P, _P, _P],
+    "xeq_message_fwd_wq_table": [c_int64, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int, _I3,
+                                 _P, _P, c_int, _P],
+    "xeq_message_bwd_wq_table": [c_int64, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int, c_int,
+                                 _I3, _P, c_int, _P],
     "xeq_message_wq_parts_floats": [c_int64, c_int64, _I3],
     "xeq_message_bwd_wq": [c_int64, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int,
                            _I3, _P, _P, _P, c_int, _P],

@@ -433,18 +433,11 @@ class EmbeddingLinear(Function):
         return None, None, None, d_w, (d_b if ctx.has_bias else None)
 
 
-def first_block_front(module, z: torch.Tensor, rows: torch.Tensor, n: int, higher_l_unread: bool = False):
-    """(s, h, xhat) of the model's FIRST message block from the element table: behind XEmbedding s = rows[Z] and x = 0, so LayerNorm,
-    EquivariantLayerNorm and scalar_mlp (nn/xpainn.py:128-139) are functions of the element alone.  They run on the table rows (once per
-    weight version: the same xeq_norm_fwd / xeq_mlp2_fwd launches, which give a row the same bits in any batch) and all three are
-    gathered by atomic number in ONE launch (xeq_first_block_front; round 4: three ATen gathers and a fill).  xhat is in BT layout; its
-    l > 0 blocks are the equivariant norm of zero: zero -- and are not even written when the caller knows that nobody reads them
-    (``higher_l_unread``: the wq message kernels under XEQ_XHAT_HIGHER_L_ZERO drop every term with a factor xhat_{l>0}; 27 MB of zeros
-    per QM9-1024 evaluation).  None when the block is not the layout the table form covers."""
+def _element_front(module, rows: torch.Tensor):
+    """(h_table [T, H], xhat0_table [T, F]): scalar_mlp(norm(.)) and the 0e block of the equivariant norm of every row of the element
+    table, cached per weight version."""
     F, mul = module.node_dim, module._mul
     D = sum(m * (2 * l + 1) for l, m in enumerate(mul))
-    if rows.dtype != torch.float32 or mul[0] != F or isinstance(module.norm, torch.nn.Identity) or z.dtype not in (torch.int32, torch.int64):
-        return None
     mlp = module.scalar_mlp
 
     def build():
@@ -453,15 +446,42 @@ def first_block_front(module, z: torch.Tensor, rows: torch.Tensor, n: int, highe
         _, h_t = _mlp_fwd(mlp, shat)
         return h_t.contiguous(), xhat_t[: zt * F].view(zt, F).contiguous()
 
-    h_t, xhat0_t = lib.cached(module, "_element_front", (rows, module.norm.weight, module.norm.bias, module.o3norm.affine_weight,
-                                                         module.o3norm.affine_bias, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias), build)
+    return lib.cached(module, "_element_front", (rows, module.norm.weight, module.norm.bias, module.o3norm.affine_weight,
+                                                 module.o3norm.affine_bias, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias), build)
+
+
+def first_block_table(module, z: torch.Tensor, rows: torch.Tensor, wq: bool, training: bool = False, per_node_front: bool = False):
+    """(atomic numbers, h_table, xhat0_table) when the first message block is to run the wq kernels' TABLE form -- its h and xhat read from
+    the element table's rows instead of the per-node copies first_block_front gathers (include/xeq.h: xeq_message_fwd_wq_table) -- else
+    None.  The rule is the C ABI's (xeq_message_wq_first_table: the registered operator asks the same function)."""
+    if not lib.load().xeq_message_wq_first_table(0 if wq else 1, int(rows.shape[0]), int(bool(training)), int(bool(per_node_front))):
+        return None
+    h_t, xhat0_t = _element_front(module, rows)
+    return z.contiguous(), h_t, xhat0_t
+
+
+def first_block_front(module, z: torch.Tensor, rows: torch.Tensor, n: int, higher_l_unread: bool = False, table_form: bool = False):
+    """(s, h, xhat) of the model's FIRST message block from the element table: behind XEmbedding s = rows[Z] and x = 0, so LayerNorm,
+    EquivariantLayerNorm and scalar_mlp (nn/xpainn.py:128-139) are functions of the element alone.  They run on the table rows (once per
+    weight version: the same xeq_norm_fwd / xeq_mlp2_fwd launches, which give a row the same bits in any batch) and all three are
+    gathered by atomic number in ONE launch (xeq_first_block_front; round 4: three ATen gathers and a fill).  xhat is in BT layout; its
+    l > 0 blocks are the equivariant norm of zero: zero -- and are not even written when the caller knows that nobody reads them
+    (``higher_l_unread``: the wq message kernels under XEQ_XHAT_HIGHER_L_ZERO drop every term with a factor xhat_{l>0}; 27 MB of zeros
+    per QM9-1024 evaluation).  ``table_form``: the block runs the wq kernels' table form (first_block_table), which reads h and xhat from
+    the table rows themselves: only s is gathered, h and xhat are returned as allocations nobody reads.  None when the block is not the
+    layout the table form covers."""
+    F, mul = module.node_dim, module._mul
+    D = sum(m * (2 * l + 1) for l, m in enumerate(mul))
+    if rows.dtype != torch.float32 or mul[0] != F or isinstance(module.norm, torch.nn.Identity) or z.dtype not in (torch.int32, torch.int64):
+        return None
+    h_t, xhat0_t = _element_front(module, rows)
     H = h_t.shape[1]
     z = z.contiguous()
     s = torch.empty((n, F), dtype=rows.dtype, device=rows.device)
     h = torch.empty((n, H), dtype=rows.dtype, device=rows.device)
     xhat = torch.empty(n * D, dtype=rows.dtype, device=rows.device)
-    call("xeq_first_block_front", ptr(z), int(z.dtype == torch.int64), n, rows.shape[0], ptr(rows), ptr(h_t), ptr(xhat0_t), F, H,
-         F if higher_l_unread else D, ptr(s), ptr(h), ptr(xhat), stream())
+    call("xeq_first_block_front", ptr(z), int(z.dtype == torch.int64), n, rows.shape[0], ptr(rows), ptr(h_t), ptr(xhat0_t), F,
+         0 if table_form else H, 0 if table_form else (F if higher_l_unread else D), ptr(s), ptr(h), ptr(xhat), stream())
     return s, h, xhat
 
 

@@ -132,9 +132,16 @@ class XEmbedding(nn.Module):
                 # memory reached d_w / d_b of message_0.rbf_lin on loss.backward())
                 params_want_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in nxt.rbf_lin.parameters())
                                                                 or any(p.requires_grad for p in self.rbf.parameters()))
-                unread = (g is not None and not rows.requires_grad and not params_want_grad and
-                          ops.select_message_impl(rows.dtype, g.n_nodes, g.n_edges, nxt.num_basis, nxt.node_dim, nxt._mul) == "wq")
-                front = first_block_front(nxt, z, rows, z.shape[0], higher_l_unread=unread)
+                wq = g is not None and ops.select_message_impl(rows.dtype, g.n_nodes, g.n_edges, nxt.num_basis, nxt.node_dim, nxt._mul) == "wq"
+                wants_grad = rows.requires_grad or params_want_grad
+                unread = wq and not wants_grad
+                # the wq kernels' table form reads the table rows themselves (fused.first_block_table): then only s is gathered per node
+                from .fused import first_block_table
+
+                table = first_block_table(nxt, z, rows, wq=wq, training=wants_grad) if nxt.node_dim == nxt._mul[0] else None
+                front = first_block_front(nxt, z, rows, z.shape[0], higher_l_unread=unread, table_form=table is not None)
+                if front is not None:
+                    front = (*front, table)
             if front is not None:
                 node_invariant = front[0]
                 data[FIRST_FRONT] = front
@@ -163,7 +170,7 @@ class XEmbedding(nn.Module):
         data[EQUIVARIANT_IS_ZERO] = True
         front = data.pop(FIRST_FRONT, None)
         if front is not None:   # the first message block finds its norms and scalar_mlp done (the hand-over an update block uses)
-            data[PRESTAGE] = (node_invariant, node_equivariant, front[1], front[2], ops.lib.XHAT_HIGHER_L_ZERO)
+            data[PRESTAGE] = (node_invariant, node_equivariant, front[1], front[2], ops.lib.XHAT_HIGHER_L_ZERO, front[3])
         return data
 
 
@@ -223,7 +230,8 @@ class XPainnMessage(nn.Module):
         if self.fused and pre is not None and pre[0] is ori_scalar and pre[1] is ori_equi and not data.get(training.PARAM_GRADS, False):
             # norms and scalar_mlp came out of the update block's launch: the message kernel alone is left (nn/fused.py::NodeBlock)
             p0, p1 = rbf.params()
-            cfg = (rbf.kind, cutoff_fn.kind, self.num_basis, float(cutoff_fn.cutoff), self.node_dim, self._mul, 1 | (pre[4] if len(pre) > 4 else 0))
+            cfg = (rbf.kind, cutoff_fn.kind, self.num_basis, float(cutoff_fn.cutoff), self.node_dim, self._mul, 1 | (pre[4] if len(pre) > 4 else 0),
+                   *((pre[5],) if len(pre) > 5 and pre[5] is not None else ()))
             new_scalar, new_equi = ops.FusedMessage.apply(pre[2], pre[3], data[keys.EDGE_VECTOR], ori_scalar, ori_equi,
                                                           self.rbf_lin.weight, self.rbf_lin.bias, p0, p1, edge_graph(data), cfg)
         elif self.fused:  # block-level path: explicit forward/reverse, see nn/fused.py

@@ -753,20 +753,39 @@ def _basis_cache_hit(cached, vec, key):
     return cached is not None and cached[0] is vec and cached[1] == key
 
 
-def edge_basis_wq(vec, plan, n_nodes, rbf_kind, cutoff_kind, num_basis, cutoff, p0, p1, deriv: bool):
+def _table_rows_hit(plan, table) -> bool:
+    """The plan's slot / quad rows of the element table were written for these atomic numbers (the tensor itself: identity, as for vec)."""
+    rows = plan.get("table_rows")
+    return rows is not None and rows[0] is table[0] and rows[1] == (int(table[1]), table[0]._version)
+
+
+def edge_basis_wq(vec, plan, n_nodes, rbf_kind, cutoff_kind, num_basis, cutoff, p0, p1, deriv: bool, table=None):
     """Per-edge records of the wave / quad kernels in the PADDED WALK ORDER of `plan` (xeq_edge_basis_wq), once per
     evaluation and direction, cached on the plan: value records for the forward walk, value + d/dd records for the
-    reverse walk."""
+    reverse walk.  ``table`` = (atomic numbers [N], rows of the element table): the same launch also writes the table row of every
+    padded slot's gathered node and of every quad's owner (xeq_edge_basis_wq_table; plan["table_rows"][2:]) for the first block's
+    table form."""
     key = (rbf_kind, cutoff_kind, num_basis, float(cutoff), p0.data_ptr(), p0._version)
     cached = plan["records"]
-    if _basis_cache_hit(cached, vec, key) and (cached[3] is not None or not deriv):   # records with derivatives serve both requests
+    if (_basis_cache_hit(cached, vec, key) and (cached[3] is not None or not deriv)   # records with derivatives serve both requests
+            and (table is None or _table_rows_hit(plan, table))):
         return cached[2], cached[3]
     E = vec.shape[0]
     width = int(lib.load().xeq_message_wq_record_floats_for(int(num_basis)))
     basis = torch.empty((plan["pcap"], width), dtype=vec.dtype, device=vec.device)
     dbasis = torch.empty((plan["pcap"], width), dtype=vec.dtype, device=vec.device) if deriv else None
-    call("xeq_edge_basis_wq", ptr(vec), n_nodes, E, ptr(plan["qptr"]), ptr(plan["peid"]), lib.RBF_KINDS[rbf_kind],
-         lib.CUTOFF_KINDS[cutoff_kind], num_basis, float(cutoff), ptr(p0), ptr(p1), ptr(basis), ptr(dbasis), stream())
+    if table is None:
+        call("xeq_edge_basis_wq", ptr(vec), n_nodes, E, ptr(plan["qptr"]), ptr(plan["peid"]), lib.RBF_KINDS[rbf_kind],
+             lib.CUTOFF_KINDS[cutoff_kind], num_basis, float(cutoff), ptr(p0), ptr(p1), ptr(basis), ptr(dbasis), stream())
+    else:
+        z, t_rows = table[0], int(table[1])
+        assert z.dtype in (torch.int32, torch.int64) and z.is_contiguous() and z.numel() == n_nodes
+        slot_rows = torch.empty(plan["pcap"], dtype=torch.int32, device=vec.device)
+        quad_rows = torch.empty(max(plan["pcap"] // 4, 1), dtype=torch.int32, device=vec.device)
+        call("xeq_edge_basis_wq_table", ptr(vec), n_nodes, E, ptr(plan["qptr"]), ptr(plan["peid"]), lib.RBF_KINDS[rbf_kind],
+             lib.CUTOFF_KINDS[cutoff_kind], num_basis, float(cutoff), ptr(p0), ptr(p1), ptr(basis), ptr(dbasis), ptr(plan["pgath"]),
+             ptr(plan["qinfo"]), ptr(z), int(z.dtype == torch.int64), t_rows, ptr(slot_rows), ptr(quad_rows), stream())
+        plan["table_rows"] = (z, (t_rows, z._version), slot_rows, quad_rows)
     plan["records"] = (vec, key, basis, dbasis)
     return basis, dbasis
 
@@ -871,9 +890,11 @@ def message_forward(h, xhat, vec, s, x, w_rbf, b_rbf, p0, p1, graph: EdgeGraph, 
     """Launch the fused message kernel.  cfg = (rbf_kind, cutoff_kind, num_basis, cutoff, node_dim, mul[, xhat_layout]).
     Returns (s_out, x_out, saved, impl): `saved` is what message_backward needs.  ``want_backward``: a reverse pass will follow
     (wq on a symmetric list: the derivative records are then written by the same launch as the value records, the reverse kernel
-    walks this plan)."""
+    walks this plan).  cfg[7], optional: (atomic numbers, h_table, xhat0_table) -- the model's first block in its table form
+    (nn/fused.py::first_block_table, include/xeq.h: xeq_message_fwd_wq_table): h and xhat are then read from the element table."""
     rbf_kind, cutoff_kind, num_basis, cutoff, node_dim, mul = cfg[:6]
     xl = int(cfg[6]) if len(cfg) > 6 else 0  # layout of xhat / grad_xhat: 0 e3nn, 1 BT
+    table = cfg[7] if len(cfg) > 7 else None
     require_hip(h, xhat, vec, s, x, w_rbf, b_rbf, p0)
     h, xhat, vec, s, x = (t.contiguous() for t in (h, xhat, vec, s, x))
     w_rbf, b_rbf, p0 = w_rbf.contiguous(), b_rbf.contiguous(), p0.reshape(-1).contiguous()
@@ -884,11 +905,24 @@ def message_forward(h, xhat, vec, s, x, w_rbf, b_rbf, p0, p1, graph: EdgeGraph, 
     assert s.shape == (N, node_dim) and x.shape == (N, D) and w_rbf.shape == (node_dim + 2 * C, num_basis)
     s_out, x_out = torch.empty_like(s), torch.empty_like(x)
     impl = select_message_impl(h.dtype, N, E, num_basis, node_dim, mul)
+    if table is not None and impl != "wq":
+        raise RuntimeError(f"message_forward: the table form of the first block is the wq kernels', this call takes {impl}")
     if impl == "wq":
         plan = graph.wq_plan(False, _wq_edges_per_stream(E, N))
+        # the evaluation's later record launches -- the reverse plan of a list without a mirror walk, requested first by the LAST block's
+        # reverse pass -- write the table rows as well: the first block says so on the graph, the later blocks leave that alone
+        if table is not None or xl & lib.XHAT_HIGHER_L_ZERO:
+            graph.first_table = None if table is None else (table[0], table[1].shape[0])
         basis, _ = edge_basis_wq(vec, plan, N, rbf_kind, cutoff_kind, num_basis, cutoff, p0, p1,
-                                 deriv=bool(want_backward and getattr(graph, "mirror_walk", False)))
+                                 deriv=bool(want_backward and getattr(graph, "mirror_walk", False)), table=getattr(graph, "first_table", None))
         wp = wq_packed_weights(w_rbf, b_rbf, num_basis, node_dim, mul)
+        if table is not None:
+            assert xl & 1 and xl & lib.XHAT_HIGHER_L_ZERO
+            KERNEL_TIMER.launch("xeq_message_fwd_wq_table", N, E, plan["n_ranges"], ptr(plan["sq"]), ptr(plan["sn"]), ptr(plan["win"]),
+                                ptr(plan["rowptr"]), ptr(plan["table_rows"][2]), ptr(plan["qinfo"]), ptr(basis), ptr(table[1]), ptr(table[2]),
+                                table[1].shape[0], ptr(s), ptr(x), ptr(wp), None, num_basis, node_dim, mul3(mul), ptr(s_out), ptr(x_out),
+                                xl | lib.WQ_PACKED_WEIGHTS, stream(), label="xeq_message_fwd_wq_first")
+            return s_out, x_out, (h, xhat, vec, w_rbf, b_rbf, p0, p1, None, None), impl
         KERNEL_TIMER.launch("xeq_message_fwd_wq", N, E, plan["n_ranges"], ptr(plan["sq"]), ptr(plan["sn"]), ptr(plan["win"]), ptr(plan["rowptr"]),
                             ptr(plan["pgath"]), ptr(plan["qinfo"]), ptr(basis), ptr(h), ptr(xhat), ptr(s), ptr(x), ptr(wp),
                             None, num_basis, node_dim, mul3(mul), ptr(s_out), ptr(x_out), xl | lib.WQ_PACKED_WEIGHTS, stream(),
@@ -962,6 +996,7 @@ def message_backward(saved, graph: EdgeGraph, cfg, impl: str, g_s, g_x, node_gra
     h, xhat, vec, w_rbf, b_rbf, p0, p1, basis, dbasis = saved
     rbf_kind, cutoff_kind, num_basis, cutoff, node_dim, mul = cfg[:6]
     xl = int(cfg[6]) if len(cfg) > 6 else 0
+    table = cfg[7] if len(cfg) > 7 else None
     D = mul[0] + 3 * mul[1] + 5 * mul[2]
     g_s = torch.zeros((graph.n_nodes, node_dim), dtype=h.dtype, device=h.device) if g_s is None else g_s.contiguous()
     g_x = torch.zeros((graph.n_nodes, D), dtype=h.dtype, device=h.device) if g_x is None else g_x.contiguous()
@@ -972,14 +1007,24 @@ def message_backward(saved, graph: EdgeGraph, cfg, impl: str, g_s, g_x, node_gra
         N, E = graph.n_nodes, graph.n_edges
         mirror = getattr(graph, "mirror_walk", False)      # symmetric list: the forward plan and its records serve both directions
         plan = graph.wq_plan(not mirror, _wq_edges_per_stream(E, N))
-        basis, dbasis = edge_basis_wq(vec, plan, N, rbf_kind, cutoff_kind, num_basis, cutoff, p0, p1, deriv=True)
+        use_table = table is not None and skip
+        if table is not None and not use_table:
+            raise RuntimeError("message_backward: node gradients of a first block in its table form (its per-node h / xhat were not gathered)")
+        basis, dbasis = edge_basis_wq(vec, plan, N, rbf_kind, cutoff_kind, num_basis, cutoff, p0, p1, deriv=True,
+                                      table=(table[0], table[1].shape[0]) if use_table else getattr(graph, "first_table", None))
         xl_bwd = xl | (lib.WQ_MIRROR_WALK if mirror else 0) | lib.WQ_PACKED_WEIGHTS
         wp = wq_packed_weights(w_rbf, b_rbf, num_basis, node_dim, mul)
         parts = torch.empty(max(1, lib.load().xeq_message_wq_parts_floats(N, E, mul3(mul))), dtype=h.dtype, device=h.device)
-        KERNEL_TIMER.launch("xeq_message_bwd_wq", N, E, plan["n_ranges"], ptr(plan["sq"]), ptr(plan["sn"]), ptr(plan["win"]), ptr(plan["rowptr"]),
-                            ptr(plan["pgath"]), ptr(plan["qinfo"]), ptr(basis), ptr(dbasis), ptr(h), ptr(xhat), ptr(g_s), ptr(g_x),
-                            ptr(wp), None, num_basis, node_dim, mul3(mul), ptr(g_h), ptr(g_xhat), ptr(parts), xl_bwd, stream(),
-                            label="xeq_message_bwd_wq_first" if (skip and xl & lib.XHAT_HIGHER_L_ZERO) else None)
+        if use_table:
+            KERNEL_TIMER.launch("xeq_message_bwd_wq_table", N, E, plan["n_ranges"], ptr(plan["sq"]), ptr(plan["sn"]), ptr(plan["win"]),
+                                ptr(plan["rowptr"]), ptr(plan["pgath"]), ptr(plan["qinfo"]), ptr(plan["table_rows"][3]), ptr(basis), ptr(dbasis),
+                                ptr(table[1]), ptr(table[2]), table[1].shape[0], ptr(g_s), ptr(g_x), ptr(wp), None, num_basis, node_dim,
+                                mul3(mul), ptr(parts), xl_bwd, stream(), label="xeq_message_bwd_wq_first")
+        else:
+            KERNEL_TIMER.launch("xeq_message_bwd_wq", N, E, plan["n_ranges"], ptr(plan["sq"]), ptr(plan["sn"]), ptr(plan["win"]), ptr(plan["rowptr"]),
+                                ptr(plan["pgath"]), ptr(plan["qinfo"]), ptr(basis), ptr(dbasis), ptr(h), ptr(xhat), ptr(g_s), ptr(g_x),
+                                ptr(wp), None, num_basis, node_dim, mul3(mul), ptr(g_h), ptr(g_xhat), ptr(parts), xl_bwd, stream(),
+                                label="xeq_message_bwd_wq_first" if (skip and xl & lib.XHAT_HIGHER_L_ZERO) else None)
         if deferral is not None:
             g_vec = deferral.add(parts, vec, graph, plan, mirror, mul)
         else:
