@@ -10,6 +10,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "../../include/xeq.h"
 
 namespace xeq {
@@ -34,6 +36,18 @@ void note_launch(const char* name);   // counts and names the kernel launches of
       return XEQ_ERR_LAUNCH;                                                     \
     }                                                                            \
   } while (0)
+
+// More than the default 64 KB of dynamic LDS is an opt-in per kernel.  Once per process and call site:
+//   static const hipError_t err = raise_dynamic_lds({(const void*)&k_a, (const void*)&k_b}, bytes);
+// (the last failure of the list, or hipSuccess)
+inline hipError_t raise_dynamic_lds(std::initializer_list<const void*> kernels, size_t bytes) {
+  hipError_t e = hipSuccess;
+  for (const void* k : kernels) {
+    const hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (r != hipSuccess) e = r;
+  }
+  return e;
+}
 
 // dtype dispatch: BODY sees `T`
 #define XEQ_DISPATCH_FLOAT(dtype, ...)                         \
@@ -297,6 +311,17 @@ inline TileSplit tile_split(int64_t tiles, int max_split) {
   }
   if (t.split < 1) t.split = 1;
   return t;
+}
+
+// the graph of node i: the last g with ptr[g] <= i, by binary search in ptr[0 .. n_graphs] (empty graphs are skipped)
+__device__ __forceinline__ int64_t graph_of(const int64_t* __restrict__ ptr, int64_t n_graphs, int64_t i) {
+  int64_t lo = 0, hi = n_graphs;
+  while (hi - lo > 1) {
+    int64_t mid = (lo + hi) >> 1;
+    if (ptr[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  return lo;
 }
 
 // ---- wave64 helpers ---------------------------------------------------------

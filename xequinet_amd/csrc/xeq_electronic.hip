@@ -6,7 +6,7 @@
 //   s_n <- s_n + (c_n + SiLU(W_2 SiLU(W_1 c_n))) / sqrt(2)                                            k_electronic_mix
 // Design: the conventions of xeq_linear.hip.  A workgroup (4 waves) owns 32 consecutive nodes; exact-f32 v_mfma_f32_32x32x2_f32 tiles
 // with the weight fragment (xeq_mlp_pack copy) as the A operand and the row operand staged in LDS.  A node's graph is found in `ptr`
-// by binary search (xeq_graph.hip::graph_of).  The graph sums A_g of the mix pass are formed in every tile that touches the graph, by
+// by binary search (graph_of, xeq_common.h).  The graph sums A_g of the mix pass are formed in every tile that touches the graph, by
 // one wave, lane l adding the graph's entries ptr[g] + l, + 64, ... and a fixed butterfly: the order depends on the graph's own
 // atoms alone, never on the tile, the batch or the shard, and no float atomics are used.  A row's sums run in one fixed order
 // whatever the batch, so a molecule gets the same bits alone, inside a batch and inside a shard.
@@ -15,9 +15,8 @@
 
 namespace xeq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int EL_ROWS = 32;
+static_assert(EL_ROWS == PW_ROWS, "stage_rows32 / pw_chain32 work on 32-row tiles");
 
 struct ElecArgs {
   const float* S;       // [n, lds] node scalars
@@ -37,16 +36,6 @@ struct ElecArgs {
   float* out;           // [n, F]
 };
 
-__device__ __forceinline__ int64_t el_graph_of(const int64_t* __restrict__ ptr, int64_t n_graphs, int64_t i) {
-  int64_t lo = 0, hi = n_graphs;  // last g with ptr[g] <= i (empty graphs are skipped)
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ptr[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // (key_in, value_in) of a graph; KIND 0: charge [relu(t), relu(-t)], KIND 1: spin [t]
 template <int KIND>
 __device__ __forceinline__ void el_inputs(float t, float kin[2], float vin[2]) {
@@ -59,33 +48,6 @@ __device__ __forceinline__ void el_inputs(float t, float kin[2], float vin[2]) {
   }
   kin[0] = vin[0] / fmaxf(vin[0], 1.f);
   kin[1] = vin[1] / fmaxf(vin[1], 1.f);
-}
-
-// W x (+ b) for output tile t of the 32 staged rows: one k-chain per tile, weight fragments four k-groups ahead (as k_linear)
-__device__ __forceinline__ f32x16 el_tile(const float* __restrict__ Wp, int t, int K, const float* xs, int lane, bool bias) {
-  const int G = K >> 3;
-  const float4* wp = reinterpret_cast<const float4*>(Wp) + (int64_t)t * (G + 1) * 64 + lane;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float4 w0 = wp[0], w1 = wp[(1 < G ? 1 : G - 1) * 64], w2 = wp[(2 < G ? 2 : G - 1) * 64], w3 = wp[(3 < G ? 3 : G - 1) * 64];
-  for (int q = 0; q < G; ++q) {
-    const float4 wn = wp[(q + 4 < G ? q + 4 : G - 1) * 64];
-    const float4 xv = *reinterpret_cast<const float4*>(xs + 8 * q);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.x, xv.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.y, xv.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.z, xv.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.w, xv.w, acc, 0, 0, 0);
-    w0 = w1;
-    w1 = w2;
-    w2 = w3;
-    w3 = wn;
-  }
-  if (bias) {
-    const float bias_a = reinterpret_cast<const float*>(wp + (int64_t)G * 64)[0];
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, (lane >> 5) == 0 ? 1.f : 0.f, acc, 0, 0, 0);
-  }
-  return acc;
 }
 
 // attention pass: q = W_q s + b_q on the matrix cores, attn[n] = softplus(<q_n, k_g(n)> scale)
@@ -102,26 +64,19 @@ __global__ void __launch_bounds__(256) k_electronic_attn(ElecArgs a) {
   const int i = lane & 31, kh = lane >> 5;
   const int64_t row0 = (int64_t)blockIdx.x * EL_ROWS;
   const int rows_here = (int)min((int64_t)EL_ROWS, a.n - row0);
-  const int k4 = a.F >> 2;
-  for (int idx = tid; idx < EL_ROWS * k4; idx += 256) {
-    const int r = idx / k4, c4 = idx - r * k4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows_here) v = *reinterpret_cast<const float4*>(a.S + (row0 + r) * a.lds + 4 * c4);
-    *reinterpret_cast<float4*>(&Xs[r * XLD + 4 * c4]) = v;
-  }
+  stage_rows32(Xs, XLD, a.S, a.lds, row0, rows_here, a.F, tid);
   if (tid < EL_ROWS) {
     float kin[2] = {0.f, 0.f}, vin[2];
-    if (tid < rows_here) el_inputs<KIND>(a.total[el_graph_of(a.ptr, a.G, row0 + tid)], kin, vin);
+    if (tid < rows_here) el_inputs<KIND>(a.total[graph_of(a.ptr, a.G, row0 + tid)], kin, vin);
     kin_s[tid][0] = kin[0];
     kin_s[tid][1] = kin[1];
   }
   __syncthreads();
   const float* xs = &Xs[i * XLD + 4 * kh];
   for (int t = wave; t < (a.F >> 5); t += 4) {
-    const f32x16 acc = el_tile(a.Wqp, t, a.F, xs, lane, true);
+    const f32x16 acc = pw_tile_product32(a.Wqp, t, a.F, xs, lane, true);
 #pragma unroll
-    for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<float4*>(&Qs[i * XLD + 32 * t + 8 * g + 4 * kh]) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+    for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(&Qs[i * XLD + 32 * t + pw_quad_col(g, kh)]) = pw_quad(acc, g);
   }
   __syncthreads();
   // <q_n, k_g>: eight threads per row, columns sub, sub + 8, ... then a butterfly -- one fixed order per row
@@ -132,9 +87,7 @@ __global__ void __launch_bounds__(256) k_electronic_attn(ElecArgs a) {
     const float kc = KIN == 2 ? fmaf(a.Wk[2 * c + 1], k1, a.Wk[2 * c] * k0) : a.Wk[c] * k0;
     acc = fmaf(Qs[r * XLD + c], kc, acc);
   }
-  acc += __shfl_xor(acc, 4, 8);
-  acc += __shfl_xor(acc, 2, 8);
-  acc += __shfl_xor(acc, 1, 8);
+  acc = row_sum8(acc);
   if (sub == 0 && r < rows_here) {
     const float x = acc * a.scale;
     a.attn[row0 + r] = x > 20.f ? x : log1pf(expf(x));   // aten softplus (beta 1, threshold 20)
@@ -162,7 +115,7 @@ __global__ void __launch_bounds__(256) k_electronic_mix(ElecArgs a) {
     float kin[2], vin[2] = {0.f, 0.f};
     int64_t g = -1;
     if (tid < rows_here) {
-      g = el_graph_of(a.ptr, a.G, row0 + tid);
+      g = graph_of(a.ptr, a.G, row0 + tid);
       el_inputs<KIND>(a.total[g], kin, vin);
     }
     gid_s[tid] = g;
@@ -201,27 +154,26 @@ __global__ void __launch_bounds__(256) k_electronic_mix(ElecArgs a) {
   __syncthreads();
   const int nt = a.F >> 5;
   for (int t = wave; t < nt; t += 4) {
-    const f32x16 acc = el_tile(a.W1p, t, a.F, &Cs[i * XLD + 4 * kh], lane, false);
+    const f32x16 acc = pw_tile_product32(a.W1p, t, a.F, &Cs[i * XLD + 4 * kh], lane, false);
 #pragma unroll
-    for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<float4*>(&Hs[i * XLD + 32 * t + 8 * g + 4 * kh]) =
-          make_float4(lin_silu(acc[4 * g]), lin_silu(acc[4 * g + 1]), lin_silu(acc[4 * g + 2]), lin_silu(acc[4 * g + 3]));
+    for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(&Hs[i * XLD + 32 * t + pw_quad_col(g, kh)]) = silu4(pw_quad(acc, g));
   }
   __syncthreads();
   for (int t = wave; t < nt; t += 4) {
-    const f32x16 acc = el_tile(a.W2p, t, a.F, &Hs[i * XLD + 4 * kh], lane, false);
+    const f32x16 acc = pw_tile_product32(a.W2p, t, a.F, &Hs[i * XLD + 4 * kh], lane, false);
     if (i < rows_here) {
       const int64_t row = row0 + i;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const int col = 32 * t + 8 * g + 4 * kh;
+        const int col = 32 * t + pw_quad_col(g, kh);
         const float4 sv = *reinterpret_cast<const float4*>(a.S + row * a.lds + col);
         const float4 cv = *reinterpret_cast<const float4*>(&Cs[i * XLD + col]);
+        const float4 m = silu4(pw_quad(acc, g));
         float4 o;
-        o.x = sv.x + a.inv_sqrt2 * (cv.x + lin_silu(acc[4 * g]));
-        o.y = sv.y + a.inv_sqrt2 * (cv.y + lin_silu(acc[4 * g + 1]));
-        o.z = sv.z + a.inv_sqrt2 * (cv.z + lin_silu(acc[4 * g + 2]));
-        o.w = sv.w + a.inv_sqrt2 * (cv.w + lin_silu(acc[4 * g + 3]));
+        o.x = sv.x + a.inv_sqrt2 * (cv.x + m.x);
+        o.y = sv.y + a.inv_sqrt2 * (cv.y + m.y);
+        o.z = sv.z + a.inv_sqrt2 * (cv.z + m.z);
+        o.w = sv.w + a.inv_sqrt2 * (cv.w + m.w);
         *reinterpret_cast<float4*>(a.out + row * a.F + col) = o;
       }
     }
@@ -231,21 +183,6 @@ __global__ void __launch_bounds__(256) k_electronic_mix(ElecArgs a) {
 }  // namespace xeq
 
 using namespace xeq;
-
-// dynamic LDS above the default 64 KB for node_dim 256 (2 x 32 x 260 floats + the static arrays): opt in once, as xeq_nodeblock.hip does
-static hipError_t el_raise_lds() {
-  static hipError_t err = [] {
-    const void* fns[] = {reinterpret_cast<const void*>(&k_electronic_attn<0>), reinterpret_cast<const void*>(&k_electronic_attn<1>),
-                         reinterpret_cast<const void*>(&k_electronic_mix<0>), reinterpret_cast<const void*>(&k_electronic_mix<1>)};
-    hipError_t e = hipSuccess;
-    for (const void* f : fns) {
-      const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * EL_ROWS * 2 * (256 + 4)));
-      if (r != hipSuccess) e = r;
-    }
-    return e;
-  }();
-  return err;
-}
 
 extern "C" {
 
@@ -262,7 +199,12 @@ int xeq_electronic_fwd(int kind, const void* s, int64_t lds, int64_t n, int node
   XEQ_CHECK_ARG(n == 0 || (s && ptr && n_graphs >= 1 && total && wq_packed && w_k && w_v && w1_packed && w2_packed && attn && out),
                 "xeq_electronic_fwd: null buffer or no graph");
   if (n == 0) return XEQ_OK;
-  XEQ_CHECK_ARG(el_raise_lds() == hipSuccess, "xeq_electronic_fwd: cannot raise the dynamic LDS limit");
+  // dynamic LDS above the default 64 KB for node_dim 256 (2 x 32 x 260 floats + the static arrays)
+  static const hipError_t lds_err =
+      raise_dynamic_lds({reinterpret_cast<const void*>(&k_electronic_attn<0>), reinterpret_cast<const void*>(&k_electronic_attn<1>),
+                         reinterpret_cast<const void*>(&k_electronic_mix<0>), reinterpret_cast<const void*>(&k_electronic_mix<1>)},
+                        sizeof(float) * EL_ROWS * 2 * (256 + 4));
+  XEQ_CHECK_ARG(lds_err == hipSuccess, "xeq_electronic_fwd: cannot raise the dynamic LDS limit");
   ElecArgs a{(const float*)s, lds, n, node_dim, ptr, n_graphs, (const float*)total, (const float*)wq_packed, (const float*)w_k,
              (const float*)w_v, (const float*)w1_packed, (const float*)w2_packed, (float)(1.0 / std::sqrt((double)node_dim)),
              (float)(1.0 / std::sqrt(2.0)), (float*)attn, (float*)out};

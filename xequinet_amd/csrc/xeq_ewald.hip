@@ -23,8 +23,6 @@
 
 namespace xeq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int EW_CHUNK = 64;      // atoms per chunk (two 32-row tiles)
 constexpr int EW_KMAX = 192;      // k-points (six tiles of 32); the reference's periodic default [3, 3, 3] has 171
 constexpr int EW_FS = 32;         // f-slab of the phase-gradient contraction
@@ -226,7 +224,7 @@ __global__ void __launch_bounds__(256) k_ewald_apply(ApArgs a) {
 }
 
 // ---- phase gradient ----------------------------------------------------------------------------------------------------------------
-struct PgArgs {
+struct EwPhaseArgs {
   EwGeom e;
   const float* GM;    // [n, ldg] dL/dm
   const float* H;     // [n, ldh]
@@ -242,7 +240,7 @@ struct PgArgs {
   float* g_pos;       // [n, 3]
 };
 
-__global__ void __launch_bounds__(256) k_ewald_phase(PgArgs a) {
+__global__ void __launch_bounds__(256) k_ewald_phase(EwPhaseArgs a) {
   // W[kk][which][32][33]: the four filtered structure factors (S_R, S_I, P_R, P_I) of the two k-tiles in flight; R[2][64][33]: gm, h
   __shared__ float W[2][4][32 * EW_FLD];
   __shared__ float R[2][EW_CHUNK * EW_FLD];
@@ -463,8 +461,7 @@ __global__ void __launch_bounds__(256) k_ewald_combine(const float* __restrict__
     float v = sa * a[idx];
     if (b) v = fmaf(sb, b[idx], v);
     if (pre) {
-      const float p = pre[idx], sg = 1.f / (1.f + expf(-p));
-      v *= sg * (1.f + p * (1.f - sg));
+      v *= silu_grad_f(pre[idx]);
     }
     out[idx] = v;
   }
@@ -478,14 +475,11 @@ static bool ew_shape_ok(int node_dim, int n_k) { return node_dim >= 32 && node_d
 static size_t ew_sf_lds(int F) { return sizeof(float) * (size_t)(2 * EW_CHUNK * 32 + EW_CHUNK * F); }
 static size_t ew_apply_lds(int F) { return sizeof(float) * (size_t)(2 * EW_CHUNK * 33 + 2 * 32 * F); }
 
-// dynamic LDS above the default 64 KB at node_dim 256: opt in once, as xeq_electronic.hip does
+// dynamic LDS above the default 64 KB at node_dim 256
 static hipError_t ew_raise_lds() {
-  static hipError_t err = [] {
-    hipError_t r1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ewald_sf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ew_sf_lds(256));
-    hipError_t r2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ewald_apply), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ew_apply_lds(256));
-    return r1 != hipSuccess ? r1 : r2;
-  }();
-  return err;
+  static const hipError_t r1 = raise_dynamic_lds({reinterpret_cast<const void*>(&k_ewald_sf)}, ew_sf_lds(256));
+  static const hipError_t r2 = raise_dynamic_lds({reinterpret_cast<const void*>(&k_ewald_apply)}, ew_apply_lds(256));
+  return r1 != hipSuccess ? r1 : r2;
 }
 
 static int ew_geom(const char* who, EwGeom& e, const void* pos, const void* kvec, int64_t kvec_gstride, int n_k, const void* damp, const int64_t* ptr,
@@ -557,7 +551,7 @@ int xeq_ewald_apply(const void* s_r, const void* s_i, const void* kf, int64_t n,
 int xeq_ewald_phase_grad(const void* gm, int64_t ldg, const void* h, int64_t ldh, const void* s_r, const void* s_i, const void* p_r, const void* p_i,
                          const void* kf, int64_t n, int node_dim, const void* pos, const void* kvec, int64_t kvec_gstride, int n_k, const void* damp,
                          const void* ddamp, const int64_t* ptr, int64_t n_graphs, void* g_theta, void* g_damp, void* g_pos, void* stream) {
-  PgArgs a{};
+  EwPhaseArgs a{};
   const int st = ew_geom("xeq_ewald_phase_grad", a.e, pos, kvec, kvec_gstride, n_k, damp, ptr, n_graphs, n, node_dim);
   if (st != XEQ_OK) return st;
   XEQ_CHECK_ARG(ldg >= node_dim && ldh >= node_dim, "xeq_ewald_phase_grad: row strides %lld, %lld", (long long)ldg, (long long)ldh);

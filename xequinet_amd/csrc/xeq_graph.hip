@@ -168,16 +168,6 @@ template <typename T> __device__ __forceinline__ T sub_rn(T a, T b);
 template <> __device__ __forceinline__ float sub_rn<float>(float a, float b) { return __fsub_rn(a, b); }
 template <> __device__ __forceinline__ double sub_rn<double>(double a, double b) { return __dsub_rn(a, b); }
 
-__device__ __forceinline__ int64_t graph_of(const int64_t* __restrict__ ptr, int64_t n_graphs, int64_t i) {
-  int64_t lo = 0, hi = n_graphs;  // last g with ptr[g] <= i
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (ptr[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // One wave per center, lane = candidate neighbour (64 at a time in ascending index: a ballot + prefix popcount keeps the
 // (center, neighbor) order).  A thread per center walking its molecule in a dependent loop took 13 + 7 us (count + fill) for
 // the 335 k distance checks of QM9-1024 on a third of the CUs.
@@ -984,8 +974,7 @@ int xeq_rowptr_from_degrees(const int32_t* deg, int64_t n_nodes, int64_t capacit
     xeq::set_error("xeq_rowptr_from_degrees: %lld nodes (the one-workgroup form takes <= %lld)", (long long)n_nodes, (long long)SCAN_WG_MAX_ITEMS);
     return XEQ_ERR_UNSUPPORTED;
   }
-  static const bool attr_ok = hipFuncSetAttribute((const void*)xeq::k_rowptr_from_degrees, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)wg_scan_lds_bytes(SCAN_WG_MAX_ITEMS)) == hipSuccess;
+  static const bool attr_ok = xeq::raise_dynamic_lds({(const void*)xeq::k_rowptr_from_degrees}, wg_scan_lds_bytes(SCAN_WG_MAX_ITEMS)) == hipSuccess;
   XEQ_CHECK_ARG(attr_ok, "xeq_rowptr_from_degrees: cannot reserve %zu bytes of LDS", wg_scan_lds_bytes(SCAN_WG_MAX_ITEMS));
   hipLaunchKernelGGL(xeq::k_rowptr_from_degrees, dim3(1), dim3(SCAN_WG_THREADS), wg_scan_lds_bytes(n_nodes), (hipStream_t)stream, deg, n_nodes,
                      capacity, rowptr, count, running_total);

@@ -27,9 +27,8 @@
 
 namespace xeq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int HP_ROWS = 32;
+static_assert(HP_ROWS == PW_ROWS, "stage_rows32 / pw_chain32 work on 32-row tiles");
 
 struct PolarArgs {
   const float* S;        // [n, lds]
@@ -55,33 +54,6 @@ __host__ __device__ inline size_t hp_lds_floats(int F, int mul0, int mul2, int H
   return (size_t)HP_ROWS * ((F + 4) + (mul0 + 4) + 5 * (mul2 + 4) + (Hp + 4) + (H0p + 4) + 5 * (H2p + 4));
 }
 
-// W x (+ bias group) for output tile t of 32 staged rows (xs: this lane's row, + 4 kh); one k-chain, fragments four k-groups ahead
-__device__ __forceinline__ f32x16 hp_tile(const float* __restrict__ Wp, int t, int K, const float* xs, int lane, bool bias) {
-  const int G = K >> 3;
-  const float4* wp = reinterpret_cast<const float4*>(Wp) + (int64_t)t * (G + 1) * 64 + lane;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float4 w0 = wp[0], w1 = wp[(1 < G ? 1 : G - 1) * 64], w2 = wp[(2 < G ? 2 : G - 1) * 64], w3 = wp[(3 < G ? 3 : G - 1) * 64];
-  for (int q = 0; q < G; ++q) {
-    const float4 wn = wp[(q + 4 < G ? q + 4 : G - 1) * 64];
-    const float4 xv = *reinterpret_cast<const float4*>(xs + 8 * q);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.x, xv.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.y, xv.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.z, xv.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.w, xv.w, acc, 0, 0, 0);
-    w0 = w1;
-    w1 = w2;
-    w2 = w3;
-    w3 = wn;
-  }
-  if (bias) {
-    const float bias_a = reinterpret_cast<const float*>(wp + (int64_t)G * 64)[0];
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, (lane >> 5) == 0 ? 1.f : 0.f, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
 __device__ __forceinline__ float hp_gate(float sq, float eps) { return 1.f / (1.f + expf(-(sqrtf(sq + eps * eps) - eps))); }
 
 __global__ void __launch_bounds__(256) k_head_polar_nodes(PolarArgs a) {
@@ -99,32 +71,17 @@ __global__ void __launch_bounds__(256) k_head_polar_nodes(PolarArgs a) {
   const int64_t row0 = (int64_t)blockIdx.x * HP_ROWS;
   const int rows_here = (int)min((int64_t)HP_ROWS, a.n - row0);
   // stage s and the 0e block (16-byte loads; rows past n as zeros)
-  const int s4 = a.F >> 2, x4 = a.mul0 >> 2;
-  for (int idx = tid; idx < HP_ROWS * s4; idx += 256) {
-    const int r = idx / s4, c4 = idx - r * s4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows_here) v = *reinterpret_cast<const float4*>(a.S + (row0 + r) * a.lds + 4 * c4);
-    *reinterpret_cast<float4*>(&Ss[r * SLD + 4 * c4]) = v;
-  }
-  for (int idx = tid; idx < HP_ROWS * x4; idx += 256) {
-    const int r = idx / x4, c4 = idx - r * x4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows_here) v = *reinterpret_cast<const float4*>(a.X + (row0 + r) * a.ldx + 4 * c4);
-    *reinterpret_cast<float4*>(&X0s[r * X0LD + 4 * c4]) = v;
-  }
+  stage_rows32(Ss, SLD, a.S, a.lds, row0, rows_here, a.F, tid);
+  stage_rows32(X0s, X0LD, a.X, a.ldx, row0, rows_here, a.mul0, tid);
   // the 2e block [mul2][5] of a node, transposed to five rows of mul2 channels
-  const int e4 = (5 * a.mul2) >> 2;
-  for (int idx = tid; idx < HP_ROWS * e4; idx += 256) {
-    const int r = idx / e4, c4 = idx - r * e4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows_here) v = *reinterpret_cast<const float4*>(a.X + (row0 + r) * a.ldx + a.off2 + 4 * c4);
+  for_rows32(a.X + a.off2, a.ldx, row0, rows_here, 5 * a.mul2, tid, nullptr, [&](int r, int c4, const float4& v) {
     const float* pv = reinterpret_cast<const float*>(&v);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int e = 4 * c4 + j, u = e / 5, m = e - 5 * u;
       X2s[(m * HP_ROWS + r) * X2LD + u] = pv[j];
     }
-  }
+  });
   __syncthreads();
   const int nt_s = a.Hp >> 5, nt_0 = a.H0p >> 5, nt_2 = a.H2p >> 5;
   const int jobs = nt_s + nt_0 + 5 * nt_2;
@@ -135,24 +92,24 @@ __global__ void __launch_bounds__(256) k_head_polar_nodes(PolarArgs a) {
     bool silu = false;
     if (job < nt_s) {
       t = job;
-      acc = hp_tile(a.Ws1p, t, a.F, &Ss[i * SLD + 4 * kh], lane, true);
+      acc = pw_tile_product32(a.Ws1p, t, a.F, &Ss[i * SLD + 4 * kh], lane, true);
       dst = &Hs[i * HLD];
       silu = true;
     } else if (job < nt_s + nt_0) {
       t = job - nt_s;
-      acc = hp_tile(a.W0p, t, a.mul0, &X0s[i * X0LD + 4 * kh], lane, true);
+      acc = pw_tile_product32(a.W0p, t, a.mul0, &X0s[i * X0LD + 4 * kh], lane, true);
       dst = &H0s[i * H0LD];
     } else {
       const int j2 = job - nt_s - nt_0, m = j2 / nt_2;
       t = j2 - m * nt_2;
-      acc = hp_tile(a.W2p, t, a.mul2, &X2s[(m * HP_ROWS + i) * X2LD + 4 * kh], lane, false);
+      acc = pw_tile_product32(a.W2p, t, a.mul2, &X2s[(m * HP_ROWS + i) * X2LD + 4 * kh], lane, false);
       dst = &H2s[(m * HP_ROWS + i) * H2LD];
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      float4 v = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
-      if (silu) v = make_float4(lin_silu(v.x), lin_silu(v.y), lin_silu(v.z), lin_silu(v.w));
-      *reinterpret_cast<float4*>(dst + 32 * t + 8 * g + 4 * kh) = v;
+      float4 v = pw_quad(acc, g);
+      if (silu) v = silu4(v);
+      *reinterpret_cast<float4*>(dst + 32 * t + pw_quad_col(g, kh)) = v;
     }
   }
   __syncthreads();
@@ -179,14 +136,11 @@ __global__ void __launch_bounds__(256) k_head_polar_nodes(PolarArgs a) {
 #pragma unroll
     for (int m = 0; m < 5; ++m) t2[m] = fmaf(wg, h[m], t2[m]);
   }
+  a0 = row_sum8(a0);
+  a2 = row_sum8(a2);
+  t0 = row_sum8(t0);
 #pragma unroll
-  for (int o = 4; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o, 8);
-    a2 += __shfl_xor(a2, o, 8);
-    t0 += __shfl_xor(t0, o, 8);
-#pragma unroll
-    for (int m = 0; m < 5; ++m) t2[m] += __shfl_xor(t2[m], o, 8);
-  }
+  for (int m = 0; m < 5; ++m) t2[m] = row_sum8(t2[m]);
   if (sub == 0 && r < rows_here) {
     a0 += a.bs2[0];
     a2 += a.bs2[1];
@@ -273,13 +227,6 @@ static bool hp_shape_ok(int node_dim, int mul0, int mul2, int hidden_dim, int hi
   return sizeof(float) * hp_lds_floats(node_dim, mul0, mul2, hp_pad32(hidden_dim), hp_pad32(hid0), hp_pad32(hid2)) <= 160 * 1024;
 }
 
-// dynamic LDS above the default 64 KB: opt in once, as xeq_electronic.hip does
-static hipError_t hp_raise_lds() {
-  static hipError_t err =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_polar_nodes), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  return err;
-}
-
 extern "C" {
 
 int xeq_head_polar_supported(int dtype, int node_dim, int mul0, int mul2, int hidden_dim, int hid0, int hid2) {
@@ -298,7 +245,8 @@ int xeq_head_polar_nodes(const void* s, int64_t lds, const void* x, int64_t ldx,
   XEQ_CHECK_ARG(n == 0 || (s && x && ws1_packed && w0_packed && w2_packed && ws2 && bs2 && wb && bb && t), "xeq_head_polar_nodes: null buffer");
   XEQ_CHECK_ARG(((uintptr_t)s % 16 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)t % 16 == 0), "xeq_head_polar_nodes: buffers must be 16-byte aligned");
   if (n == 0) return XEQ_OK;
-  XEQ_CHECK_ARG(hp_raise_lds() == hipSuccess, "xeq_head_polar_nodes: cannot raise the dynamic LDS limit");
+  static const hipError_t lds_err = raise_dynamic_lds({reinterpret_cast<const void*>(&k_head_polar_nodes)}, 160 * 1024);
+  XEQ_CHECK_ARG(lds_err == hipSuccess, "xeq_head_polar_nodes: cannot raise the dynamic LDS limit");
   PolarArgs a{(const float*)s, (const float*)x, lds, ldx, n, node_dim, mul0, mul2, off2, hidden_dim, hid0, hid2, hp_pad32(hidden_dim), hp_pad32(hid0),
               hp_pad32(hid2), (const float*)ws1_packed, (const float*)w0_packed, (const float*)w2_packed, (const float*)ws2, (const float*)bs2,
               (const float*)wb, (const float*)bb, (float)eps, (float*)t};

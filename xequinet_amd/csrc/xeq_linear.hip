@@ -9,7 +9,7 @@
 //
 // Design: the MLP kernels' conventions (xeq_mlp.hip).  A workgroup (4 waves) owns 32 consecutive rows; exact-f32
 // v_mfma_f32_32x32x2_f32 tiles D[column][row] with the WEIGHT fragment as the A operand, read global -> register from the copy
-// xeq_mlp_pack makes (packed[tile][k-group][lane][4], the bias as one more k-group against a row of ones); the row operand is
+// xeq_mlp_pack makes (the format and its readers: xeq_packed_w.h); the row operand is
 // staged once in LDS (K <= 256) with 16-byte loads, optionally gathered through a row index (the embedding table lookup).
 // Wave w computes output tiles w, w + 4.  These are small products (K <= 224, at most 8 output tiles): one k-chain per tile.
 #include "xeq_common.h"
@@ -17,9 +17,8 @@
 
 namespace xeq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int LIN_ROWS = 32;
+static_assert(LIN_ROWS == PW_ROWS, "stage_rows32 / pw_chain32 work on 32-row tiles");
 
 
 __global__ void __launch_bounds__(256) k_linear(LinArgs a) {
@@ -29,53 +28,24 @@ __global__ void __launch_bounds__(256) k_linear(LinArgs a) {
   const int i = lane & 31, kh = lane >> 5;
   const int64_t row0 = (int64_t)blockIdx.x * LIN_ROWS;
   const int rows_here = (int)min((int64_t)LIN_ROWS, a.n - row0);
-  const int k4 = a.K >> 2;   // float4 per row
-  for (int idx = tid; idx < LIN_ROWS * k4; idx += 256) {
-    const int r = idx / k4, c4 = idx - r * k4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows_here) {
-      int64_t src = row0 + r;
-      if (a.row_index) src = a.row_index[src];
-      v = *reinterpret_cast<const float4*>(a.X + src * a.ldx + 4 * c4);
-    }
-    *reinterpret_cast<float4*>(&Xs[r * LIN_XLD + 4 * c4]) = v;
-  }
+  stage_rows32(Xs, LIN_XLD, a.X, a.ldx, row0, rows_here, a.K, tid, a.row_index);
   __syncthreads();
   const int G = a.K >> 3, nt = a.n_out >> 5;
   const float one_k0 = kh == 0 ? 1.f : 0.f;
   const float* xs = &Xs[i * LIN_XLD + 4 * kh];
   const bool row_ok = i < rows_here;
   for (int t = wave; t < nt; t += 4) {
-    const float4* wp = reinterpret_cast<const float4*>(a.Wp) + (int64_t)t * (G + 1) * 64 + lane;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // weight fragments four k-groups ahead of their MFMAs (an L2 round trip is ~500 cycles, a group's four MFMAs 256)
-    float4 w0 = wp[0], w1 = wp[(1 < G ? 1 : G - 1) * 64], w2 = wp[(2 < G ? 2 : G - 1) * 64], w3 = wp[(3 < G ? 3 : G - 1) * 64];
-    for (int q = 0; q < G; ++q) {
-      const float4 wn = wp[(q + 4 < G ? q + 4 : G - 1) * 64];
-      const float4 xv = *reinterpret_cast<const float4*>(xs + 8 * q);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.x, xv.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.y, xv.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.z, xv.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.w, xv.w, acc, 0, 0, 0);
-      w0 = w1;
-      w1 = w2;
-      w2 = w3;
-      w3 = wn;
-    }
-    if (a.has_bias) {
-      const float bias_a = reinterpret_cast<const float*>(wp + (int64_t)G * 64)[0];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, one_k0, acc, 0, 0, 0);
-    }
+    const float4* wp = pw_tile32(a.Wp, t, G) + lane;
+    f32x16 acc = pw_chain32(wp, xs, 0, G);
+    if (a.has_bias) acc = pw_bias_step32(acc, wp, G, one_k0);
     if (row_ok) {
       const int64_t row = row0 + i;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const int col = 32 * t + 8 * g + 4 * kh;
-        float4 v = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        const int col = 32 * t + pw_quad_col(g, kh);
+        float4 v = pw_quad(acc, g);
         if (a.pre) *reinterpret_cast<float4*>(a.pre + row * a.n_out + col) = v;
-        if (a.act == 1) v = make_float4(lin_silu(v.x), lin_silu(v.y), lin_silu(v.z), lin_silu(v.w));
+        if (a.act == 1) v = silu4(v);
         *reinterpret_cast<float4*>(a.Y + row * a.ldy + col) = v;
       }
     }
@@ -120,12 +90,8 @@ __global__ void k_head_bwd_hidden(const float* __restrict__ pre, int64_t n, int 
   const float ga = g_atomic ? g_atomic[node] : 1.f;
   const float4 p = *reinterpret_cast<const float4*>(pre + node * H + c);
   const float4 w = *reinterpret_cast<const float4*>(w2 + c);
-  auto dsilu = [](float x) {   // aten silu_backward: sig (1 + x (1 - sig))
-    const float sig = 1.f / (1.f + expf(-x));
-    return sig * (1.f + x * (1.f - sig));
-  };
   *reinterpret_cast<float4*>(g_hidden + node * H + c) =
-      make_float4(ga * w.x * dsilu(p.x), ga * w.y * dsilu(p.y), ga * w.z * dsilu(p.z), ga * w.w * dsilu(p.w));
+      make_float4(ga * w.x * silu_grad_f(p.x), ga * w.y * silu_grad_f(p.y), ga * w.z * silu_grad_f(p.z), ga * w.w * silu_grad_f(p.w));
 }
 
 // ---- the whole energy head of a force evaluation in one launch (round 5) -------------------------------------------------------------
@@ -157,13 +123,7 @@ __global__ void __launch_bounds__(256) k_head_fused(HeadArgs a) {
   const int i = lane & 31, kh = lane >> 5;
   const int64_t row0 = (int64_t)blockIdx.x * LIN_ROWS;
   const int rows_here = (int)min((int64_t)LIN_ROWS, a.n - row0);
-  const int k4 = a.F >> 2;
-  for (int idx = tid; idx < LIN_ROWS * k4; idx += 256) {
-    const int r = idx / k4, c4 = idx - r * k4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < rows_here) v = *reinterpret_cast<const float4*>(a.S + (row0 + r) * a.lds + 4 * c4);
-    *reinterpret_cast<float4*>(&Xs[r * XLD + 4 * c4]) = v;
-  }
+  stage_rows32(Xs, XLD, a.S, a.lds, row0, rows_here, a.F, tid);
   __syncthreads();
   const float one_k0 = kh == 0 ? 1.f : 0.f;
   {  // hidden layer: a wave takes (output tile t of 32 hidden columns, half kp of the k range) when the tiles leave waves idle (the
@@ -173,32 +133,12 @@ __global__ void __launch_bounds__(256) k_head_fused(HeadArgs a) {
     for (int item = wave; item < nt * ksplit; item += 4) {
       const int t = item % nt, kp = item / nt;
       const int q0 = kp * (G / ksplit), q1 = q0 + G / ksplit;
-      const float4* wp = reinterpret_cast<const float4*>(a.W1p) + (int64_t)t * (G + 1) * 64 + lane;
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      auto wq = [&](int q) { return wp[(q < q1 ? q : q1 - 1) * 64]; };
-      float4 w0 = wq(q0), w1 = wq(q0 + 1), w2r = wq(q0 + 2), w3 = wq(q0 + 3);
-      for (int q = q0; q < q1; ++q) {
-        const float4 wn = wq(q + 4);
-        const float4 xv = *reinterpret_cast<const float4*>(xs + 8 * q);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.x, xv.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.y, xv.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.z, xv.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.w, xv.w, acc, 0, 0, 0);
-        w0 = w1;
-        w1 = w2r;
-        w2r = w3;
-        w3 = wn;
-      }
-      if (kp == 0) {   // the bias rides with the first half
-        const float bias_a = reinterpret_cast<const float*>(wp + (int64_t)G * 64)[0];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, one_k0, acc, 0, 0, 0);
-      }
+      const float4* wp = pw_tile32(a.W1p, t, G) + lane;
+      f32x16 acc = pw_chain32(wp, xs, q0, q1);
+      if (kp == 0) acc = pw_bias_step32(acc, wp, G, one_k0);   // the bias rides with the first half
       float* dst = kp == 0 ? Es : Gs;   // partial pre-activations
 #pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<float4*>(&dst[i * HLD + 32 * t + 8 * g + 4 * kh]) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+      for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(&dst[i * HLD + 32 * t + pw_quad_col(g, kh)]) = pw_quad(acc, g);
     }
     __syncthreads();
     // pre = half 0 (+ half 1); e = SiLU(pre) w2 -> Es, w2 SiLU'(pre) -> Gs, in place: a thread per four columns
@@ -217,8 +157,8 @@ __global__ void __launch_bounds__(256) k_head_fused(HeadArgs a) {
       for (int c = 0; c < 4; ++c) {
         const float x = xq[c];
         const float sig = 1.f / (1.f + expf(-x));
-        e[c] = (x * sig) * wq4[c];                               // SiLU(pre) w2
-        gh[c] = wq4[c] * (sig * (1.f + x * (1.f - sig)));        // w2 SiLU'(pre)  (aten silu_backward's form)
+        e[c] = (x * sig) * wq4[c];                               // SiLU(pre) w2 as x sig (not silu_f's quotient: other bits)
+        gh[c] = wq4[c] * silu_grad_f(x);                         // w2 SiLU'(pre), the same sigmoid
       }
       *reinterpret_cast<float4*>(&Es[r * HLD + col]) = make_float4(e[0], e[1], e[2], e[3]);
       *reinterpret_cast<float4*>(&Gs[r * HLD + col]) = make_float4(gh[0], gh[1], gh[2], gh[3]);
@@ -229,37 +169,18 @@ __global__ void __launch_bounds__(256) k_head_fused(HeadArgs a) {
     const int r = tid >> 3, sub = tid & 7;
     float acc = 0.f;
     for (int c = sub; c < a.H; c += 8) acc += Es[r * HLD + c];
-    acc += __shfl_xor(acc, 4, 8);
-    acc += __shfl_xor(acc, 2, 8);
-    acc += __shfl_xor(acc, 1, 8);
+    acc = row_sum8(acc);
     if (sub == 0 && r < rows_here) a.atomic[row0 + r] = acc + (a.b2 ? a.b2[0] : 0.f);
   }
   if (a.J) {  // J = (w2 . SiLU'(pre)) W1: output tile t (32 input columns) per wave, K = H
     const int G = a.H >> 3, nt = a.F >> 5;
     const float* gs = &Gs[i * HLD + 4 * kh];
     for (int t = wave; t < nt; t += 4) {
-      const float4* wp = reinterpret_cast<const float4*>(a.W1tp) + (int64_t)t * (G + 1) * 64 + lane;
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      float4 w0 = wp[0], w1 = wp[(1 < G ? 1 : G - 1) * 64], w2r = wp[(2 < G ? 2 : G - 1) * 64], w3 = wp[(3 < G ? 3 : G - 1) * 64];
-      for (int q = 0; q < G; ++q) {
-        const float4 wn = wp[(q + 4 < G ? q + 4 : G - 1) * 64];
-        const float4 xv = *reinterpret_cast<const float4*>(gs + 8 * q);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.x, xv.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.y, xv.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.z, xv.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0.w, xv.w, acc, 0, 0, 0);
-        w0 = w1;
-        w1 = w2r;
-        w2r = w3;
-        w3 = wn;
-      }
+      const f32x16 acc = pw_chain32(pw_tile32(a.W1tp, t, G) + lane, gs, 0, G);
       if (i < rows_here) {
         const int64_t row = row0 + i;
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(a.J + row * a.F + 32 * t + 8 * g + 4 * kh) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(a.J + row * a.F + 32 * t + pw_quad_col(g, kh)) = pw_quad(acc, g);
       }
     }
   }
@@ -460,7 +381,11 @@ int xeq_head_fwd(const void* s, int64_t lds, int64_t n, int node_dim, int hidden
   if (n == 0) return XEQ_OK;
   HeadArgs a{(const float*)s, lds, n, node_dim, hidden_dim, (const float*)w1_packed, (const float*)w1t_packed, (const float*)w2, (const float*)b2,
              (float*)atomic, (float*)jac};
-  const size_t shmem = sizeof(float) * (size_t)LIN_ROWS * ((node_dim + 4) + 2 * (hidden_dim + 4));
+  const auto head_lds = [](int F, int H) { return sizeof(float) * (size_t)LIN_ROWS * ((F + 4) + 2 * (H + 4)); };
+  // above the default 64 KB of dynamic LDS as soon as F + 2 H > 500; sized for the widest head xeq_head_supported admits
+  static const hipError_t lds_err = raise_dynamic_lds({reinterpret_cast<const void*>(&k_head_fused)}, head_lds(LIN_KMAX, 256));
+  XEQ_CHECK_ARG(lds_err == hipSuccess, "xeq_head_fwd: cannot raise the dynamic LDS limit");
+  const size_t shmem = head_lds(node_dim, hidden_dim);
   hipLaunchKernelGGL(k_head_fused, dim3((unsigned)((n + LIN_ROWS - 1) / LIN_ROWS)), dim3(256), shmem, (hipStream_t)stream, a);
   XEQ_CHECK_LAUNCH("xeq_head_fwd");
   return XEQ_OK;

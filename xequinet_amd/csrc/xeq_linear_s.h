@@ -1,11 +1,10 @@
 // The few-row form of the single linear layers (k_linear_s, csrc/xeq_linear.hip) as a device function: also one half of the launches
 // that run two independent products of a node block side by side (csrc/xeq_mlp.hip: k_mlp2_linear_s).
 #pragma once
-#include "xeq_common.h"
+#include "xeq_packed_w.h"
 
 namespace xeq {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int LIN_KMAX = 256;
 constexpr int LIN_XLD = LIN_KMAX + 4;
 constexpr int LIN_S_ROWS = 16;
@@ -21,8 +20,6 @@ struct LinArgs {
   float* Y;                 // [n, ldy]
   int64_t ldy;
 };
-
-__device__ __forceinline__ float lin_silu(float x) { return x / (1.f + expf(-x)); }
 
 // ---- the same product for FEW rows (MD-sized systems: 21 .. a few thousand atoms) ---------------------------------------------------------
 // An exact-f32 matrix instruction is a chain of fused multiply-adds in k order, whatever its tile shape: v_mfma_f32_16x16x4_f32 fed the
@@ -67,28 +64,28 @@ __device__ __forceinline__ void linear_s_body(const LinArgs& a, float* Xs, int b
     xo[j] = in ? r * LIN_XLD + 4 * c4 : -1;
   }
   __builtin_amdgcn_sched_barrier(0);
-  const float4* wp = reinterpret_cast<const float4*>(a.Wp) + (int64_t)(t16 >> 1) * (G + 1) * 64 + 16 * (t16 & 1) + i + 32 * kh;
+  const float4* wp = pw_tile16(a.Wp, t16, G, i, kh);
   float wa[LIN_KMAX / 8][2];
 #pragma unroll
   for (int q = 0; q < LIN_KMAX / 8; ++q) {
     const float4 v = wp[(q < G ? q : G - 1) * 64];
-    wa[q][0] = sel ? v.y : v.x;
-    wa[q][1] = sel ? v.w : v.z;
+    wa[q][0] = pw_pick0(sel, v);
+    wa[q][1] = pw_pick1(sel, v);
   }
-  const float bias_a = (a.has_bias && kq == 0) ? reinterpret_cast<const float*>(wp + (int64_t)G * 64)[0] : 0.f;
+  const float bias_a = (a.has_bias && kq == 0) ? pw_bias(wp, G) : 0.f;
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int j = 0; j < XN; ++j)
     if (xo[j] >= 0) *reinterpret_cast<float4*>(&Xs[xo[j]]) = xr[j];
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // orders LDS traffic only: the weights stay in flight
+  lds_barrier();   // orders LDS traffic only: the weights stay in flight
   const float* xs = &Xs[i * LIN_XLD + 4 * kh];
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int q = 0; q < LIN_KMAX / 8; ++q)
     if (q < G) {
       const float4 xv = *reinterpret_cast<const float4*>(xs + 8 * q);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[q][0], sel ? xv.y : xv.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[q][1], sel ? xv.w : xv.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[q][0], pw_pick0(sel, xv), acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[q][1], pw_pick1(sel, xv), acc, 0, 0, 0);
     }
   if (a.has_bias) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(bias_a, kq == 0 ? 1.f : 0.f, acc, 0, 0, 0);
   if (i < rows_here && tile_ok) {
@@ -96,7 +93,7 @@ __device__ __forceinline__ void linear_s_body(const LinArgs& a, float* Xs, int b
     const int col = 16 * t16 + 4 * kq;
     float4 v = make_float4(acc[0], acc[1], acc[2], acc[3]);
     if (a.pre) *reinterpret_cast<float4*>(a.pre + row * a.n_out + col) = v;
-    if (a.act == 1) v = make_float4(lin_silu(v.x), lin_silu(v.y), lin_silu(v.z), lin_silu(v.w));
+    if (a.act == 1) v = silu4(v);
     *reinterpret_cast<float4*>(a.Y + row * a.ldy + col) = v;
   }
 }

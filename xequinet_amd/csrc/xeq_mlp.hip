@@ -10,10 +10,8 @@
 // wide.  Wave w computes hidden columns [32 w, 32 w + 32) in stage 1 and the output tiles w, w + 4, ... in stage 2.  The row
 // operands (shared by the waves) come from LDS: the X tile is staged in 64-column chunks (double buffered), the hidden tile is
 // written once by its producers.  The weight operands are private to a wave, so they go global -> register directly from a PACKED
-// copy in fragment order, packed[tile][k-group][lane][4] = W[32 tile + (lane & 31)][8 group + 4 (lane >> 5) + j], one coalesced
-// 16-byte load per lane for four MFMA steps (the k order inside a group of 8 is a permutation, applied to both operands); the
-// bias is one more k-group, multiplied by a row of ones.  Results do not depend on the number of rows: every row sees the same
-// summation order in every form.
+// copy in fragment order (xeq_packed_w.h: the format, this file's k_mlp_pack as its writer, and the readers every kernel shares).
+// Results do not depend on the number of rows: every row sees the same summation order in every form.
 #include <type_traits>
 
 #include "xeq_common.h"
@@ -21,10 +19,14 @@
 
 namespace xeq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define MLP_SB() __builtin_amdgcn_sched_barrier(0)
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains this wave's global stores and prefetches (vmcnt(0))
-#define MLP_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#ifdef XEQ_SILU_FAST   // development switch (xeq_packed_w.h: silu_exp), this file's kernels only
+constexpr bool MLP_FAST = true;
+#else
+constexpr bool MLP_FAST = false;
+#endif
+__device__ __forceinline__ float mlp_silu(float x) { return silu_f<MLP_FAST>(x); }
+__device__ __forceinline__ float mlp_silu_grad(float x) { return silu_grad_f<MLP_FAST>(x); }
 
 constexpr int MLP_ROWS = 32;
 constexpr int MLP_H = 128;        // hidden width (node_dim of the default and of every shipped configuration)
@@ -48,35 +50,17 @@ struct MlpArgs {
 __global__ void k_mlp_pack(const float* __restrict__ W, const float* __restrict__ bias, int n_out, int k_in, int transposed,
                            float* __restrict__ out) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one float4 of the packed buffer
-  const int groups = k_in / 8 + 1;                                      // + the bias group
-  const int64_t total = (int64_t)(n_out / 32) * groups * 64;
-  if (idx >= total) return;
-  const int lane = (int)(idx & 63);
-  const int64_t tq = idx >> 6;
-  const int q = (int)(tq % groups), t = (int)(tq / groups);
-  const int n = 32 * t + (lane & 31), k0 = 8 * q + 4 * (lane >> 5);
+  if (idx >= pw_float4s(n_out, k_in / 8)) return;
+  const PwSlot p = pw_slot(idx, k_in / 8);
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (q == groups - 1) {
-    if (bias && (lane >> 5) == 0) v.x = bias[n];
+  if (p.bias) {
+    if (bias && p.bias_lane) v.x = bias[p.n];
   } else {
     float* pv = reinterpret_cast<float*>(&v);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) pv[j] = transposed ? W[(int64_t)(k0 + j) * n_out + n] : W[(int64_t)n * k_in + k0 + j];
+    for (int j = 0; j < 4; ++j) pv[j] = transposed ? W[(int64_t)(p.k0 + j) * n_out + p.n] : W[(int64_t)p.n * k_in + p.k0 + j];
   }
   reinterpret_cast<float4*>(out)[idx] = v;
-}
-
-// exp: the library's expf (<= 1 ulp, what the reference's SiLU evaluates); -DXEQ_SILU_FAST: the hardware exp2 path (~2 ulp + the
-// rounding of x log2 e), kept as a development switch for the accuracy / time comparison of DESIGN section 2
-#ifdef XEQ_SILU_FAST
-__device__ __forceinline__ float silu_exp(float x) { return __expf(x); }
-#else
-__device__ __forceinline__ float silu_exp(float x) { return expf(x); }
-#endif
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + silu_exp(-x)); }
-__device__ __forceinline__ float silu_grad_f(float x) {  // aten silu_backward: sig (1 + x (1 - sig))
-  const float sig = 1.f / (1.f + silu_exp(-x));
-  return sig * (1.f + x * (1.f - sig));
 }
 
 __device__ __forceinline__ float4 keep4(bool ok, const float4& v) {
@@ -143,7 +127,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     *reinterpret_cast<float4*>(&Xs[c & 1][sr * MLP_XLD + sc]) = keep4(r0ok && cok, v0);
     *reinterpret_cast<float4*>(&Xs[c & 1][(sr + 16) * MLP_XLD + sc]) = keep4(r1ok && cok, v1);
   };
-  const float4* w1 = reinterpret_cast<const float4*>(a.W1p) + (int64_t)wave * (g1 + 1) * 64;   // wave-uniform base, lane offset in the load
+  const float4* w1 = pw_tile32(a.W1p, wave, g1);   // wave-uniform base, lane offset in the load
   auto fetch_w = [&](float4 (&b)[8], int g0) {   // four k-groups from g0 on
 #pragma unroll
     for (int q = 0; q < 4; ++q) b[q] = w1[min(g0 + q, g1 - 1) * 64 + lane];   // past K1: any finite weight, the staged rows are zero there
@@ -161,7 +145,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
   // so it arrives with the weight stream instead of as a separate load that later waits behind this wave's stores
   const float one_k0 = kh == 0 ? 1.f : 0.f;
   float bias_a = 0.f;
-  if (a.bias1) bias_a = reinterpret_cast<const float*>(w1 + (int64_t)g1 * 64 + lane)[0];
+  if (a.bias1) bias_a = pw_bias(w1, g1, lane);
   float4 pv[4];   // reverse: silu'(pre) needs the forward's pre-activations of this tile; fetched under the chunk loop
   if (REVERSE) {
 #pragma unroll
@@ -171,7 +155,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
   fetch(0, x0, x1);
   fetch_w(B0, 0);
   stash(0, x0, x1);
-  MLP_LDS_BARRIER();
+  lds_barrier();
 #ifdef XEQ_MLP_STAMPS
   unsigned long long cp1_, rp1_; MLP_STAMP(cp1_, rp1_);
 #endif
@@ -198,7 +182,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     half(B1, 1);
     MLP_SB();
     if (more) stash(c + 1, x0, x1);
-    MLP_LDS_BARRIER();
+    lds_barrier();
   }
   if (a.bias1) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, one_k0, acc0, 0, 0, 0);
 #ifdef XEQ_MLP_STAMPS
@@ -235,13 +219,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     float4 v;
     if (!REVERSE) {
       if (row_ok && part_ == 0) *reinterpret_cast<float4*>(preb + ((unsigned)i * MLP_H + (unsigned)col)) = t;
-      v = make_float4(silu_f(t.x), silu_f(t.y), silu_f(t.z), silu_f(t.w));
+      v = make_float4(mlp_silu(t.x), mlp_silu(t.y), mlp_silu(t.z), mlp_silu(t.w));
     } else {
-      v = make_float4(t.x * silu_grad_f(pv[g].x), t.y * silu_grad_f(pv[g].y), t.z * silu_grad_f(pv[g].z), t.w * silu_grad_f(pv[g].w));
+      v = make_float4(t.x * mlp_silu_grad(pv[g].x), t.y * mlp_silu_grad(pv[g].y), t.z * mlp_silu_grad(pv[g].z), t.w * mlp_silu_grad(pv[g].w));
     }
     *reinterpret_cast<float4*>(&Ts[i * MLP_TLD + col]) = v;
   }
-  MLP_LDS_BARRIER();
+  lds_barrier();
 #ifdef XEQ_MLP_STAMPS
   unsigned long long cp3_, cx_, cy_, rx_, st2c_ = 0; MLP_STAMP(cp3_, rx_);
 #endif
@@ -257,8 +241,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     }
     float bias_ya = 0.f, bias_yb = 0.f;
     if (a.bias2) {
-      bias_ya = reinterpret_cast<const float*>(w2 + ((int64_t)tt * (G2 + 1) + G2) * 64 + lane)[0];
-      if (TWO) bias_yb = reinterpret_cast<const float*>(w2 + ((int64_t)(tt + 4) * (G2 + 1) + G2) * 64 + lane)[0];
+      bias_ya = pw_bias(pw_tile32(a.W2p, tt, G2), G2, lane);
+      if (TWO) bias_yb = pw_bias(pw_tile32(a.W2p, tt + 4, G2), G2, lane);
     }
 #ifdef XEQ_MLP_STAMPS
     MLP_STAMP(cy_, rx_);
@@ -398,7 +382,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
 #pragma unroll
     for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(&Xs[c & 1][(sr + 16 * k) * MLP_XLD + sc]) = keep4(rok[k] && cok, v[k]);
   };
-  const float4* w1 = reinterpret_cast<const float4*>(a.W1p) + (int64_t)wave * (g1 + 1) * 64;
+  const float4* w1 = pw_tile32(a.W1p, wave, g1);
   auto fetch_w = [&](float4 (&b)[4], int g0) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) b[q] = w1[min(g0 + q, g1 - 1) * 64 + lane];
@@ -410,7 +394,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
   }
   const float one_k0 = kh == 0 ? 1.f : 0.f;
   float bias_a = 0.f;
-  if (a.bias1) bias_a = reinterpret_cast<const float*>(w1 + (int64_t)g1 * 64 + lane)[0];
+  if (a.bias1) bias_a = pw_bias(w1, g1, lane);
   float4 pv[2][4];
   if (REVERSE) {
 #pragma unroll
@@ -423,7 +407,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
   fetch(0, xv);
   fetch_w(B0, 0);
   stash(0, xv);
-  MLP_LDS_BARRIER();
+  lds_barrier();
   for (int c = 0; c < n_chunks; ++c) {
     const bool more = c + 1 < n_chunks;
     if (more) fetch(c + 1, xv);
@@ -452,7 +436,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
     half(B1, 1);
     MLP_SB();
     if (more) stash(c + 1, xv);
-    MLP_LDS_BARRIER();
+    lds_barrier();
   }
   if (a.bias1) {
     acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, one_k0, acc[0][0], 0, 0, 0);
@@ -480,15 +464,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
       float4 v;
       if (!REVERSE) {
         if (row < rows_here && part_ == 0) *reinterpret_cast<float4*>(preb + ((unsigned)row * MLP_H + (unsigned)col)) = t;
-        v = make_float4(silu_f(t.x), silu_f(t.y), silu_f(t.z), silu_f(t.w));
+        v = make_float4(mlp_silu(t.x), mlp_silu(t.y), mlp_silu(t.z), mlp_silu(t.w));
       } else {
-        v = make_float4(t.x * silu_grad_f(pv[rt][g].x), t.y * silu_grad_f(pv[rt][g].y), t.z * silu_grad_f(pv[rt][g].z),
-                        t.w * silu_grad_f(pv[rt][g].w));
+        v = make_float4(t.x * mlp_silu_grad(pv[rt][g].x), t.y * mlp_silu_grad(pv[rt][g].y), t.z * mlp_silu_grad(pv[rt][g].z),
+                        t.w * mlp_silu_grad(pv[rt][g].w));
       }
       *reinterpret_cast<float4*>(&Ts[row * MLP_TLD + col]) = v;
     }
   }
-  MLP_LDS_BARRIER();
+  lds_barrier();
   const float* ts = &Ts[i * MLP_TLD + 4 * kh];
   for (; t0 < nt2; t0 += 4 * parts) {
     const int tn = t0 + 4 * parts;
@@ -499,7 +483,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
       yb[r] = 0.f;
     }
     float bias_y = 0.f;
-    if (a.bias2) bias_y = reinterpret_cast<const float*>(w2 + ((int64_t)t0 * (G2 + 1) + G2) * 64 + lane)[0];
+    if (a.bias2) bias_y = pw_bias(pw_tile32(a.W2p, t0, G2), G2, lane);
     auto quarter = [&](const float4 (&b)[4], int qq) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -598,7 +582,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
   for (int p = 0; 4 * p < nh; ++p) {
     const bool mine = wave + 4 * p < nh;               // wave-uniform
     const int ht = mine ? wave + 4 * p : 0;            // (a tile that exists, for the addresses of a wave without one)
-    const float4* w1 = reinterpret_cast<const float4*>(a.W1p) + (int64_t)ht * (g1 + 1) * 64;
+    const float4* w1 = pw_tile32(a.W1p, ht, g1);
     auto fetch_w = [&](float4 (&b)[4], int g0) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) b[q] = w1[min(g0 + q, g1 - 1) * 64 + lane];   // past K1: any finite weight, the staged rows are zero there
@@ -610,7 +594,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
       acc1[r] = 0.f;
     }
     float bias_a = 0.f;
-    if (a.bias1) bias_a = reinterpret_cast<const float*>(w1 + (int64_t)g1 * 64 + lane)[0];
+    if (a.bias1) bias_a = pw_bias(w1, g1, lane);
     float4 pv[4];
     if (REVERSE) {
 #pragma unroll
@@ -619,7 +603,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     fetch(0, x0, x1);
     fetch_w(B0, 0);
     stash(0, x0, x1);   // (every wave is past the last chunk of the pass before: the barrier that ends its loop)
-    MLP_LDS_BARRIER();
+    lds_barrier();
     for (int c = 0; c < n_chunks; ++c) {
       const bool more = c + 1 < n_chunks;
       if (more) fetch(c + 1, x0, x1);
@@ -643,7 +627,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
       if (mine) half(B1, 1);
       MLP_SB();
       if (more) stash(c + 1, x0, x1);
-      MLP_LDS_BARRIER();
+      lds_barrier();
     }
     if (mine) {
       if (a.bias1) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_a, one_k0, acc0, 0, 0, 0);
@@ -655,9 +639,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
         float4 v;
         if (!REVERSE) {
           if (row_ok && part_ == 0) *reinterpret_cast<float4*>(preb + ((unsigned)i * (unsigned)H + (unsigned)col)) = t;
-          v = make_float4(silu_f(t.x), silu_f(t.y), silu_f(t.z), silu_f(t.w));
+          v = make_float4(mlp_silu(t.x), mlp_silu(t.y), mlp_silu(t.z), mlp_silu(t.w));
         } else {
-          v = make_float4(t.x * silu_grad_f(pv[g].x), t.y * silu_grad_f(pv[g].y), t.z * silu_grad_f(pv[g].z), t.w * silu_grad_f(pv[g].w));
+          v = make_float4(t.x * mlp_silu_grad(pv[g].x), t.y * mlp_silu_grad(pv[g].y), t.z * mlp_silu_grad(pv[g].z), t.w * mlp_silu_grad(pv[g].w));
         }
         *reinterpret_cast<float4*>(&Ts[i * TLD + col]) = v;
       }
@@ -676,14 +660,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
   };
   int t0 = wave + 4 * part;
   fetch_q(B0, t0, 0);
-  MLP_LDS_BARRIER();   // the hidden tile is whole
+  lds_barrier();   // the hidden tile is whole
   const float* ts = &Ts[i * TLD + 4 * kh];
   for (; t0 < nt2; t0 += 4 * parts) {
     f32x16 ya;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ya[r] = 0.f;
     float bias_ya = 0.f;
-    if (a.bias2) bias_ya = reinterpret_cast<const float*>(w2 + ((int64_t)t0 * (G2 + 1) + G2) * 64 + lane)[0];
+    // (the group counted from the buffer's start, not pw_tile32 + G2 as in k_mlp2: with G2 a run-time value that form costs this
+    // kernel 13 instructions of address arithmetic)
+    if (a.bias2) bias_ya = pw_bias(w2, (int64_t)t0 * (G2 + 1) + G2, lane);
     for (int qq = 0; qq < nh; ++qq) {
       const bool last = qq + 1 == nh;
       fetch_q(B1, last ? t0 + 4 * parts : t0, last ? 0 : qq + 1);
@@ -753,8 +739,7 @@ __device__ __forceinline__ void mlp2_s_body(const MlpArgs& a, int parts, float* 
   float4 pv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (REVERSE) pv = *reinterpret_cast<const float4*>(a.pre + (row0 + ic) * MLP_H + 16 * wave + 4 * kq);
   MLP_SB();
-  const float2* w1 = reinterpret_cast<const float2*>(reinterpret_cast<const float4*>(a.W1p) + (int64_t)(wave >> 1) * (g1 + 1) * 64 +
-                                                     16 * (wave & 1) + i + 32 * kh) + sel;
+  const float2* w1 = reinterpret_cast<const float2*>(pw_tile16(a.W1p, wave, g1, i, kh)) + sel;
   float2 eo[G1];
 #pragma unroll
   for (int q = 0; q < G1; ++q) eo[q] = w1[(q < g1 ? q : g1 - 1) * 128];
@@ -765,21 +750,21 @@ __device__ __forceinline__ void mlp2_s_body(const MlpArgs& a, int parts, float* 
   float bias2_a = 0.f;
   auto fetch2 = [&](int t) {
     const int tc = t < nt16 ? t : 0;
-    const float4* w2 = reinterpret_cast<const float4*>(a.W2p) + (int64_t)(tc >> 1) * (G2 + 1) * 64 + 16 * (tc & 1) + i + 32 * kh;
+    const float4* w2 = pw_tile16(a.W2p, tc, G2, i, kh);
 #pragma unroll
     for (int q = 0; q < G2; ++q) {
       const float4 v = w2[q * 64];
-      wb[q][0] = sel ? v.y : v.x;
-      wb[q][1] = sel ? v.w : v.z;
+      wb[q][0] = pw_pick0(sel, v);
+      wb[q][1] = pw_pick1(sel, v);
     }
-    bias2_a = (a.bias2 && kq == 0) ? reinterpret_cast<const float*>(w2 + (int64_t)G2 * 64)[0] : 0.f;
+    bias2_a = (a.bias2 && kq == 0) ? pw_bias(w2, G2) : 0.f;
   };
   MLP_SB();
   // the rows into LDS (the weights stay in flight across the barrier: it orders LDS traffic only)
 #pragma unroll
   for (int j = 0; j < NCH; ++j)
     if (xo[j] >= 0) *reinterpret_cast<float4*>(&Xs[xo[j]]) = xr[j];
-  MLP_LDS_BARRIER();
+  lds_barrier();
   fetch2(t2);   // (behind the stage-1 weights in any case; here the rows' registers are free again)
   MLP_SB();
   // ---- stage 1: hidden columns [16 wave, 16 wave + 16)
@@ -799,13 +784,13 @@ __device__ __forceinline__ void mlp2_s_body(const MlpArgs& a, int parts, float* 
     float4 v;
     if (!REVERSE) {
       if (i < rows_here && part == 0) *reinterpret_cast<float4*>(a.pre + (row0 + i) * MLP_H + col) = t;
-      v = make_float4(silu_f(t.x), silu_f(t.y), silu_f(t.z), silu_f(t.w));
+      v = make_float4(mlp_silu(t.x), mlp_silu(t.y), mlp_silu(t.z), mlp_silu(t.w));
     } else {
-      v = make_float4(t.x * silu_grad_f(pv.x), t.y * silu_grad_f(pv.y), t.z * silu_grad_f(pv.z), t.w * silu_grad_f(pv.w));
+      v = make_float4(t.x * mlp_silu_grad(pv.x), t.y * mlp_silu_grad(pv.y), t.z * mlp_silu_grad(pv.z), t.w * mlp_silu_grad(pv.w));
     }
     *reinterpret_cast<float4*>(&Ts[i * MLP_TLD + col]) = v;
   }
-  MLP_LDS_BARRIER();
+  lds_barrier();
   // ---- stage 2: output tiles 8 part + wave, + 8 parts, ...
   const float* ts = &Ts[i * MLP_TLD + 4 * kh];
   for (; t2 < nt16; t2 += 8 * parts) {
@@ -813,8 +798,8 @@ __device__ __forceinline__ void mlp2_s_body(const MlpArgs& a, int parts, float* 
 #pragma unroll
     for (int q = 0; q < G2; ++q) {
       const float4 tv = *reinterpret_cast<const float4*>(ts + 8 * q);
-      y = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[q][0], sel ? tv.y : tv.x, y, 0, 0, 0);
-      y = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[q][1], sel ? tv.w : tv.z, y, 0, 0, 0);
+      y = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[q][0], pw_pick0(sel, tv), y, 0, 0, 0);
+      y = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[q][1], pw_pick1(sel, tv), y, 0, 0, 0);
     }
     if (a.bias2) y = __builtin_amdgcn_mfma_f32_16x16x4f32(bias2_a, kq == 0 ? 1.f : 0.f, y, 0, 0, 0);
     if (i < rows_here) *reinterpret_cast<float4*>(a.Y + (row0 + i) * a.ldy + 16 * t2 + 4 * kq) = make_float4(y[0], y[1], y[2], y[3]);

@@ -14,12 +14,10 @@
 // the wave's LDS slice (one slot per lane and channel block), are reduced over the four edge groups of the C layout at the end and
 // stored once per node with the residual added: no atomics, a fixed summation order.  rbf[E, B], fcut[E] and the unit vectors
 // never exist in memory.
-#include "xeq_common.h"
+#include "xeq_packed_w.h"
 
 namespace xeq {
 namespace painn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CHUNK = 16;        // edges per staged chunk (rows of one matrix-core tile)
 constexpr int KPAD = 32;         // padded basis width: num_basis + 1 (bias column) <= 32

@@ -14,11 +14,9 @@
 //     time with 16-byte loads through wave-private LDS, the center's gradient rows stay in registers while the center stays;
 //   * the four waves of a workgroup take quarters of the workgroup's edge range and add their tiles up through LDS: one part per
 //     workgroup, parts[part][row][64], summed by the caller in a fixed order.
-#include "xeq_common.h"
+#include "xeq_packed_w.h"
 
 namespace xeq {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // T row: [f rho_k (B) | f | f d rho_k/d p0 (B) | f d rho_k/d p1 (B, gaussian only) | pad to 4 | Y_1 (3) Y_2 (5) | pad to 32]
 struct PbLayout {

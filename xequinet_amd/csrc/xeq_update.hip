@@ -12,16 +12,13 @@
 // channels for every m with exact-f32 v_mfma_f32_32x32x2_f32 (weights as the A operand: a lane holds four consecutive
 // channels of one node per register quad, so every store is 16 bytes), from weights packed in fragment order
 // (xeq_mlp_pack of [W_U | W_V] / sqrt(mul), the l = 0 biases as one more k-group).
-#include <mutex>
 #include <type_traits>
 
-#include "xeq_common.h"
+#include "xeq_packed_w.h"
 
 namespace xeq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define UV_SB() __builtin_amdgcn_sched_barrier(0)
-#define UV_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 constexpr int UV_ROWS = 32;
 constexpr int UV_MAXX4 = 16;   // D <= 512 (8 lanes x 16 float4 per node row)
@@ -65,8 +62,8 @@ __device__ __forceinline__ void uv_job(const UvFwdArgs& a, const float* xh, int 
   const int base = l == 0 ? 0 : (l == 1 ? m0 : m0 + 3 * m1);   // flat offset of the block in a node row (xhat tile, BT)
   const int goff = l == 0 ? 0 : (l == 1 ? m0 : m0 + m1);       // first gate channel of the block
   const bool row_ok = i < rows_here;
-  const float4* wU = reinterpret_cast<const float4*>(a.wp[l]) + (int64_t)t * (G + 1) * 64;
-  const float4* wV = reinterpret_cast<const float4*>(a.wp[l]) + (int64_t)(mul / 32 + t) * (G + 1) * 64;
+  const float4* wU = pw_tile32(a.wp[l], t, G);
+  const float4* wV = pw_tile32(a.wp[l], mul / 32 + t, G);
   float* __restrict__ uvb = a.uv + a.n * 2 * base + row0 * d * 2 * mul;   // BT pair buffer, this tile's first row of block l
   // weights: G <= 8 groups stay in registers for every m of the job; G = 16 streams them in quarters of 4 groups, each
   // fetched one quarter ahead into the other half of the register buffer
@@ -91,8 +88,8 @@ __device__ __forceinline__ void uv_job(const UvFwdArgs& a, const float* xh, int 
   const float one_k0 = kh == 0 ? 1.f : 0.f;
   float bu = 0.f, bv = 0.f;
   if (bias) {
-    bu = reinterpret_cast<const float*>(wU + G * 64 + lane)[0];
-    bv = reinterpret_cast<const float*>(wV + G * 64 + lane)[0];
+    bu = pw_bias(wU, G, lane);
+    bv = pw_bias(wV, G, lane);
   }
   f32x16 pacc, vacc;
 #pragma unroll
@@ -213,7 +210,7 @@ __device__ __forceinline__ void uv_phase_a(const UvFwdArgs& a, float* xh, const 
       xv[k] = make_float4(v ? t.x : 0.f, v ? t.y : 0.f, v ? t.z : 0.f, v ? t.w : 0.f);
     }
     after_loads();
-    UV_LDS_BARRIER();   // the staged parameters (the row loads above stay in flight across it)
+    lds_barrier();   // the staged parameters (the row loads above stay in flight across it)
     if (!live) return;
     float mean = 0.f, rstd = 1.f, mean0 = 0.f, r = 1.f;
     if (do_norm) {
@@ -326,7 +323,7 @@ __global__ void __launch_bounds__(256) k_update_uv_fwd(UvFwdArgs a) {
   }
 
   uv_phase_a<M0, M1, M2, FF, NORM, UV_ROWS, 256>(a, xh, lnw, lnb, eqw, eqb, row0, rows_here, part_, tid);
-  UV_LDS_BARRIER();
+  lds_barrier();
 
   // ---- phase B: the o3.Linear pair on the matrix cores, v and p from the accumulators
   // split tiles (TileSplit, xeq_common.h): `parts` workgroups share the node tile, each repeats phase A and takes every parts-th job
@@ -346,7 +343,6 @@ __global__ void __launch_bounds__(256) k_update_uv_fwd(UvFwdArgs a) {
 // the chain per wave, four times the waves.  Phase A as above (threads 0..127 of both workgroups: within 256 registers, which 16 waves
 // in one workgroup are not); phase B: job = (l, 16 output channels), one per wave.
 constexpr int UVS_ROWS = 16, UVS_NT = 512, UVS_PARTS = 2;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct UvJobS {   // one job of the few-node forward form: (l, 16 output channels) and its weight fragments, requested whole
   int l, t16, mul;
@@ -360,22 +356,21 @@ __device__ __forceinline__ void uv_job_s_load(const UvFwdArgs& a, int jj, int m0
   j.mul = j.l == 0 ? m0 : (j.l == 1 ? m1 : m2);
   const int i = lane & 15, kq = lane >> 4, kh = kq & 1, G = j.mul >> 3;
   const bool sel = (kq >> 1) != 0;
-  const int lo = 16 * (j.t16 & 1) + i + 32 * kh;   // this lane's slot in a packed 32-column tile
-  const float4* wU = reinterpret_cast<const float4*>(a.wp[j.l]) + (int64_t)(j.t16 >> 1) * (G + 1) * 64 + lo;
-  const float4* wV = reinterpret_cast<const float4*>(a.wp[j.l]) + (int64_t)(j.mul / 32 + (j.t16 >> 1)) * (G + 1) * 64 + lo;
+  const float4* wU = pw_tile16(a.wp[j.l], j.t16, G, i, kh);
+  const float4* wV = pw_half16(pw_tile32(a.wp[j.l], j.mul / 32 + (j.t16 >> 1), G), j.t16, i, kh);
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     const int qc = q < G ? q : G - 1;
     const float4 u = wU[qc * 64], v = wV[qc * 64];
-    j.wu[q][0] = sel ? u.y : u.x;
-    j.wu[q][1] = sel ? u.w : u.z;
-    j.wv[q][0] = sel ? v.y : v.x;
-    j.wv[q][1] = sel ? v.w : v.z;
+    j.wu[q][0] = pw_pick0(sel, u);
+    j.wu[q][1] = pw_pick1(sel, u);
+    j.wv[q][0] = pw_pick0(sel, v);
+    j.wv[q][1] = pw_pick1(sel, v);
   }
   j.bu = j.bv = 0.f;
   if (j.l == 0 && a.has_bias && kq == 0) {
-    j.bu = reinterpret_cast<const float*>(wU + G * 64)[0];
-    j.bv = reinterpret_cast<const float*>(wV + G * 64)[0];
+    j.bu = pw_bias(wU, G);
+    j.bv = pw_bias(wV, G);
   }
 }
 
@@ -399,7 +394,7 @@ __device__ __forceinline__ void uv_job_s_run(const UvFwdArgs& a, const UvJobS& j
 #pragma unroll
     for (int q = 0; q < G; ++q) {
       const float4 xv = *reinterpret_cast<const float4*>(xs + 8 * q);
-      const float b0 = sel ? xv.y : xv.x, b1 = sel ? xv.w : xv.z;
+      const float b0 = pw_pick0(sel, xv), b1 = pw_pick1(sel, xv);
       U = __builtin_amdgcn_mfma_f32_16x16x4f32(j.wu[q][0], b0, U, 0, 0, 0);
       V = __builtin_amdgcn_mfma_f32_16x16x4f32(j.wv[q][0], b0, V, 0, 0, 0);
       U = __builtin_amdgcn_mfma_f32_16x16x4f32(j.wu[q][1], b1, U, 0, 0, 0);
@@ -460,7 +455,7 @@ __global__ void __launch_bounds__(UVS_NT) k_update_uv_fwd_s(UvFwdArgs a) {
     if (jj < n_jobs) uv_job_s_load(a, jj, m0, m1, m2, lane, job);
   };
   uv_phase_a<M0, M1, M2, FF, NORM, UVS_ROWS, UVS_NT>(a, xh, lnw, lnb, eqw, eqb, row0, rows_here, part, tid, load_first);
-  UV_LDS_BARRIER();
+  lds_barrier();
   for (; jj < n_jobs; jj += UVS_PARTS * UVS_NT / 64) {
     if (job.mul == 128) uv_job_s_run<16>(a, job, xh, XLD, row0, rows_here, lane);
     else if (job.mul == 64) uv_job_s_run<8>(a, job, xh, XLD, row0, rows_here, lane);
@@ -553,7 +548,7 @@ __device__ __forceinline__ void uvb_contract(const UvBwdArgs& a, const float* bf
   const int T = mul >> 5, d = 2 * l + 1, G = 4 * GQ;
   for (int job = part + parts * wave; job < d * T; job += 4 * parts) {
     const int m = job / T, t = job - m * T;
-    const float4* wT = reinterpret_cast<const float4*>(a.wt[l]) + (int64_t)t * (G + 1) * 64;
+    const float4* wT = pw_tile32(a.wt[l], t, G);
     const float* bs = bf + i * BLD + m * 2 * mul + 4 * kh;
     f32x16 acc0, acc1;
 #pragma unroll
@@ -625,27 +620,27 @@ __global__ void __launch_bounds__(256) k_update_uv_bwd(UvBwdArgs a) {
   // ---- phases 1 and 2, block by block
   if (m0 > 0) {
     uvb_form<1>(a, bf, BLD, m0, 0, 0, F, D, row0, rows_here, tid);
-    UV_LDS_BARRIER();
+    lds_barrier();
     if (m0 == 128) uvb_contract<8, FUSE>(a, bf, BLD, gt, XLD, 0, m0, 0, wave, lane, row0, rows_here, part, parts);
     else if (m0 == 64) uvb_contract<4, FUSE>(a, bf, BLD, gt, XLD, 0, m0, 0, wave, lane, row0, rows_here, part, parts);
     else uvb_contract<2, FUSE>(a, bf, BLD, gt, XLD, 0, m0, 0, wave, lane, row0, rows_here, part, parts);
-    UV_LDS_BARRIER();
+    lds_barrier();
   }
   if (m1 > 0) {
     uvb_form<3>(a, bf, BLD, m1, m0, m0, F, D, row0, rows_here, tid);
-    UV_LDS_BARRIER();
+    lds_barrier();
     if (m1 == 128) uvb_contract<8, FUSE>(a, bf, BLD, gt, XLD, 1, m1, m0, wave, lane, row0, rows_here, part, parts);
     else if (m1 == 64) uvb_contract<4, FUSE>(a, bf, BLD, gt, XLD, 1, m1, m0, wave, lane, row0, rows_here, part, parts);
     else uvb_contract<2, FUSE>(a, bf, BLD, gt, XLD, 1, m1, m0, wave, lane, row0, rows_here, part, parts);
-    UV_LDS_BARRIER();
+    lds_barrier();
   }
   if (m2 > 0) {
     uvb_form<5>(a, bf, BLD, m2, m0 + 3 * m1, m0 + m1, F, D, row0, rows_here, tid);
-    UV_LDS_BARRIER();
+    lds_barrier();
     if (m2 == 128) uvb_contract<8, FUSE>(a, bf, BLD, gt, XLD, 2, m2, m0 + 3 * m1, wave, lane, row0, rows_here, part, parts);
     else if (m2 == 64) uvb_contract<4, FUSE>(a, bf, BLD, gt, XLD, 2, m2, m0 + 3 * m1, wave, lane, row0, rows_here, part, parts);
     else uvb_contract<2, FUSE>(a, bf, BLD, gt, XLD, 2, m2, m0 + 3 * m1, wave, lane, row0, rows_here, part, parts);
-    UV_LDS_BARRIER();
+    lds_barrier();
   }
   if (!FUSE) return;
   // ---- phase 3: reverse of both norms, 8 lanes per node
@@ -781,8 +776,7 @@ __device__ __forceinline__ void uvb_job_s_load(const UvBwdArgs& a, int jj, int m
   j.m = r / T;
   j.t16 = r - j.m * T;
   const int i = lane & 15, kq = lane >> 4, kh = kq & 1, sel = kq >> 1, G = j.mul >> 2;   // k = 2 mul: G groups of 8
-  const float2* wT = reinterpret_cast<const float2*>(reinterpret_cast<const float4*>(a.wt[j.l]) + (int64_t)(j.t16 >> 1) * (G + 1) * 64 +
-                                                     16 * (j.t16 & 1) + i + 32 * kh) + sel;
+  const float2* wT = reinterpret_cast<const float2*>(pw_tile16(a.wt[j.l], j.t16, G, i, kh)) + sel;
 #pragma unroll
   for (int q = 0; q < 32; ++q) j.w[q] = wT[(q < G ? q : G - 1) * 128];
 }
@@ -832,7 +826,7 @@ __global__ void __launch_bounds__(UVS_NT) k_update_uv_bwd_s(UvBwdArgs a) {
   if (m0 > 0) uvb_form<1, UVS_ROWS, UVS_NT>(a, bf0, BLD0, m0, 0, 0, F, D, row0, rows_here, tid);
   if (m1 > 0) uvb_form<3, UVS_ROWS, UVS_NT>(a, bf1, BLD1, m1, m0, m0, F, D, row0, rows_here, tid);
   if (m2 > 0) uvb_form<5, UVS_ROWS, UVS_NT>(a, bf2, BLD2, m2, m0 + 3 * m1, m0 + m1, F, D, row0, rows_here, tid);
-  UV_LDS_BARRIER();
+  lds_barrier();
   auto run = [&](const UvbJobS& j) {
     const float* bf = j.l == 0 ? bf0 : (j.l == 1 ? bf1 : bf2);
     const int BLD = j.l == 0 ? BLD0 : (j.l == 1 ? BLD1 : BLD2);
@@ -953,15 +947,9 @@ int xeq_update_uv_bwd(const float* uv_bt, const float* g_p, const float* g_cat, 
   const int64_t tiles = (n + UV_ROWS - 1) / UV_ROWS;
   b.ts = tile_split(tiles, fuse ? 1 : min_jobs);
   const dim3 grid(b.ts.grid(tiles));
-  static std::once_flag attr_once;   // more than 64 KB of dynamic LDS (fused form): opt in once per process
-  static hipError_t attr_err = hipSuccess;
-  std::call_once(attr_once, [] {
-    const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_uv_bwd<128, 64, 32, 128, 1, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_uv_bwd<-1, -1, -1, -1, -1, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_err = e0 != hipSuccess ? e0 : e1;
-  });
+  // more than 64 KB of dynamic LDS (fused form)
+  static const hipError_t attr_err = raise_dynamic_lds({reinterpret_cast<const void*>(&k_update_uv_bwd<128, 64, 32, 128, 1, true>),
+                                                        reinterpret_cast<const void*>(&k_update_uv_bwd<-1, -1, -1, -1, -1, true>)}, 160 * 1024);
   XEQ_CHECK_ARG(attr_err == hipSuccess, "xeq_update_uv_bwd: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr_err));
   const bool dflt = mul[0] == 128 && mul[1] == 64 && mul[2] == 32 && node_dim == 128 && do_norm;
   const size_t lds_s = (size_t)UVS_ROWS * (2 * mul[0] + 6 * mul[1] + 10 * mul[2] + 12) * sizeof(float);
