@@ -155,12 +155,17 @@ def from_bt(flat, mul, n):
     return torch.cat(parts, dim=1)
 
 
-def message_ref(mul, h, xhat, vec, s, x, W, b, params, edge_index, rbf_kind, cutoff_kind, cutoff):
-    """(s_out, x_out) of one message block; ``params``: the basis parameters as the oracle's functions take them (p0[, p1])"""
-    irreps, C, F = irreps_of(mul), sum(mul), mul[0]
+def message_ref(mul, h, xhat, vec, s, x, W, b, params, edge_index, rbf_kind, cutoff_kind, cutoff, y00=None):
+    """(s_out, x_out) of one message block; ``params``: the basis parameters as the oracle's functions take them (p0[, p1]).  The scalar
+    width is what h holds beyond its 2 C gate columns (the wq kernels: mul[0]).  ``y00``: the value of the l = 0 harmonic when it is not
+    1 (tests/sb_message_cases.py: XEQ_SB_Y0_ZERO)."""
+    irreps, C = irreps_of(mul), sum(mul)
+    F = h.shape[1] - 2 * C
     center, nbr = edge_index[0].long(), edge_index[1].long()
     rbf, fcut, _ = pc.radial_ref(vec, rbf_kind, cutoff_kind, params, cutoff)
     rsh = orc.spherical_harmonics(irreps, vec[:, [1, 2, 0]])
+    if y00 is not None:
+        rsh = torch.cat([rsh[:, :mul[0]] * y00, rsh[:, mul[0]:]], dim=1)
     filt = torch.nn.functional.linear(rbf, W, b) * fcut
     g_state, g_edge, m_s = torch.split(h.index_select(0, nbr) * filt, [C, C, F], dim=-1)
     m_x = orc.elementwise_tp(irreps, xhat.index_select(0, nbr), g_state) + orc.elementwise_tp(irreps, rsh, g_edge)

@@ -159,7 +159,8 @@ __device__ __forceinline__ void lane_y(const T* __restrict__ tail, int l, T (&y)
 // 0.72 to 0.57 ms; 5 waves (96 VGPRs) spills the weight rows and is 3-5x slower.
 // STAGE (few nodes: an MD-sized system, where the launch is ONE segment's latency chain): the records of a group of <= 64 edges are
 // copied to LDS with one round of vector loads before the group's arithmetic, instead of one scalar-memory round trip per edge batch in
-// front of its filters; the filters then read their record operands from LDS (broadcast reads).  The same arithmetic, the same bits.
+// front of its filters; the filters then read their record operands from LDS (broadcast reads).  The same arithmetic, the same bits
+// as the general instantiation of the same basis count (sb_stage_form says where; tests/test_gpu_sb_message.py compares every count).
 template <typename T>
 __device__ __forceinline__ void sb_stage_records(const T* __restrict__ src, int EW, int32_t eid_v, int cnt, T* __restrict__ dst, int lane, int wave) {
   constexpr int LPE = sizeof(T) == 4 ? 16 : 32, EPI = 64 / LPE;   // lanes per edge (16 bytes each), edges per wave instruction
@@ -907,6 +908,26 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   }
 }
 
+// The invariant of every instantiation: filt() reads rec[0 .. MAXB) whatever num_basis is (zero weights above it), so
+//   roundup(B, 4) <= MAXB   the weights cover the zero-padded record head, and
+//   MAXB <= eb_width(B)     no filter operand lies outside the edge's own record [rec, rec + EW).
+// The second one matters for 0 x what lies behind the record: the next edge's record in global memory (finite), but in the few-row
+// form's LDS copy the slot behind a group's last edge was not staged by that group and holds whatever LDS held -- 0 x NaN is a NaN.
+// sb_maxb is the rule of the dispatch macros below, stated once more for the host-side check (sb_check).
+constexpr int SB_STAGE_MAXB = 20;   // the one instantiation of the few-row (STAGE) form
+static int sb_maxb(int num_basis) { return num_basis <= 8 ? 8 : num_basis <= 16 ? 16 : num_basis <= 20 ? 20 : 32; }
+static bool sb_maxb_fits(int num_basis, int maxb) { return eb_bp(num_basis) <= maxb && maxb <= eb_width(num_basis); }
+// The few-row form: f32, few nodes (an MD-sized system: at most two workgroups per CU), 9 .. 20 basis functions.
+//   num_basis <= 4: records of 16 floats, shorter than the staged instantiation's 20 operands (the invariant above).
+//   num_basis 5 .. 8: the row count must pick a form, never a result, and here it did.  Measured on MI355X
+//     (tests/test_gpu_sb_message.py): x_out of <float, 20, STAGE> and of the general <float, 8> differ in their last bits -- which
+//     product of `xv * gs + y * ge` is fused into the FMA is the compiler's choice per instantiation (-ffp-contract=fast), and the
+//     8-operand kernel comes out the other way round than the 16-, 20- and staged 20-operand ones, which agree bit for bit.
+// Both ranges take the general <float, 8> form at every row count.
+static bool sb_stage_form(int dtype, int64_t n_nodes, int num_basis) {
+  return dtype == XEQ_F32 && num_basis > 8 && sb_maxb_fits(num_basis, SB_STAGE_MAXB) && n_nodes <= 512 && n_nodes <= xeq_small_rows();
+}
+
 // what the scalar-broadcast kernels cover: at most 256 channels per kind (one thread each) and 32-bit row offsets
 static bool sb_fits(int64_t n_nodes, int64_t n_edges, int num_basis, int node_dim, const int32_t mul[3]) {
   if (num_basis < 1 || num_basis > 32 || mul[0] < 0 || mul[1] < 0 || mul[2] < 0) return false;
@@ -934,6 +955,8 @@ static int sb_check(const char* who, int64_t n_nodes, int64_t n_edges, int num_b
                 "%s: tensors too large for 32-bit row offsets (shard the batch)", who);
   a.n_nodes = n_nodes;
   a.n_edges = n_edges;
+  XEQ_CHECK_ARG(sb_maxb_fits(num_basis, sb_maxb(num_basis)), "%s: no instantiation keeps its filter operands inside a record of %d floats",
+                who, eb_width(num_basis));
   a.chunk = n_nodes >= 32 * 1024 ? 32 : (int)(n_nodes / 1024 > 0 ? n_nodes / 1024 : 1);
   return XEQ_OK;
 }
@@ -942,7 +965,7 @@ static int sb_check(const char* who, int64_t n_nodes, int64_t n_edges, int num_b
 
 using namespace xeq;
 
-// MAXB must cover the zero-padded record head BP = roundup(B, 4)
+// MAXB: sb_maxb(num_basis), see the invariant stated there
 #define XEQ_SB_DISPATCH(KERNEL, UF, UD, ...)                                                                        \
   do {                                                                                                              \
     if (dtype == XEQ_F32) {                                                                                         \
@@ -1002,10 +1025,10 @@ int xeq_message_fwd_sb(int dtype, int64_t n_nodes, int64_t n_edges, const int32_
   a.xl = xhat_layout & 1;   // the XEQ_XHAT_HIGHER_L_ZERO hint is for the wq kernels; this family computes the general form
   a.y0_zero = (xhat_layout & XEQ_SB_Y0_ZERO) ? 1 : 0;
   dim3 grid((unsigned)(n_nodes < 2048 ? n_nodes : 2048));
-  if (dtype == XEQ_F32 && num_basis <= 20 && n_nodes <= 512 && n_nodes <= xeq_small_rows()) {
-    // few nodes (an MD-sized system: at most two workgroups per CU): records staged in LDS per segment, 256 registers allowed
+  if (sb_stage_form(dtype, n_nodes, num_basis)) {
+    // few nodes: records staged in LDS per segment, 256 registers allowed
     using T = float;
-    hipLaunchKernelGGL((k_message_fwd_sb<T, 20, 2, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)basis, (const T*)h, (const T*)xhat,
+    hipLaunchKernelGGL((k_message_fwd_sb<T, SB_STAGE_MAXB, 2, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)basis, (const T*)h, (const T*)xhat,
                        (const T*)s_in, (const T*)x_in, (const T*)w_rbf, (const T*)b_rbf, (T*)s_out, (T*)x_out);
   } else
   XEQ_SB_DISPATCH(k_message_fwd_sb, 2, 2, a, (const T*)basis, (const T*)h, (const T*)xhat, (const T*)s_in, (const T*)x_in,
@@ -1029,11 +1052,11 @@ int xeq_message_bwd_sb(int dtype, int64_t n_nodes, int64_t n_edges, const int32_
   a.xl = xhat_layout & 1;   // the XEQ_XHAT_HIGHER_L_ZERO hint is for the wq kernels; this family computes the general form
   a.acc_vec = (xhat_layout & XEQ_SB_ACCUM_VEC) ? 1 : 0;
   dim3 grid((unsigned)(n_nodes < 2048 ? n_nodes : 2048));
-  if (dtype == XEQ_F32 && num_basis <= 20 && n_nodes <= 512 && n_nodes <= xeq_small_rows()) {
-    // few nodes (an MD-sized system: at most two workgroups per CU): the group's records staged in LDS (one round of vector loads
-    // instead of a scalar-memory round trip per edge) and 256 registers allowed (no spills) -- the arithmetic is the same
+  if (sb_stage_form(dtype, n_nodes, num_basis)) {
+    // few nodes: the group's records staged in LDS (one round of vector loads instead of a scalar-memory round trip per edge) and
+    // 256 registers allowed (no spills) -- the arithmetic is the same
     using T = float;
-    hipLaunchKernelGGL((k_message_bwd_sb<T, 20, 1, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)basis, (const T*)dbasis, (const T*)h,
+    hipLaunchKernelGGL((k_message_bwd_sb<T, SB_STAGE_MAXB, 1, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, a, (const T*)basis, (const T*)dbasis, (const T*)h,
                        (const T*)xhat, (const T*)grad_s, (const T*)grad_x, (const T*)w_rbf, (const T*)b_rbf, (T*)grad_h, (T*)grad_xhat,
                        (T*)grad_vec);
   } else
