@@ -465,6 +465,21 @@ int xeq_train_out(int dtype, int reverse, int64_t n, const void* const uv[3], co
                   const void* inner, const void* inner_tan, const void* g_s, const void* g_x, int node_dim, const int32_t mul[3],
                   void* out0, void* out1, void* const d_uv[3], void* stream);
 
+/* Edge geometry of an evaluation that is differentiated twice with respect to the POSITIONS (hessian.py; csrc/xeq_train_edge.hip, host
+ * side nn/training_ops.py EdgeRecordFn / EdgeRecordGrad): vec[E, 3] -> the per-edge record [E, W], W = xeq_edge_basis_width(B), in
+ * xeq_edge_basis's layout [f rho_k (B) | 0 to a multiple of 4 | f | Y_1 (3) | Y_2 (5) | 0 0 0], with the values of the tensor chain of
+ * nn/training.py (component-normalised harmonics in (y, z, x) order, norm clamped at 1e-12; f and all its derivatives 0 at |vec| >= cutoff).
+ * Dual-number convention of xeq_train_norm: with a *_tan pointer given the same body runs on (value, tangent) and `out` holds the TANGENT.
+ *   reverse = 0: out[E, W] = record(vec); with vec_tan: J(vec) vec_tan.  g_rec / g_rec_tan must be NULL.
+ *   reverse = 1: out[E, 3] = dL/dvec = J(vec)^T g_rec; with tangents: the tangent of that at (vec + eps vec_tan, g_rec + eps g_rec_tan);
+ *                either tangent may be NULL (= zero).
+ * Pad columns and the last three entries of a record are written as exact zeros.  p0 / p1: the basis parameters (Bessel: freq; Gaussian:
+ * mean, std), inputs only -- no parameter gradient.  f32 / f64, Bessel and Gaussian bases, both envelopes, num_basis 1..32;
+ * xeq_train_edge_supported -> 1 / 0 says so (0 for the exponential bases, which the entry refuses).  n_edges = 0: success, no launch. */
+int xeq_train_edge_supported(int dtype, int rbf_kind, int cutoff_kind, int num_basis);
+int xeq_train_edge(int dtype, int reverse, int64_t n_edges, const void* vec, const void* vec_tan, const void* g_rec, const void* g_rec_tan,
+                   int rbf_kind, int cutoff_kind, int num_basis, double cutoff, const void* p0, const void* p1, void* out, void* stream);
+
 /* Launch policy, stated ONCE for every front (the Python modules' ops.select_message_impl / ops._wq_edges_per_stream and the
  * registered operator xeq::xpainn_eval call these): the kernel family `auto` takes for a configuration and these sizes, and the
  * stream length of a wq walk plan (n_ranges = ceil(E / (2 x edges_per_stream))). */

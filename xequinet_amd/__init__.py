@@ -5,3 +5,13 @@ C ABI of include/xeq.h; this package is the host-side mirror of the reference's
 from . import keys  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # hessian / hessian_vector_products (hessian.py), imported on first use: the package itself imports without the built library
+    if name in ("hessian", "hessian_vector_products"):
+        import importlib
+
+        mod = importlib.import_module(".hessian", __name__)     # (binds the callable module as ``hessian``)
+        return mod if name == "hessian" else mod.hessian_vector_products
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

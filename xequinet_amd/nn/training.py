@@ -37,6 +37,12 @@ NATIVE_LINEAR = True
 # GPU work per QM9-1024 step, too little to hide the nodes' host cost behind (12.7 ms with torch.nn's layers, 18-22 ms with these).  A
 # choice between two correct forms, so a plain module variable is enough.
 _SECOND_ORDER_PASS = False
+# data-dict flag that hessian.py ALONE sets, once it knows that every message block of the model takes ops.DiffMessage: the embedding forms
+# the per-edge records from the edge vectors in one launch per order (training_ops.EdgeRecordFn, csrc/xeq_train_edge.hip) and none of the
+# [E, B] tensors; no gradient reaches the basis parameters that way, which is why a training pass never sets it
+EDGE_KERNEL = "_xeq_edge_kernel"
+# False: the edge geometry of such an evaluation stays on the tensor chain (the cross-check of the kernel form, tests/test_gpu_hessian.py)
+NATIVE_EDGE = True
 # data-dict flag set by BaseModel.forward for a training pass whose loss reads energies only (no forces, no virial): the blocks stay on
 # the fused HIP kernels and hand their parameters to the block functions, which return the parameter gradients (nn/fused.py)
 PARAM_GRADS = "_xeq_param_grads"
@@ -179,6 +185,14 @@ def embedding(module, data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     s = module.embedding(z.long() if isinstance(module.embedding, torch.nn.Embedding) else z)
     dist = data[keys.EDGE_LENGTH].unsqueeze(-1)
     data[keys.NODE_INVARIANT] = s
+    if NATIVE_EDGE and data.get(EDGE_KERNEL, False):
+        from .training_ops import EdgeRecordFn
+
+        rbf = module.rbf
+        p0, p1 = (p if p is None else p.detach().to(vectors.dtype).reshape(-1).contiguous() for p in rbf.params())
+        data[_REC], _ = EdgeRecordFn.apply(vectors, p0, p1, (rbf.kind, module.cutoff_fn.kind, int(rbf.num_basis), float(module.cutoff_fn.cutoff)))
+        data[keys.NODE_EQUIVARIANT] = torch.zeros((s.shape[0], module.node_irreps.dim), dtype=s.dtype, device=s.device)
+        return data
     data[keys.RADIAL_BASIS_FUNCTION] = radial_basis(module.rbf, dist)
     data[keys.ENVELOPE_FUNCTION] = envelope(module.cutoff_fn, dist)
     data[_RSH] = spherical_harmonics(vectors, module.node_irreps.lmax)

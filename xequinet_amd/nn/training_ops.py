@@ -12,6 +12,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from .. import lib
 from ..lib import call, dtype_code, mul3, ptr, ptr3, require_hip, stream
 
 
@@ -92,6 +93,8 @@ class NormGrad(Function):
         u_s, u_x = _z(s, u_s), _z(x, u_x)
         d_gs, d_gx, _ = _norm_call(0, s, u_s, x, u_x, ln_w, ln_b, eq_w, eq_b, None, None, ctx.meta)
         d_s, d_x, rows = _norm_call(1, s, u_s, x, u_x, ln_w, ln_b, eq_w, eq_b, g_s, g_x, ctx.meta)
+        if not (ctx.needs_input_grad[2] or ctx.needs_input_grad[4]):     # frozen parameters (hessian.py): the sums over the nodes are left out
+            return d_s, d_x, None, None, None, None, d_gs, d_gx, None, None
         d_lw, _, d_ew, _ = _norm_rows(rows, F, sum(mul), mul[0])
         return d_s, d_x, d_lw, None, d_ew, None, d_gs, d_gx, None, None
 
@@ -209,6 +212,90 @@ class UpdateOutGrad(Function):
         d_gs, d_gx = _out_call(0, uv, u, a, u_a, inner, u_in, None, None, ctx.meta)
         d_uv, d_a, d_in = _out_call(1, uv, u, a, u_a, inner, u_in, g_s, g_x, ctx.meta)
         return (*d_uv, d_a, d_in, d_gs, d_gx, None)
+
+
+# ---- edge geometry: vec -> per-edge record (csrc/xeq_train_edge.hip) ------------------------------------------------------------------
+def edge_record_supported(vec: torch.Tensor, rbf_kind: str, cutoff_kind: str, num_basis: int) -> bool:
+    return bool(vec.is_cuda and vec.dtype in (torch.float32, torch.float64) and rbf_kind in lib.RBF_KINDS and cutoff_kind in lib.CUTOFF_KINDS
+                and lib.load().xeq_train_edge_supported(dtype_code(vec), lib.RBF_KINDS[rbf_kind], lib.CUTOFF_KINDS[cutoff_kind], int(num_basis)))
+
+
+def _edge_call(reverse, vec, vec_t, g, g_t, p0, p1, meta):
+    rbf_kind, cutoff_kind, num_basis, cutoff = meta
+    E = vec.shape[0]
+    width = 3 if reverse else int(lib.load().xeq_edge_basis_width(num_basis))
+    out = torch.empty((E, width), dtype=vec.dtype, device=vec.device)
+    call("xeq_train_edge", dtype_code(vec), int(reverse), E, ptr(vec), ptr(vec_t), ptr(g), ptr(g_t), lib.RBF_KINDS[rbf_kind],
+         lib.CUTOFF_KINDS[cutoff_kind], int(num_basis), float(cutoff), ptr(p0), ptr(p1), ptr(out), stream())
+    return out
+
+
+def _graph_task() -> int:
+    get = getattr(torch._C, "_current_graph_task_id", None)
+    return -1 if get is None else int(get())
+
+
+class EdgeRecordFn(Function):
+    """vec [E, 3] -> the per-edge record [E, roundup(B, 4) + 12] of the kernel message (ops.training_records' layout and values) in one
+    launch; meta = (rbf kind, cutoff kind, num_basis, cutoff).  p0 / p1: the basis parameters in the dtype of vec, inputs only (no
+    parameter gradient: the caller differentiates with respect to the positions alone, hessian.py).
+
+    Second output ``link`` [E, 3] (never read, to be ignored by the caller): it is handed to the reverse node, ``EdgeRecordGrad``, so that
+    in the autograd graph that node leads back to THIS one.  A second-order pass then reaches this node once, after the message blocks,
+    with both the cotangent w of the record and the cotangent u of dL/dvec (sent along ``link``), and forms
+    (sum_k g_k Hess rec_k) u + J^T w in ONE launch of the reverse form with both tangents -- instead of one launch in each node and an add."""
+
+    @staticmethod
+    def forward(ctx, vec, p0, p1, meta):
+        require_hip(vec, p0, p1)
+        vec = vec.contiguous()
+        link = torch.empty_like(vec)
+        ctx.save_for_backward(vec, p0, p1, link)
+        ctx.meta = meta
+        ctx.pending = []     # (graph task, u, g_rec) of the EdgeRecordGrad nodes that ran in a second-order pass and wait for this node
+        ctx.set_materialize_grads(False)
+        return _edge_call(0, vec, None, None, None, p0, p1, meta), link
+
+    @staticmethod
+    def backward(ctx, g_rec, u_link):
+        vec, p0, p1, link = ctx.saved_tensors
+        task = _graph_task()
+        waiting = [p for p in ctx.pending if p[0] == task] if u_link is not None else []
+        ctx.pending.clear()
+        if not waiting:      # a first-order pass: J^T g_rec as a node that can be differentiated again
+            if g_rec is None:
+                return None, None, None, None
+            return EdgeRecordGrad.apply(vec, g_rec.contiguous(), link, p0, p1, ctx.meta, ctx.pending), None, None, None
+        w = None if g_rec is None else g_rec.contiguous()
+        out = None
+        for _, u, g in waiting:
+            term = _edge_call(1, vec, u, g, w, p0, p1, ctx.meta)
+            out, w = term if out is None else out + term, None
+        return out, None, None, None
+
+
+class EdgeRecordGrad(Function):
+    """(vec, g_rec) -> dL/dvec = J(vec)^T g_rec.  Its own reverse pass, for the cotangent u of dL/dvec: d g_rec = J(vec) u, the forward
+    form at tangent u, here; d vec = (sum_k g_k Hess rec_k) u, the reverse form at tangent u, in the ``EdgeRecordFn`` node that ``link``
+    leads to (see there)."""
+
+    @staticmethod
+    def forward(ctx, vec, g_rec, link, p0, p1, meta, pending):
+        ctx.save_for_backward(vec, g_rec, p0, p1)
+        ctx.meta, ctx.pending = meta, pending
+        return _edge_call(1, vec, None, g_rec, None, p0, p1, meta)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, u):
+        vec, g_rec, p0, p1 = ctx.saved_tensors
+        u = u.contiguous()
+        d_g = _edge_call(0, vec, u, None, None, p0, p1, ctx.meta) if ctx.needs_input_grad[1] else None
+        d_link = None
+        if ctx.needs_input_grad[2]:
+            ctx.pending.append((_graph_task(), u, g_rec))
+            d_link = u
+        return None, d_g, d_link, None, None, None, None
 
 
 # ---- linear layers: the weight-gradient products on the row-chunk kernel ----------------------------------------------------------------
