@@ -974,6 +974,59 @@ int xeq_ewald_layernorm_fwd(const void* x, int64_t n, int node_dim, const void* 
 int xeq_ewald_layernorm_bwd(const void* g, const void* x, const void* stats, const void* weight, int64_t n, int node_dim, void* g_x, void* stream);
 int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const void* pre, int64_t count, void* out, void* stream);
 
+/* Device-resident molecular dynamics around a whole-step graph (xequinet_amd/md.py, csrc/xeq_md.hip), f32 / f64.
+ * One MD step is xeq_md_front, the step's graph on the step object's static buffers, xeq_md_back; nothing reaches the host between them.
+ * Per-atom arithmetic runs in double whatever `dtype` is and is rounded once where it is stored.
+ *
+ * Per-atom inputs, all of `dtype`: inv_mass [n] = A / m_i (A: the factor from force / mass to length / fs^2; 0: a FIXED atom, which
+ * neither moves nor keeps a velocity), half_mass [n] = m_i / (2 A) (kinetic energy per squared velocity; 0 for a fixed atom).  batch [n]:
+ * the atom's graph.  book: int64 [4] on the device = {steps done, largest n_edges seen, non-finite flag, unused}, maintained by
+ * xeq_md_back with plain stores of one lane; the host resets entries 1 and 2 when it has read them.
+ *
+ * Generator: Philox4x32-10 with key = (seed low word, seed high word) and counter
+ *   c0 = rng_id low word, c1 = rng_id high word, c2 = step low word, c3 = step bits 32 .. 61 | purpose << 30
+ * (purpose 0: the Langevin O step, 1: Maxwell-Boltzmann velocities; step < 2^62).  With u_k = (word_k + 1) 2^-32 in (0, 1], rounded once
+ * to `dtype`: z0 = sqrt(-2 ln u_0) cos(2 pi u_1), z1 = sqrt(-2 ln u_0) sin(2 pi u_1), z2 = sqrt(-2 ln u_2) cos(2 pi u_3), with the accurate
+ * logf / sincosf for f32 and log / sincos for f64.
+ * xeq_md_normals: words [n, 4] (uint32, optional) and normals [n, 3] (`dtype`, optional) of the ids rng_id [n].
+ *
+ * xeq_md_front, per atom: [berendsen: v *= lambda_g, lambda_g = sqrt(1 + dt_over_tau (t0 / T_g - 1)) clamped to [0.9, 1.1] with
+ * T_g = ke[g] tfac[g], and 1 where T_g is not positive]; v += dt / 2 * frc * inv_mass; [nve, berendsen: x += dt v] [langevin:
+ * v' = c1 v + sqrt(noise2 inv_mass) z with z from (seed, 0, rng_id[i], book[0]); x += dt / 2 * (v + v'); v = v'] (noise2 = (1 - c1^2) k_B T);
+ * then, with a cell and a periodic axis, the wrap: s = floor(x . inv(cell)) along the periodic axes, x -= s . cell, image [n, 3] += s
+ * (applied twice: rounding to `dtype` can put an atom exactly on the far face).  cell: 9 doubles ON THE HOST (rows = lattice vectors),
+ * pbc: 3 int32 on the host; both NULL for open boundaries.  pos, vel, image are updated in place.  dt = 0 is the wrap alone,
+ * whatever the ensemble (no kick, no drift, no thermostat).
+ *
+ * xeq_md_back: the second half of a step.
+ *   Chunks: chunk_atom0 / chunk_n [n_chunks] name at most XEQ_MD_CHUNK consecutive atoms of ONE graph, counted from the graph's first
+ *   atom; graph_chunk_ptr [n_graphs + 1] gives a graph's chunks.  The caller builds the three once from ptr.
+ *   First launch, one workgroup per chunk: frc = frc_step; with `advance`, v += half_dt * frc * inv_mass; the chunk's kinetic energy
+ *   sum_i half_mass_i |v_i|^2 in double (lanes, butterfly, the four waves in order) into partial [n_chunks]; its non-finite-force flag
+ *   into partial_bad [n_chunks]; the recorder's positions.
+ *   Second launch, one workgroup: ke[g] = the graph's partials in chunk order (one lane for up to four chunks, a wave with a butterfly
+ *   beyond), epot[g] = energy_step[g]; then one lane: book[0] += advance, book[1] = max(book[1], n_edges_step[0]), book[2] = 1 on a
+ *   non-finite force or energy.  With a single chunk the first launch's workgroup does this part itself and there is no second launch.
+ *   No atomics; a graph's ke has the same bits alone and anywhere in a batch.
+ *   Recorder (record_every > 0 and advance): when d = book[0] - record_start behind this step is a positive multiple of record_every,
+ *   row d / record_every - 1 (< record_rows) of traj_pos [rows, n, 3] (unwrapped: pos + image . cell), traj_epot / traj_ekin
+ *   [rows, n_graphs] and traj_step [rows] is written.
+ * xeq_md_inverse_cell: the inverse the wrap uses (host only; inv [9] with frac_k = sum_j x_j inv[3 j + k]). */
+#define XEQ_MD_CHUNK 256
+enum { XEQ_MD_NVE = 0, XEQ_MD_LANGEVIN = 1, XEQ_MD_BERENDSEN = 2 };
+enum { XEQ_MD_PURPOSE_LANGEVIN = 0, XEQ_MD_PURPOSE_MAXWELL = 1 };
+int xeq_md_inverse_cell(const double* cell, double* inv);
+int xeq_md_normals(int dtype, uint64_t seed, int purpose, uint64_t step, const int64_t* rng_id, int64_t n, uint32_t* words, void* normals,
+                   void* stream);
+int xeq_md_front(int dtype, int ensemble, int64_t n, int64_t n_graphs, void* pos, void* vel, const void* frc, const void* inv_mass,
+                 const int64_t* batch, const void* ke, const void* tfac, const int64_t* rng_id, const int64_t* book, uint64_t seed, double dt,
+                 double c1, double noise2, double dt_over_tau, double t0, const double* cell, const int32_t* pbc, int32_t* image, void* stream);
+int xeq_md_back(int dtype, int advance, int64_t n, int64_t n_graphs, int64_t n_chunks, const void* pos, void* vel, void* frc, const void* frc_step,
+                const void* energy_step, const int32_t* n_edges_step, const void* inv_mass, const void* half_mass, const int32_t* chunk_atom0,
+                const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* ke, void* epot, int64_t* book,
+                double half_dt, const double* cell, const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start,
+                int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

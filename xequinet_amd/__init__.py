@@ -14,4 +14,8 @@ def __getattr__(name):
 
         mod = importlib.import_module(".hessian", __name__)     # (binds the callable module as ``hessian``)
         return mod if name == "hessian" else mod.hessian_vector_products
+    if name == "md":     # device-resident molecular dynamics (md.py), imported on first use for the same reason
+        import importlib
+
+        return importlib.import_module(".md", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,428 @@
+"""Molecular dynamics that stays on the GPU: an integrator next to the whole-step graphs of runtime.py.
+
+``runtime.GraphedStep`` / ``GraphedStepPBC`` evaluate one MD step -- neighbour search, model, forces -- as one captured HIP graph, and every
+consumer so far took the results back to the host once per step.  ``Dynamics`` is the consumer that does not: one MD step is
+
+    xeq_md_front   (Berendsen scale, half kick, drift, Langevin O step, wrap: writes the step object's static ``pos``)
+    the step's graph, replayed on its static buffers
+    xeq_md_back    (half kick, per-graph kinetic energy, step counter / largest edge count / non-finite flag, trajectory rows)
+
+enqueued on the current stream with no host synchronisation; every ``check_every`` steps the host reads three integers back.  The step's
+own graph is REPLAYED between the two launches rather than captured again inside a larger graph: the step classes keep their capture logic
+(weights that moved, a list that outgrew its capacity) and the two launches take arguments that change between runs (recorder rows)
+without a re-capture.  Measured (profiles/md_timing.txt): with its arguments bound once per window the host needs 0.13 ms to enqueue an
+aspirin step that takes the GPU 0.38 ms, and 0.02-0.03 ms for 1 024 molecules; one captured graph per MD step was tried and gave the
+same device time and the same 0.13 ms, so it was not kept.
+
+A batch of independent open-boundary molecules (``ptr``) runs on GraphedStep, one periodic box (``cell``) on GraphedStepPBC; the models
+those classes refuse are refused here by constructing them.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from ctypes import c_void_p
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import keys, lib, ops
+from .lib import call, dtype_code, require_hip
+from .runtime import GraphedStep, GraphedStepPBC, pair_capacity
+from .utils import units as _units
+
+ENSEMBLES = {"nve": 0, "langevin": 1, "berendsen": 2}        # XEQ_MD_NVE / _LANGEVIN / _BERENDSEN of include/xeq.h
+PURPOSE_LANGEVIN, PURPOSE_MAXWELL = 0, 1                     # XEQ_MD_PURPOSE_*
+BOLTZMANN_J_PER_K = 1.380649e-23                             # exact (SI 2019)
+
+
+def unit_factors(energy_unit: str, length_unit: str) -> Dict[str, float]:
+    """``accel``: (energy / length) / (g / mol) in length / fs^2; ``kB``: the Boltzmann constant in energy / K -- from the constants of
+    utils/units.py (the table holds every unit in atomic units) and k_B in J / K."""
+    joule, metre = _units.eval_unit("J"), _units.eval_unit("m")
+    e_j = _units.eval_unit(energy_unit) / joule                  # one energy unit in J
+    l_m = _units.eval_unit(length_unit) / metre                  # one length unit in m
+    kg_per_gmol = 1.0e-3 / _units.eval_unit("mol")               # one g / mol in kg
+    fs = 1.0e-15
+    return {"accel": e_j / (l_m * kg_per_gmol) * fs * fs / l_m, "kB": BOLTZMANN_J_PER_K / e_j}
+
+
+def default_rng_id(ptr_host) -> np.ndarray:
+    """int64 [N]: the atom's index within its graph in the low word, the graph's index in the high word."""
+    ptr_host = np.asarray(ptr_host, dtype=np.int64)
+    counts = np.diff(ptr_host)
+    graph = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+    return (np.arange(int(ptr_host[-1]), dtype=np.int64) - ptr_host[graph]) | (graph << 32)
+
+
+def chunk_tables(ptr_host, chunk: int = lib.MD_CHUNK):
+    """(chunk_atom0 int32 [C], chunk_n int32 [C], graph_chunk_ptr int32 [G + 1]): every graph cut into chunks of at most ``chunk`` atoms
+    counted from ITS first atom (an empty graph has none), in graph order."""
+    ptr_host = np.asarray(ptr_host, dtype=np.int64)
+    atom0, count, gptr = [], [], [0]
+    for a, b in zip(ptr_host[:-1], ptr_host[1:]):
+        for s in range(int(a), int(b), chunk):
+            atom0.append(s)
+            count.append(min(chunk, int(b) - s))
+        gptr.append(len(atom0))
+    return np.asarray(atom0, dtype=np.int32), np.asarray(count, dtype=np.int32), np.asarray(gptr, dtype=np.int32)
+
+
+def normals(seed: int, purpose: int, step: int, rng_id: torch.Tensor, dtype=torch.float32, want_words: bool = True):
+    """(words uint32-as-int32 [n, 4] or None, normals [n, 3]) of the device generator (xeq_md_normals)."""
+    require_hip(rng_id)
+    rng_id = rng_id.to(torch.int64).contiguous()
+    n = int(rng_id.numel())
+    words = torch.empty((n, 4), dtype=torch.int32, device=rng_id.device) if want_words else None
+    out = torch.empty((n, 3), dtype=dtype, device=rng_id.device)
+    call("xeq_md_normals", dtype_code(out), int(seed) & (2**64 - 1), int(purpose), int(step), lib.ptr(rng_id), n, lib.ptr(words), lib.ptr(out), lib.stream())
+    return words, out
+
+
+class Dynamics:
+    """``Dynamics(model, pos, atomic_numbers, masses, ptr=... | cell=..., timestep_fs=..., ensemble=...)``: see the module text and
+    DESIGN.md section 12.  ``masses`` [N] in g / mol (0 or inf: a fixed atom); ``ensemble``: "nve" (velocity Verlet), "langevin" (BAOAB;
+    ``temperature_K``, ``friction_per_fs``), "berendsen" (``temperature_K``, ``taut_fs``)."""
+
+    def __init__(self, model, pos: torch.Tensor, atomic_numbers: torch.Tensor, masses: torch.Tensor, *, ptr: Optional[torch.Tensor] = None,
+                 cell: Optional[torch.Tensor] = None, pbc=None, timestep_fs: float, ensemble: str = "nve", temperature_K: Optional[float] = None,
+                 friction_per_fs: Optional[float] = None, taut_fs: Optional[float] = None, seed: int = 0, rng_id: Optional[torch.Tensor] = None,
+                 edge_capacity: Optional[int] = None, energy_unit: Optional[str] = None, length_unit: Optional[str] = None) -> None:
+        if ensemble not in ENSEMBLES:
+            raise ValueError(f"Dynamics: ensemble {ensemble!r} (one of {sorted(ENSEMBLES)})")
+        self.ensemble = ensemble
+        self.dt = float(timestep_fs)
+        if not (math.isfinite(self.dt) and self.dt > 0.0):
+            raise ValueError(f"Dynamics: timestep_fs {timestep_fs}")
+        if ensemble != "nve" and (temperature_K is None or not temperature_K >= 0.0):
+            raise ValueError(f"Dynamics: ensemble {ensemble!r} needs temperature_K >= 0")
+        if ensemble == "langevin" and (friction_per_fs is None or not friction_per_fs >= 0.0):
+            raise ValueError("Dynamics: ensemble 'langevin' needs friction_per_fs >= 0")
+        if ensemble == "berendsen" and (taut_fs is None or not taut_fs > 0.0):
+            raise ValueError("Dynamics: ensemble 'berendsen' needs taut_fs > 0")
+        N = int(pos.shape[0])
+        if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,) or masses.shape != (N,):
+            raise ValueError("Dynamics: pos [N, 3], atomic_numbers [N] and masses [N] are needed")
+        self.periodic = cell is not None
+        ptr_host = np.array([0, N], dtype=np.int64) if ptr is None else np.asarray(ptr.detach().cpu().numpy(), dtype=np.int64)
+        if ptr_host[0] != 0 or ptr_host[-1] != N or np.any(np.diff(ptr_host) < 0):
+            raise ValueError("Dynamics: ptr must rise from 0 to the atom count")
+        if self.periodic and len(ptr_host) != 2:
+            raise ValueError("Dynamics: a periodic system is ONE graph (GraphedStepPBC)")
+        self.ptr_host = ptr_host
+        self.n_atoms, self.n_graphs = N, len(ptr_host) - 1
+        cutoff = float((model if isinstance(model, torch.nn.Module) else model.model).cutoff_radius)
+        # the step object first: it refuses the models the whole-step classes do not take, whatever device the tensors are on
+        if self.periodic:
+            cell_h = np.asarray(cell.detach().double().cpu().numpy()).reshape(3, 3)
+            if edge_capacity is None:       # from the density; a list that outgrows it is met by the restore protocol
+                vol = abs(float(np.linalg.det(cell_h)))
+                edge_capacity = int(1.25 * N * (N / vol if vol > 0 else 0.0) * 4.0 / 3.0 * math.pi * cutoff**3) + 64
+            self.step = GraphedStepPBC(model, N, int(edge_capacity))
+            self._explicit_capacity = False
+        else:
+            self._explicit_capacity = edge_capacity is not None
+            self.step = GraphedStep(model, (N, self.n_graphs, int(pair_capacity(ptr_host) if edge_capacity is None else edge_capacity)))
+        require_hip(pos, atomic_numbers, masses, ptr, cell, rng_id)
+        dev, dt_ = self.step.pos.device, self.step.pos.dtype
+        if dev.type != "cuda":
+            raise RuntimeError("xequinet_amd ops run on MI355X (HIP) tensors only and have no CPU fallback; the model is on " + str(dev))
+        self.device, self.dtype = dev, dt_
+        self._code = dtype_code(self.step.pos)
+
+        u = _units.get_default_units()
+        self.energy_unit = energy_unit or u.get(keys.TOTAL_ENERGY, "eV")
+        self.length_unit = length_unit or u.get(keys.POSITIONS, "Angstrom")
+        fac = unit_factors(self.energy_unit, self.length_unit)
+        self.accel, self.kB = fac["accel"], fac["kB"]
+        self.temperature_K = None if temperature_K is None else float(temperature_K)
+        self.seed = int(seed) & (2**64 - 1)
+        gamma = 0.0 if friction_per_fs is None else float(friction_per_fs)
+        self._c1 = math.exp(-gamma * self.dt)
+        self._noise2 = (1.0 - self._c1 * self._c1) * self.kB * (self.temperature_K or 0.0)
+        self._dt_over_tau = 0.0 if taut_fs is None else self.dt / float(taut_fs)
+
+        m = masses.detach().double().cpu().numpy()
+        free = np.isfinite(m) & (m > 0.0)
+        safe = np.where(free, m, 1.0)
+        self._mass_host = np.where(free, m, 0.0)
+        on = lambda a, t: torch.from_numpy(np.ascontiguousarray(a)).to(t).to(dev)
+        self.inv_mass = on(np.where(free, self.accel / safe, 0.0), dt_)
+        self.half_mass = on(np.where(free, safe / (2.0 * self.accel), 0.0), dt_)
+        n_free = np.add.reduceat(np.concatenate([free.astype(np.int64), [0]]), ptr_host[:-1])[: self.n_graphs] * (np.diff(ptr_host) > 0)
+        self.n_free = n_free
+        self.tfac = on(np.where(n_free > 0, 2.0 / (3.0 * np.maximum(n_free, 1) * self.kB), 0.0), dt_)
+        self.rng_id = (on(default_rng_id(ptr_host), torch.int64) if rng_id is None else rng_id.detach().to(torch.int64).contiguous().clone())
+        if self.rng_id.shape != (N,):
+            raise ValueError("Dynamics: rng_id [N]")
+        a0, cn, gp = chunk_tables(ptr_host)
+        self.n_chunks = len(a0)
+        self._chunk_atom0, self._chunk_n, self._graph_chunk_ptr = on(a0, torch.int32), on(cn, torch.int32), on(gp, torch.int32)
+        self._partial = torch.zeros(max(self.n_chunks, 1), dtype=torch.float64, device=dev)
+        self._partial_bad = torch.zeros(max(self.n_chunks, 1), dtype=torch.int32, device=dev)
+
+        G = self.n_graphs
+        self.vel = torch.zeros((N, 3), dtype=dt_, device=dev)
+        self.frc = torch.zeros((N, 3), dtype=dt_, device=dev)
+        self.image = torch.zeros((N, 3), dtype=torch.int32, device=dev)
+        self.ke = torch.zeros(G, dtype=dt_, device=dev)
+        self.epot = torch.zeros(G, dtype=dt_, device=dev)
+        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # steps done, largest n_edges, non-finite flag, unused
+        self._ck = None
+        self._steps_host = 0
+        self._fresh = False            # frc / ke / epot belong to the current positions and velocities
+        self._rec = (0, 0, 0)
+        self.trajectory: Dict[str, torch.Tensor] = {}
+        self._back_args = None
+        self._front_args = None
+        self._ke_stale = False         # velocities were set since ke was formed
+        self._no_edges = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._run_serial = 0           # (part of the cache key of xeq_md_back's arguments: every run has its own trajectory buffers)
+
+        z = atomic_numbers.detach()
+        if self.periodic:
+            pbc_ = [True, True, True] if pbc is None else [bool(v) for v in (pbc.tolist() if isinstance(pbc, torch.Tensor) else pbc)]
+            self.step._load_cell(cell.detach().to(dt_).to(dev), pbc_)          # once: the box is fixed for the run
+            ops.copy_many([(self.step.pos, pos.detach().to(dt_).contiguous()), (self.step.z, z.to(torch.int32).contiguous())])
+            cell_t = self.step.cell.reshape(3, 3)
+            self._cell_dev = cell_t.double()
+            self._cell_c = (ctypes.c_double * 9)(*[float(v) for v in cell_t.double().cpu().reshape(-1).tolist()])
+            self._pbc_c = (ctypes.c_int32 * 3)(*[int(v) for v in pbc_])
+            self._any_pbc = any(pbc_)
+        else:
+            self.step._load(pos, z, torch.from_numpy(ptr_host).to(dev), None)
+            self._cell_dev, self._cell_c, self._pbc_c, self._any_pbc = None, None, None, False
+        self._pos = self.step.pos[:N]        # THE positions: the step's static buffer (a periodic system's are wrapped into the box)
+        call("xeq_md_front", *self._front_tuple(0.0), lib.stream())     # dt = 0: the wrap alone: the search sweeps +- reps images around the box, not around a stray atom
+
+    # ------------------------------------------------------------------------------------------------ launches
+    def _front_tuple(self, dt: float):
+        p = lib.ptr
+        return (self._code, ENSEMBLES[self.ensemble], self.n_atoms, self.n_graphs, p(self._pos), p(self.vel), p(self.frc), p(self.inv_mass),
+                p(self.step.batch), p(self.ke), p(self.tfac), p(self.rng_id), p(self.book), self.seed, dt, self._c1, self._noise2,
+                self._dt_over_tau, self.temperature_K or 0.0, self._cell_c, self._pbc_c, p(self.image))
+
+    def _front(self, dt: float) -> None:
+        if dt == self.dt:
+            if self._front_args is None:
+                self._front_args = self._front_tuple(dt)          # (every buffer named here lives as long as this object)
+            call("xeq_md_front", *self._front_args, lib.stream())
+        else:
+            call("xeq_md_front", *self._front_tuple(dt), lib.stream())
+
+    def _eval(self) -> None:
+        """The whole step on what the static buffers hold, through the step object's own logic (captured on first use, again when the
+        weights moved or the edge arrays grew)."""
+        self.step.replay()
+
+    def _back_tuple(self, outputs, frc=None, energy=None, n_edges=None, record=True):
+        p = lib.ptr
+        frc = outputs[keys.FORCES] if frc is None else frc
+        en = outputs[keys.TOTAL_ENERGY] if energy is None else energy
+        ne = outputs["n_edges"] if n_edges is None else n_edges
+        assert frc.is_contiguous() and frc.dtype == self.dtype and en.is_contiguous() and en.dtype == self.dtype and ne.dtype == torch.int32
+        t = self.trajectory if record else {}
+        every, start, rows = self._rec if record else (0, 0, 0)
+        return (self.n_atoms, self.n_graphs, self.n_chunks, p(self._pos), p(self.vel), p(self.frc), p(frc), p(en), p(ne), p(self.inv_mass),
+                p(self.half_mass), p(self._chunk_atom0), p(self._chunk_n), p(self._graph_chunk_ptr), p(self._partial), p(self._partial_bad),
+                p(self.ke), p(self.epot), p(self.book), 0.5 * self.dt, self._cell_c, self._pbc_c, p(self.image), every, start, rows,
+                p(t.get("pos")), p(t.get("epot")), p(t.get("ekin")), p(t.get("step")))
+
+    def _back(self, advance: bool) -> None:
+        key = (self.step.captures, self._rec, self._run_serial)
+        if self._back_args is None or self._back_args[0] != key:
+            self._back_args = (key, self._back_tuple(self.step.outputs))
+        call("xeq_md_back", self._code, int(advance), *self._back_args[1], lib.stream())
+
+    def _back_ke(self) -> None:
+        """The kinetic energies of new velocities: the back kernel without a kick on the forces and energies this object holds (they
+        depend on the positions alone); no evaluation, no read-back."""
+        call("xeq_md_back", self._code, 0, *self._back_tuple(None, self.frc, self.epot, self._no_edges, record=False), lib.stream())
+        self._ke_stale = False
+
+    def _enqueue(self, n: int) -> None:
+        """``n`` steps on the current stream; nothing here waits for the device."""
+        if n <= 0:
+            return
+        # the step's own graph between two launches.  The first evaluation goes through the step object's logic; nothing can move the
+        # weights between that one and the window's check, so the others replay the graph it left.  Arguments are bound once.
+        L = lib.load()
+        front, back = L.xeq_md_front, L.xeq_md_back
+        if self._front_args is None:
+            self._front_args = self._front_tuple(self.dt)
+        stream = lib.stream()
+        fa = (*self._front_args, stream)
+        if front(*fa):
+            raise RuntimeError(f"xeq_md_front failed: {L.xeq_last_error().decode()}")
+        self._eval()
+        self._back(True)
+        ba = (self._code, 1, *self._back_args[1], stream)
+        replay = self.step.graph.replay
+        for _ in range(n - 1):
+            if front(*fa):
+                raise RuntimeError(f"xeq_md_front failed: {L.xeq_last_error().decode()}")
+            replay()
+            if back(*ba):
+                raise RuntimeError(f"xeq_md_back failed: {L.xeq_last_error().decode()}")
+
+    def _read_book(self):
+        """THE read-back: (steps done, largest n_edges since the last check, non-finite flag).  A sync-debug guard of the caller is lifted
+        for exactly this call."""
+        mode = torch.cuda.get_sync_debug_mode()
+        if mode:
+            torch.cuda.set_sync_debug_mode(0)
+        try:
+            vals = self.book.cpu().tolist()
+        finally:
+            if mode:
+                torch.cuda.set_sync_debug_mode(mode)
+        return int(vals[0]), int(vals[1]), bool(vals[2])
+
+    # ------------------------------------------------------------------------------------------------ check / restore
+    def _state(self):
+        return [self._pos, self.image, self.vel, self.frc, self.ke, self.epot, self.book]
+
+    def _save(self) -> None:
+        if self._ck is None:
+            self._ck = [torch.empty_like(t) for t in self._state()]
+        self.book[1:3].zero_()
+        ops.copy_many(list(zip(self._ck, self._state())))
+        self._ck_fresh = self._fresh
+
+    def _restore(self) -> None:
+        ops.copy_many(list(zip(self._state(), self._ck)))
+        self._fresh = self._ck_fresh
+
+    def _window(self, n: int) -> None:
+        """``n`` steps and one check behind them.  A list that outgrew the edge capacity voids the window: back to the checkpoint, more
+        room (GraphedStepPBC.grow), a new capture, the same steps again -- the random stream is a function of (seed, purpose, id, step),
+        so the second pass gives what a run with room from the start gives, bit for bit.  A non-finite force or energy also puts the
+        checkpoint back before it raises: the object stays at the last state that was checked."""
+        first = self._steps_host
+        if self._fresh and self._ke_stale:
+            self._back_ke()
+        self._save()
+        while True:
+            if not self._fresh:
+                self._eval()
+                self._back(False)
+                self._fresh, self._ke_stale = True, False
+            self._enqueue(n)
+            steps, most, bad = self._read_book()
+            cap = self.step.n_edges
+            if most <= cap:
+                break
+            self._restore()
+            if not self.periodic:
+                raise ValueError(f"Dynamics: the neighbour list reached {most} edges, the edge capacity is {cap}" +
+                                 (" (edge_capacity was given: pass a larger one)" if self._explicit_capacity else ""))
+            self.step.grow(most)
+        if bad:
+            self._restore()
+            self.book[1:3].zero_()
+            raise FloatingPointError(f"Dynamics: non-finite force or energy in steps {first} .. {first + n}; the state is that of step {first}")
+        self._steps_host = steps
+
+    def _settle(self) -> None:
+        if not self._fresh:
+            self._window(0)
+        elif self._ke_stale:
+            self._back_ke()
+
+    # ------------------------------------------------------------------------------------------------ public
+    def run(self, n_steps: int, check_every: int = 100, record_every: int = 0) -> None:
+        n_steps, check_every, record_every = int(n_steps), max(1, int(check_every)), max(0, int(record_every))
+        if n_steps < 0:
+            raise ValueError("Dynamics.run: n_steps < 0")
+        self._run_serial += 1
+        if record_every > 0:
+            rows = n_steps // record_every
+            self.trajectory = {"pos": torch.zeros((rows, self.n_atoms, 3), dtype=self.dtype, device=self.device),
+                               "epot": torch.zeros((rows, self.n_graphs), dtype=self.dtype, device=self.device),
+                               "ekin": torch.zeros((rows, self.n_graphs), dtype=self.dtype, device=self.device),
+                               "step": torch.zeros(rows, dtype=torch.int64, device=self.device)}
+            self._rec = (record_every, self._steps_host, rows)
+        else:
+            self.trajectory, self._rec = {}, (0, 0, 0)
+        done = 0
+        while done < n_steps:
+            w = min(check_every, n_steps - done)
+            self._window(w)
+            done += w
+        self._settle()
+
+    def _velocities_changed(self) -> None:
+        self._ke_stale = True        # forces and potential energy depend on the positions alone: only the kinetic energy is redone
+
+    def set_velocities(self, v: torch.Tensor) -> None:
+        require_hip(v)
+        if v.shape != self.vel.shape:
+            raise ValueError(f"Dynamics.set_velocities: {tuple(v.shape)}, the state is {tuple(self.vel.shape)}")
+        self.vel.copy_(v.detach().to(self.dtype) * (self.inv_mass > 0).to(self.dtype)[:, None])      # (a fixed atom has none)
+        self._velocities_changed()
+
+    def maxwell_boltzmann(self, temperature_K: float) -> None:
+        """v_i = sqrt(k_B T / m_i) z_i with z from the device generator under the Maxwell-Boltzmann tag at the current step count."""
+        _, z = normals(self.seed, PURPOSE_MAXWELL, self._steps_host, self.rng_id, self.dtype, want_words=False)
+        sigma = torch.sqrt(self.kB * float(temperature_K) * self.inv_mass.double())
+        self.set_velocities((sigma[:, None] * z.double()).to(self.dtype))
+
+    def zero_momentum(self) -> None:
+        """Per graph: the centre-of-mass velocity of the free atoms is taken off them.  A set-up operation that SYNCHRONISES: the velocities
+        go to the host and back, and the sums are formed there in f64 in a fixed order that depends on the graph alone."""
+        v = self.vel.double().cpu().numpy()
+        m = self._mass_host
+        for a, b in zip(self.ptr_host[:-1], self.ptr_host[1:]):
+            mt = m[a:b].sum()
+            if mt > 0.0:
+                vcm = (m[a:b, None] * v[a:b]).sum(0) / mt
+                v[a:b] -= vcm * (m[a:b, None] > 0.0)
+        self.vel.copy_(torch.from_numpy(v).to(self.dtype))
+        self._velocities_changed()
+
+    @property
+    def step_count(self) -> int:
+        return self._steps_host
+
+    @property
+    def edge_capacity(self) -> int:
+        return self.step.n_edges
+
+    @property
+    def positions(self) -> torch.Tensor:
+        return self._pos.clone()
+
+    @property
+    def unwrapped_positions(self) -> torch.Tensor:
+        """pos + image . cell, in the operation order of the recorder (csrc/xeq_md.hip): the two agree bit for bit."""
+        if not self._any_pbc:
+            return self._pos.clone()
+        i, c = self.image.double(), self._cell_dev
+        x = self._pos.double()
+        return (x + ((i[:, 0:1] * c[0] + i[:, 1:2] * c[1]) + i[:, 2:3] * c[2])).to(self.dtype)
+
+    @property
+    def velocities(self) -> torch.Tensor:
+        return self.vel.clone()
+
+    @property
+    def forces(self) -> torch.Tensor:
+        self._settle()
+        return self.frc.clone()
+
+    @property
+    def potential_energy(self) -> torch.Tensor:
+        self._settle()
+        return self.epot.clone()
+
+    @property
+    def kinetic_energy(self) -> torch.Tensor:
+        self._settle()
+        return self.ke.clone()
+
+    @property
+    def temperature(self) -> torch.Tensor:
+        """T_g = 2 KE_g / (3 n_free,g k_B); 0 for a graph without a free atom."""
+        self._settle()
+        return self.ke * self.tfac

@@ -399,6 +399,10 @@ class GraphedStep:
             self.captures += 1
         self.graph.replay()
 
+    def replay(self) -> None:
+        """The step on whatever the static buffers hold (md.Dynamics writes positions there itself); results in ``outputs``."""
+        self._replay()
+
     def __call__(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, ptr: torch.Tensor, batch: Optional[torch.Tensor] = None,
                  ptr_host=None) -> Dict[str, torch.Tensor]:
         """-> {energy [G], atomic_energies [n], forces [n, 3], n_edges [1] (device)}: views of the graph's output buffers,
@@ -900,6 +904,16 @@ class GraphedStepPBC:
                 self.outputs = self._step()
             self.captures += 1
         self.graph.replay()
+
+    def replay(self) -> None:
+        """The step on whatever the static buffers hold (md.Dynamics writes positions there itself); results in ``outputs``."""
+        self._run()
+
+    def grow(self, n_edges_seen: int) -> None:
+        """More room for a list that reached ``n_edges_seen`` edges, by the rule of ``__call__``; the next replay captures again."""
+        self.n_edges = int(self.GROWTH * max(self.n_edges, int(n_edges_seen))) + 64
+        self._alloc_edges()
+        self.graph = None
 
     def __call__(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, cell: torch.Tensor, pbc, check: bool = True) -> Dict[str, torch.Tensor]:
         """-> {energy [1], atomic_energies [n], forces [n, 3], n_edges [1] (device)}: the graph's output buffers, overwritten by the
