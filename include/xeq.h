@@ -1027,6 +1027,49 @@ int xeq_md_back(int dtype, int advance, int64_t n, int64_t n_graphs, int64_t n_c
                 double half_dt, const double* cell, const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start,
                 int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* stream);
 
+/* Device-resident batched geometry optimisation (FIRE) around a whole-step graph (xequinet_amd/optimize.py, csrc/xeq_md.hip, DESIGN.md
+ * section 13), f32 / f64.  One iteration is xeq_fire_front, the step's graph on the step object's static buffers, xeq_fire_back; nothing
+ * reaches the host between them.  Every graph is its own FIRE system.  Per-atom and per-graph arithmetic runs in double whatever `dtype`
+ * is and is rounded once where it is stored; dt, alpha [n_graphs] and coef [n_graphs, 3] = (c_v, c_f, d) are double.
+ *
+ * Per-graph state: status int32 (XEQ_FIRE_FRESH: no velocity yet, ASE's `v is None`; _ACTIVE; _CONVERGED), n_pos int32 (evaluations with
+ * P > 0 in a row), converged_at int64 (the evaluation at which the graph converged, counted from 0; the caller starts it at -1), epot and
+ * fmax of `dtype`.  fixed: uint8 [n] or NULL, nonzero = the atom never moves, keeps v = 0, its force is left out of every sum and its
+ * entry in frc is 0.  batch [n]: the atom's graph.  book: int64 [4] on the device = {evaluations done, largest n_edges seen, non-finite
+ * flag, graphs not converged}, kept by xeq_fire_back with plain stores of one lane; the host resets entries 1 and 2 when it has read them.
+ *
+ * xeq_fire_back, behind evaluation number book[0]:
+ *   First launch, one workgroup per chunk (chunk tables as for xeq_md_back): frc = frc_step (0 for a fixed atom; untouched for a converged
+ *   graph); the chunk's P = sum f.v, ff = sum f.f, vv = sum v.v, max |f_i|^2 over its free atoms in double (lanes, butterfly, the four
+ *   waves in order) into partial [n_chunks, 4]; its non-finite-force flag into partial_bad [n_chunks]; the recorder's positions.
+ *   Second launch, one workgroup: a graph's partials in chunk order (one lane for up to four chunks, a wave with a butterfly beyond),
+ *   then, by the lane that holds them, for a graph that is not converged: epot = energy_step, fmax = sqrt(max |f_i|^2);
+ *     fmax < fmax_tol:  status = converged, converged_at = book[0]; nothing else, and nothing of this graph is written ever after;
+ *     fresh:            c_v = 0, c_f = dt;
+ *     P > 0:            c_v = 1 - alpha; if n_pos > n_min: dt = min(dt f_inc, dtmax), alpha *= f_alpha; n_pos += 1;
+ *                       c_f = alpha_old sqrt(vv) / sqrt(ff) + dt;
+ *     otherwise:        c_v = 0, alpha = alpha_start, dt *= f_dec, n_pos = 0, c_f = dt;
+ *     then |v'|^2 = c_v^2 vv + 2 c_v c_f P + c_f^2 ff, norm = dt sqrt(|v'|^2), d = norm > maxstep ? dt (maxstep / norm) : dt,
+ *     status = active.
+ *   Then one lane: book[0] += 1, book[1] = max(book[1], n_edges_step[0]), book[2] = 1 on a non-finite force or energy of a graph that
+ *   is not converged, book[3] = graphs not converged.  With a single chunk the first launch's workgroup does this part itself and
+ *   there is no second launch.  No atomics; a graph's sums and state have the same bits alone and anywhere in a batch.
+ *   Recorder (record_every > 0): when d = book[0] - record_start (book[0] read BEFORE the increment: this evaluation's number) is a
+ *   positive multiple of record_every, row d / record_every - 1 (< record_rows) of traj_pos [rows, n, 3] (unwrapped), traj_epot /
+ *   traj_fmax [rows, n_graphs] and traj_step [rows] is written.
+ * xeq_fire_front, per free atom of an ACTIVE graph: v = c_v v + c_f frc, x += d v, then the wrap of xeq_md_front (cell, pbc on the
+ * host, NULL for open boundaries).  Atoms of fresh or converged graphs and fixed atoms are not written. */
+enum { XEQ_FIRE_FRESH = 0, XEQ_FIRE_ACTIVE = 1, XEQ_FIRE_CONVERGED = 2 };
+int xeq_fire_front(int dtype, int64_t n, int64_t n_graphs, void* pos, void* vel, const void* frc, const uint8_t* fixed, const int64_t* batch,
+                   const int32_t* status, const double* coef, const double* cell, const int32_t* pbc, int32_t* image, void* stream);
+int xeq_fire_back(int dtype, int64_t n, int64_t n_graphs, int64_t n_chunks, const void* pos, const void* vel, void* frc, const void* frc_step,
+                  const void* energy_step, const int32_t* n_edges_step, const uint8_t* fixed, const int64_t* batch, const int32_t* chunk_atom0,
+                  const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* epot, void* fmax, double* dt,
+                  double* alpha, int32_t* n_pos, int32_t* status, int64_t* converged_at, double* coef, int64_t* book, double fmax_tol,
+                  double maxstep, double dtmax, int n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, const double* cell,
+                  const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start, int64_t record_rows, void* traj_pos,
+                  void* traj_epot, void* traj_fmax, int64_t* traj_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

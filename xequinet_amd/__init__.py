@@ -18,4 +18,8 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(".md", __name__)
+    if name == "optimize":     # device-resident batched FIRE minimiser (optimize.py), likewise
+        import importlib
+
+        return importlib.import_module(".optimize", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,6 +1,7 @@
 // Device-resident molecular dynamics around the whole-step graphs (xequinet_amd/md.py): the integrator's two
 // halves -- xeq_md_front in front of the step's graph, xeq_md_back behind it -- and the counter-based generator they share with
-// xeq_md_normals.  Plain vector code, f32 and f64 state.
+// xeq_md_normals; behind them the two halves of the batched FIRE minimiser (xequinet_amd/optimize.py), which share
+// the wrap, the chunk sums and the join.  Plain vector code, f32 and f64 state.
 //
 // Arithmetic.  Every per-atom update is evaluated in double whatever the state's type and rounded ONCE when it is stored: the state of an
 // f32 run is within half an ulp of the f64 value of the same expression on the same stored inputs, and no result depends on how the compiler
@@ -208,14 +209,18 @@ struct MdBackArgs {
   int64_t* traj_step;
 };
 
-// The trajectory row this step fills (-1: none): row (step - record_start) / record_every - 1 of the run's buffers, `step` counted behind it.
+// The trajectory row a step fills (-1: none): row (step - record_start) / record_every - 1 of the run's buffers, `step` counted behind it.
+__device__ __forceinline__ int64_t md_record_row_of(int64_t record_every, int64_t record_start, int64_t record_rows, int64_t step_after) {
+  if (record_every <= 0) return -1;
+  const int64_t d = step_after - record_start;
+  if (d <= 0 || d % record_every) return -1;
+  const int64_t row = d / record_every - 1;
+  return row < record_rows ? row : -1;
+}
+
 template <typename T>
 __device__ __forceinline__ int64_t md_record_row(const MdBackArgs<T>& a, int64_t step_after) {
-  if (!a.advance || a.record_every <= 0) return -1;
-  const int64_t d = step_after - a.record_start;
-  if (d <= 0 || d % a.record_every) return -1;
-  const int64_t row = d / a.record_every - 1;
-  return row < a.record_rows ? row : -1;
+  return a.advance ? md_record_row_of(a.record_every, a.record_start, a.record_rows, step_after) : -1;
 }
 
 __device__ __forceinline__ double md_wave_sum(double v) {
@@ -223,9 +228,55 @@ __device__ __forceinline__ double md_wave_sum(double v) {
   return v;
 }
 
-// One workgroup joins every graph's chunk partials in chunk order; then ONE lane does the bookkeeping with plain stores.  A graph of at
-// most MD_JOIN_SERIAL chunks is summed by one lane, chunk after chunk (a batch of many small molecules: a graph per lane); a larger one by
-// a wave, lane l adding chunks l, l + 64, ... and a butterfly.  Which of the two depends on the graph's own chunk count alone.
+// One workgroup joins every graph's chunk partials in chunk order.  A graph of at most MD_JOIN_SERIAL chunks is summed by one lane, chunk
+// after chunk (a batch of many small molecules: a graph per lane); a larger one by a wave, lane l adding chunks l, l + 64, ... and a
+// butterfly.  Which of the two depends on the graph's own chunk count alone.  `make()` gives an empty accumulator with add(chunk) and
+// wave() (the butterfly); `done(g, acc)` is called by the one lane that holds the graph's sum.  (The MD and the FIRE joins share this.)
+template <typename Make, typename Done>
+__device__ __forceinline__ void md_join_graphs(int64_t n_graphs, int64_t n_chunks, const int32_t* __restrict__ graph_chunk_ptr, Make make, Done done) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  int wide = 0;
+  for (int64_t g = threadIdx.x; g < n_graphs; g += blockDim.x) {
+    int64_t cb = graph_chunk_ptr[g], ce = graph_chunk_ptr[g + 1];
+    cb = cb < 0 ? 0 : cb;
+    ce = ce > n_chunks ? n_chunks : ce;
+    if (ce - cb > MD_JOIN_SERIAL) {
+      wide = 1;
+      continue;
+    }
+    auto s = make();
+    for (int64_t c = cb; c < ce; ++c) s.add(c);
+    done(g, s);
+  }
+  if (__syncthreads_or(wide)) {
+    for (int64_t g = wave; g < n_graphs; g += waves) {
+      int64_t cb = graph_chunk_ptr[g], ce = graph_chunk_ptr[g + 1];
+      cb = cb < 0 ? 0 : cb;
+      ce = ce > n_chunks ? n_chunks : ce;
+      if (ce - cb <= MD_JOIN_SERIAL) continue;
+      auto s = make();
+      for (int64_t c = cb + lane; c < ce; c += 64) s.add(c);
+      s.wave();
+      if (lane == 0) done(g, s);
+    }
+  }
+}
+
+struct MdKeSum {
+  const double* partial;
+  const int32_t* partial_bad;
+  double s;
+  int bad;
+  __device__ __forceinline__ void add(int64_t c) {
+    s = s + partial[c];
+    bad |= partial_bad[c];
+  }
+  __device__ __forceinline__ void wave() {
+    s = md_wave_sum(s);
+    for (int off = 32; off > 0; off >>= 1) bad |= __shfl_xor(bad, off, 64);   // (the one lane that stores carries every lane's flag)
+  }
+};
+
 template <typename T>
 __device__ __forceinline__ void md_join_store(const MdBackArgs<T>& a, int64_t g, int64_t row, double s, int* bad) {
   const T e = a.energy_step[g];
@@ -238,42 +289,18 @@ __device__ __forceinline__ void md_join_store(const MdBackArgs<T>& a, int64_t g,
   }
 }
 
+// The MD join; then ONE lane does the bookkeeping with plain stores.
 template <typename T>
 __device__ __forceinline__ void md_join(const MdBackArgs<T>& a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
   const int64_t step_after = a.book[0] + (a.advance ? 1 : 0);
   const int64_t row = md_record_row(a, step_after);
-  int bad = 0, wide = 0;
-  for (int64_t g = threadIdx.x; g < a.n_graphs; g += blockDim.x) {
-    int64_t cb = a.graph_chunk_ptr[g], ce = a.graph_chunk_ptr[g + 1];
-    cb = cb < 0 ? 0 : cb;
-    ce = ce > a.n_chunks ? a.n_chunks : ce;
-    if (ce - cb > MD_JOIN_SERIAL) {
-      wide = 1;
-      continue;
-    }
-    double s = 0.0;
-    for (int64_t c = cb; c < ce; ++c) {
-      s = s + a.partial[c];
-      bad |= a.partial_bad[c];
-    }
-    md_join_store(a, g, row, s, &bad);
-  }
-  if (__syncthreads_or(wide)) {
-    for (int64_t g = wave; g < a.n_graphs; g += waves) {
-      int64_t cb = a.graph_chunk_ptr[g], ce = a.graph_chunk_ptr[g + 1];
-      cb = cb < 0 ? 0 : cb;
-      ce = ce > a.n_chunks ? a.n_chunks : ce;
-      if (ce - cb <= MD_JOIN_SERIAL) continue;
-      double s = 0.0;
-      for (int64_t c = cb + lane; c < ce; c += 64) {
-        s = s + a.partial[c];
-        bad |= a.partial_bad[c];
-      }
-      s = md_wave_sum(s);
-      if (lane == 0) md_join_store(a, g, row, s, &bad);
-    }
-  }
+  int bad = 0;
+  md_join_graphs(
+      a.n_graphs, a.n_chunks, a.graph_chunk_ptr, [&]() { return MdKeSum{a.partial, a.partial_bad, 0.0, 0}; },
+      [&](int64_t g, const MdKeSum& k) {
+        bad |= k.bad;
+        md_join_store(a, g, row, k.s, &bad);
+      });
   const int any_bad = __syncthreads_or(bad);
   if (threadIdx.x == 0) {
     const int64_t ne = (int64_t)a.n_edges_step[0];
@@ -341,6 +368,261 @@ __global__ void __launch_bounds__(MD_CHUNK) k_md_back(MdBackArgs<T> a) {
     __threadfence_block();
     __syncthreads();
     md_join(a);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- FIRE
+// Batched geometry optimisation around the same whole-step graphs (xequinet_amd/optimize.py): every graph is its
+// own FIRE system (Bitzek et al., PRL 97, 170201 (2006), in the form of ASE's optimize.FIRE).  xeq_fire_back behind an evaluation forms a
+// graph's P = sum f.v, ff = sum f.f, vv = sum v.v and max |f_i|^2 over its free atoms -- chunk partials and join exactly as the kinetic
+// energy above -- and the lane that holds them runs the graph's state machine; xeq_fire_front in front of the next evaluation moves the
+// atoms by the three coefficients that lane left.  The per-graph state (dt, alpha, c_v, c_f, d) is double whatever the state's type.
+template <typename T>
+struct FireBackArgs {
+  int64_t n, n_graphs, n_chunks;
+  const T* pos;
+  const T* vel;
+  T* frc;
+  const T* frc_step;
+  const T* energy_step;
+  const int32_t* n_edges_step;
+  const uint8_t* fixed;
+  const int64_t* batch;
+  const int32_t* chunk_atom0;
+  const int32_t* chunk_n;
+  const int32_t* graph_chunk_ptr;
+  double* partial;   // [n_chunks, 4]: P, ff, vv, max |f|^2
+  int32_t* partial_bad;
+  T* epot;
+  T* fmax;
+  double* dt;
+  double* alpha;
+  int32_t* n_pos;
+  int32_t* status;
+  int64_t* converged_at;
+  double* coef;   // [n_graphs, 3]: c_v, c_f, d
+  int64_t* book;
+  double fmax_tol, maxstep, dtmax, f_inc, f_dec, alpha_start, f_alpha;
+  int n_min;
+  const int32_t* image;
+  MdBox box;
+  int64_t record_every, record_start, record_rows;
+  T* traj_pos;
+  T* traj_epot;
+  T* traj_fmax;
+  int64_t* traj_step;
+};
+
+__device__ __forceinline__ double md_wave_max(double v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+struct FireSums {
+  const double* partial;
+  const int32_t* partial_bad;
+  double p, ff, vv, m2;
+  int bad;
+  __device__ __forceinline__ void add(int64_t c) {
+    p = p + partial[4 * c];
+    ff = ff + partial[4 * c + 1];
+    vv = vv + partial[4 * c + 2];
+    m2 = fmax(m2, partial[4 * c + 3]);
+    bad |= partial_bad[c];
+  }
+  __device__ __forceinline__ void wave() {
+    p = md_wave_sum(p);
+    ff = md_wave_sum(ff);
+    vv = md_wave_sum(vv);
+    m2 = md_wave_max(m2);
+    for (int off = 32; off > 0; off >>= 1) bad |= __shfl_xor(bad, off, 64);
+  }
+};
+
+// One graph's state machine, run by the lane that holds its sums behind evaluation number `eval`.  A converged graph is left alone, bit
+// for bit; only its recorder row is filled, from what it kept.
+template <typename T>
+__device__ __forceinline__ void fire_decide(const FireBackArgs<T>& a, int64_t g, int64_t row, int64_t eval, const FireSums& s, int* bad) {
+  const int st = a.status[g];
+  if (st != XEQ_FIRE_CONVERGED) {
+    const T e = a.energy_step[g];
+    *bad |= s.bad | !isfinite((double)e);
+    const double fm = sqrt(s.m2);
+    a.epot[g] = e;
+    a.fmax[g] = (T)fm;
+    if (fm < a.fmax_tol) {
+      a.status[g] = XEQ_FIRE_CONVERGED;
+      a.converged_at[g] = eval;
+    } else {
+      double dt = a.dt[g], al = a.alpha[g], cv, cf;
+      int np = a.n_pos[g];
+      if (st == XEQ_FIRE_FRESH) {
+        cv = 0.0;
+        cf = dt;
+      } else if (s.p > 0.0) {
+        const double al_old = al;
+        cv = 1.0 - al;
+        if (np > a.n_min) {
+          dt = fmin(dt * a.f_inc, a.dtmax);
+          al = al * a.f_alpha;
+        }
+        np = np + 1;
+        cf = al_old * sqrt(s.vv) / sqrt(s.ff) + dt;
+      } else {
+        cv = 0.0;
+        al = a.alpha_start;
+        dt = dt * a.f_dec;
+        np = 0;
+        cf = dt;
+      }
+      const double vn2 = ((cv * cv) * s.vv + ((2.0 * cv) * cf) * s.p) + (cf * cf) * s.ff;   // |c_v v + c_f f|^2 from the same three sums
+      const double norm = dt * sqrt(fmax(vn2, 0.0));
+      const double d = norm > a.maxstep ? dt * (a.maxstep / norm) : dt;
+      a.dt[g] = dt;
+      a.alpha[g] = al;
+      a.n_pos[g] = np;
+      a.status[g] = XEQ_FIRE_ACTIVE;
+      a.coef[3 * g] = cv;
+      a.coef[3 * g + 1] = cf;
+      a.coef[3 * g + 2] = d;
+    }
+  }
+  if (row >= 0) {
+    a.traj_epot[row * a.n_graphs + g] = a.epot[g];
+    a.traj_fmax[row * a.n_graphs + g] = a.fmax[g];
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void fire_join(const FireBackArgs<T>& a) {
+  const int64_t eval = a.book[0];   // this evaluation's number: the first one is 0
+  const int64_t row = md_record_row_of(a.record_every, a.record_start, a.record_rows, eval);
+  int bad = 0;
+  md_join_graphs(
+      a.n_graphs, a.n_chunks, a.graph_chunk_ptr, [&]() { return FireSums{a.partial, a.partial_bad, 0.0, 0.0, 0.0, 0.0, 0}; },
+      [&](int64_t g, const FireSums& s) { fire_decide(a, g, row, eval, s, &bad); });
+  const int any_bad = __syncthreads_or(bad);   // (also orders the status stores above before the count below)
+  int64_t active = 0;
+  for (int64_t base = 0; base < a.n_graphs; base += blockDim.x) {
+    const int64_t g = base + threadIdx.x;
+    active += __syncthreads_count(g < a.n_graphs && a.status[g] != XEQ_FIRE_CONVERGED);
+  }
+  if (threadIdx.x == 0) {
+    const int64_t ne = (int64_t)a.n_edges_step[0];
+    a.book[0] = eval + 1;
+    if (ne > a.book[1]) a.book[1] = ne;
+    if (any_bad) a.book[2] = 1;
+    a.book[3] = active;
+    if (row >= 0) a.traj_step[row] = eval;
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(MD_JOIN_THREADS) k_fire_join(FireBackArgs<T> a) {
+  fire_join(a);
+}
+
+// One workgroup per chunk: the step's forces into the driver's copy (a fixed atom's entry zero, a converged graph's left alone), the
+// chunk's four partials over its free atoms and its non-finite flag, the recorder's positions.
+template <typename T>
+__global__ void __launch_bounds__(MD_CHUNK) k_fire_back(FireBackArgs<T> a) {
+  __shared__ double wsum[4][MD_CHUNK / 64];
+  const int c = blockIdx.x;
+  const int tid = threadIdx.x;
+  int cn = a.chunk_n[c];
+  cn = cn < 0 ? 0 : (cn > MD_CHUNK ? MD_CHUNK : cn);
+  const int64_t i = (int64_t)a.chunk_atom0[c] + tid;
+  double p = 0.0, ff = 0.0, vv = 0.0;
+  int bad = 0;
+  if (tid < cn && i >= 0 && i < a.n) {
+    int64_t g = a.batch[i];
+    g = g < 0 ? 0 : (g >= a.n_graphs ? a.n_graphs - 1 : g);
+    const bool frozen = a.status[g] == XEQ_FIRE_CONVERGED;
+    const bool fix = a.fixed && a.fixed[i];
+    double f[3], v[3];
+    for (int k = 0; k < 3; ++k) {
+      const T fk = a.frc_step[3 * i + k];
+      bad |= !isfinite((double)fk);
+      f[k] = fix ? 0.0 : (double)fk;
+      v[k] = fix ? 0.0 : (double)a.vel[3 * i + k];
+      if (!frozen) a.frc[3 * i + k] = fix ? T(0) : fk;
+    }
+    p = (f[0] * v[0] + f[1] * v[1]) + f[2] * v[2];
+    ff = (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2];
+    vv = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    const int64_t row = md_record_row_of(a.record_every, a.record_start, a.record_rows, a.book[0]);
+    if (row >= 0) {
+      for (int j = 0; j < 3; ++j) {
+        double x = (double)a.pos[3 * i + j];
+        if (a.box.any)
+          x = x + (((double)a.image[3 * i] * a.box.cell[j] + (double)a.image[3 * i + 1] * a.box.cell[3 + j]) +
+                   (double)a.image[3 * i + 2] * a.box.cell[6 + j]);
+        a.traj_pos[(row * a.n + i) * 3 + j] = (T)x;
+      }
+    }
+  }
+  const double m2 = md_wave_max(ff);   // (a lane's ff IS its atom's |f|^2)
+  p = md_wave_sum(p);
+  ff = md_wave_sum(ff);
+  vv = md_wave_sum(vv);
+  const int any_bad = __syncthreads_or(bad);
+  if ((tid & 63) == 0) {
+    wsum[0][tid >> 6] = p;
+    wsum[1][tid >> 6] = ff;
+    wsum[2][tid >> 6] = vv;
+    wsum[3][tid >> 6] = m2;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    double s = wsum[tid][0];
+    for (int w = 1; w < MD_CHUNK / 64; ++w) s = tid == 3 ? fmax(s, wsum[tid][w]) : s + wsum[tid][w];
+    a.partial[4 * (int64_t)c + tid] = s;
+    if (tid == 0) a.partial_bad[c] = any_bad ? 1 : 0;
+  }
+  if (a.n_chunks == 1) {   // the only chunk: its workgroup joins, decides and keeps the books itself, one launch less
+    __threadfence_block();
+    __syncthreads();
+    fire_join(a);
+  }
+}
+
+template <typename T>
+struct FireFrontArgs {
+  int64_t n, n_graphs;
+  T* pos;
+  T* vel;
+  const T* frc;
+  const uint8_t* fixed;
+  const int64_t* batch;
+  const int32_t* status;
+  const double* coef;
+  int32_t* image;
+  MdBox box;
+};
+
+// Per free atom of a graph that is not converged: v = c_v v + c_f f, x += d v, the wrap.  Nothing else is written.
+template <typename T>
+__global__ void __launch_bounds__(256) k_fire_front(FireFrontArgs<T> a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  if (a.fixed && a.fixed[i]) return;
+  int64_t g = a.batch[i];
+  g = g < 0 ? 0 : (g >= a.n_graphs ? a.n_graphs - 1 : g);
+  if (a.status[g] != XEQ_FIRE_ACTIVE) return;   // converged, or never evaluated: there are no coefficients
+  const double cv = a.coef[3 * g], cf = a.coef[3 * g + 1], d = a.coef[3 * g + 2];
+  double v[3], x[3];
+  for (int k = 0; k < 3; ++k) {
+    v[k] = cv * (double)a.vel[3 * i + k] + cf * (double)a.frc[3 * i + k];
+    x[k] = (double)a.pos[3 * i + k] + d * v[k];
+  }
+  if (a.box.any) {
+    int32_t img[3] = {a.image[3 * i], a.image[3 * i + 1], a.image[3 * i + 2]};
+    md_wrap<T>(a.box, x, img);
+    for (int k = 0; k < 3; ++k) a.image[3 * i + k] = img[k];
+  }
+  for (int k = 0; k < 3; ++k) {
+    a.vel[3 * i + k] = (T)v[k];
+    a.pos[3 * i + k] = (T)x[k];
   }
 }
 
@@ -465,6 +747,71 @@ int xeq_md_back(int dtype, int advance, int64_t n, int64_t n_graphs, int64_t n_c
     if (n_chunks != 1) hipLaunchKernelGGL(k_md_join<T>, dim3(1), dim3(n_graphs > 64 ? MD_JOIN_THREADS : 256), 0, (hipStream_t)stream, a);
   });
   XEQ_CHECK_LAUNCH("xeq_md_back");
+  return XEQ_OK;
+}
+
+int xeq_fire_front(int dtype, int64_t n, int64_t n_graphs, void* pos, void* vel, const void* frc, const uint8_t* fixed, const int64_t* batch,
+                   const int32_t* status, const double* coef, const double* cell, const int32_t* pbc, int32_t* image, void* stream) {
+  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_fire_front: dtype %d (0 f32, 1 f64)", dtype);
+  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3 && n_graphs >= 0, "xeq_fire_front: %lld atoms, %lld graphs", (long long)n, (long long)n_graphs);
+  XEQ_CHECK_ARG(n == 0 || n_graphs >= 1, "xeq_fire_front: %lld atoms in no graph", (long long)n);
+  MdBox box;
+  XEQ_CHECK_ARG(md_box(cell, pbc, &box), "xeq_fire_front: the cell is singular or not finite");
+  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && batch && status && coef), "xeq_fire_front: null state buffer");
+  XEQ_CHECK_ARG(n == 0 || !box.any || image, "xeq_fire_front: a periodic system needs the image counts");
+  if (n == 0) return XEQ_OK;
+  XEQ_DISPATCH_FLOAT(dtype, {
+    FireFrontArgs<T> a{n, n_graphs, (T*)pos, (T*)vel, (const T*)frc, fixed, batch, status, coef, image, box};
+    hipLaunchKernelGGL(k_fire_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  });
+  XEQ_CHECK_LAUNCH("xeq_fire_front");
+  return XEQ_OK;
+}
+
+int xeq_fire_back(int dtype, int64_t n, int64_t n_graphs, int64_t n_chunks, const void* pos, const void* vel, void* frc, const void* frc_step,
+                  const void* energy_step, const int32_t* n_edges_step, const uint8_t* fixed, const int64_t* batch, const int32_t* chunk_atom0,
+                  const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* epot, void* fmax, double* dt,
+                  double* alpha, int32_t* n_pos, int32_t* status, int64_t* converged_at, double* coef, int64_t* book, double fmax_tol,
+                  double maxstep, double dtmax, int n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, const double* cell,
+                  const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start, int64_t record_rows, void* traj_pos,
+                  void* traj_epot, void* traj_fmax, int64_t* traj_step, void* stream) {
+  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_fire_back: dtype %d (0 f32, 1 f64)", dtype);
+  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3 && n_graphs >= 0 && n_chunks >= 0 && n_chunks < ((int64_t)1 << 29),
+                "xeq_fire_back: %lld atoms, %lld graphs, %lld chunks", (long long)n, (long long)n_graphs, (long long)n_chunks);
+  XEQ_CHECK_ARG(n_chunks <= n && n_chunks * XEQ_MD_CHUNK >= n, "xeq_fire_back: %lld chunks of at most %d atoms cannot hold %lld atoms", (long long)n_chunks,
+                XEQ_MD_CHUNK, (long long)n);
+  XEQ_CHECK_ARG(n == 0 || n_graphs >= 1, "xeq_fire_back: %lld atoms in no graph", (long long)n);
+  XEQ_CHECK_ARG(fmax_tol > 0.0 && md_finite(fmax_tol), "xeq_fire_back: fmax %g", fmax_tol);
+  XEQ_CHECK_ARG(maxstep > 0.0 && dtmax > 0.0 && md_finite(maxstep) && md_finite(dtmax), "xeq_fire_back: maxstep %g, dtmax %g", maxstep, dtmax);
+  XEQ_CHECK_ARG(f_inc >= 1.0 && md_finite(f_inc) && f_dec > 0.0 && f_dec < 1.0 && alpha_start >= 0.0 && alpha_start <= 1.0 && f_alpha > 0.0 &&
+                    f_alpha <= 1.0 && n_min >= 0,
+                "xeq_fire_back: mixing parameters (f_inc %g, f_dec %g, alpha_start %g, f_alpha %g, n_min %d)", f_inc, f_dec, alpha_start, f_alpha, n_min);
+  XEQ_CHECK_ARG(record_every >= 0 && record_rows >= 0 && record_start >= 0, "xeq_fire_back: recorder (%lld, %lld, %lld)", (long long)record_every,
+                (long long)record_start, (long long)record_rows);
+  MdBox box;
+  XEQ_CHECK_ARG(md_box(cell, pbc, &box), "xeq_fire_back: the cell is singular or not finite");
+  XEQ_CHECK_ARG(book && n_edges_step, "xeq_fire_back: null evaluation counter or edge count");
+  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && frc_step && batch && chunk_atom0 && chunk_n && partial && partial_bad),
+                "xeq_fire_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(n_graphs == 0 || (energy_step && graph_chunk_ptr && epot && fmax && dt && alpha && n_pos && status && converged_at && coef),
+                "xeq_fire_back: null per-graph buffer");
+  const bool rec = record_every > 0 && record_rows > 0;
+  XEQ_CHECK_ARG(!rec || ((n == 0 || traj_pos) && (n_graphs == 0 || (traj_epot && traj_fmax)) && traj_step), "xeq_fire_back: null trajectory buffer");
+  XEQ_CHECK_ARG(!rec || n == 0 || !box.any || image, "xeq_fire_back: a periodic system's recorder needs the image counts");
+  XEQ_DISPATCH_FLOAT(dtype, {
+    FireBackArgs<T> a{n, n_graphs, n_chunks, (const T*)pos, (const T*)vel, (T*)frc, (const T*)frc_step, (const T*)energy_step, n_edges_step, fixed, batch,
+                      chunk_atom0, chunk_n, graph_chunk_ptr, partial, partial_bad, (T*)epot, (T*)fmax, dt, alpha, n_pos, status, converged_at, coef, book,
+                      fmax_tol, maxstep, dtmax, f_inc, f_dec, alpha_start, f_alpha, n_min, image, box, rec ? record_every : 0, record_start, record_rows,
+                      (T*)traj_pos, (T*)traj_epot, (T*)traj_fmax, traj_step};
+    if (n_chunks > 0) {
+      hipLaunchKernelGGL(k_fire_back<T>, dim3((unsigned)n_chunks), dim3(MD_CHUNK), 0, (hipStream_t)stream, a);
+      XEQ_CHECK_LAUNCH("xeq_fire_back");
+    }
+    if (n_chunks != 1) {
+      hipLaunchKernelGGL(k_fire_join<T>, dim3(1), dim3(n_graphs > 64 ? MD_JOIN_THREADS : 256), 0, (hipStream_t)stream, a);
+      XEQ_CHECK_LAUNCH("xeq_fire_back");
+    }
+  });
   return XEQ_OK;
 }
 

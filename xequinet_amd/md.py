@@ -19,17 +19,15 @@ those classes refuse are refused here by constructing them.  There is no CPU fal
 """
 from __future__ import annotations
 
-import ctypes
 import math
-from ctypes import c_void_p
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import keys, lib, ops
+from . import keys, lib
 from .lib import call, dtype_code, require_hip
-from .runtime import GraphedStep, GraphedStepPBC, pair_capacity
+from .resident import ResidentDriver, chunk_tables  # noqa: F401  (chunk_tables: part of this module's interface)
 from .utils import units as _units
 
 ENSEMBLES = {"nve": 0, "langevin": 1, "berendsen": 2}        # XEQ_MD_NVE / _LANGEVIN / _BERENDSEN of include/xeq.h
@@ -56,19 +54,6 @@ def default_rng_id(ptr_host) -> np.ndarray:
     return (np.arange(int(ptr_host[-1]), dtype=np.int64) - ptr_host[graph]) | (graph << 32)
 
 
-def chunk_tables(ptr_host, chunk: int = lib.MD_CHUNK):
-    """(chunk_atom0 int32 [C], chunk_n int32 [C], graph_chunk_ptr int32 [G + 1]): every graph cut into chunks of at most ``chunk`` atoms
-    counted from ITS first atom (an empty graph has none), in graph order."""
-    ptr_host = np.asarray(ptr_host, dtype=np.int64)
-    atom0, count, gptr = [], [], [0]
-    for a, b in zip(ptr_host[:-1], ptr_host[1:]):
-        for s in range(int(a), int(b), chunk):
-            atom0.append(s)
-            count.append(min(chunk, int(b) - s))
-        gptr.append(len(atom0))
-    return np.asarray(atom0, dtype=np.int32), np.asarray(count, dtype=np.int32), np.asarray(gptr, dtype=np.int32)
-
-
 def normals(seed: int, purpose: int, step: int, rng_id: torch.Tensor, dtype=torch.float32, want_words: bool = True):
     """(words uint32-as-int32 [n, 4] or None, normals [n, 3]) of the device generator (xeq_md_normals)."""
     require_hip(rng_id)
@@ -80,7 +65,7 @@ def normals(seed: int, purpose: int, step: int, rng_id: torch.Tensor, dtype=torc
     return words, out
 
 
-class Dynamics:
+class Dynamics(ResidentDriver):
     """``Dynamics(model, pos, atomic_numbers, masses, ptr=... | cell=..., timestep_fs=..., ensemble=...)``: see the module text and
     DESIGN.md section 12.  ``masses`` [N] in g / mol (0 or inf: a fixed atom); ``ensemble``: "nve" (velocity Verlet), "langevin" (BAOAB;
     ``temperature_K``, ``friction_per_fs``), "berendsen" (``temperature_K``, ``taut_fs``)."""
@@ -104,32 +89,8 @@ class Dynamics:
         N = int(pos.shape[0])
         if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,) or masses.shape != (N,):
             raise ValueError("Dynamics: pos [N, 3], atomic_numbers [N] and masses [N] are needed")
-        self.periodic = cell is not None
-        ptr_host = np.array([0, N], dtype=np.int64) if ptr is None else np.asarray(ptr.detach().cpu().numpy(), dtype=np.int64)
-        if ptr_host[0] != 0 or ptr_host[-1] != N or np.any(np.diff(ptr_host) < 0):
-            raise ValueError("Dynamics: ptr must rise from 0 to the atom count")
-        if self.periodic and len(ptr_host) != 2:
-            raise ValueError("Dynamics: a periodic system is ONE graph (GraphedStepPBC)")
-        self.ptr_host = ptr_host
-        self.n_atoms, self.n_graphs = N, len(ptr_host) - 1
-        cutoff = float((model if isinstance(model, torch.nn.Module) else model.model).cutoff_radius)
-        # the step object first: it refuses the models the whole-step classes do not take, whatever device the tensors are on
-        if self.periodic:
-            cell_h = np.asarray(cell.detach().double().cpu().numpy()).reshape(3, 3)
-            if edge_capacity is None:       # from the density; a list that outgrows it is met by the restore protocol
-                vol = abs(float(np.linalg.det(cell_h)))
-                edge_capacity = int(1.25 * N * (N / vol if vol > 0 else 0.0) * 4.0 / 3.0 * math.pi * cutoff**3) + 64
-            self.step = GraphedStepPBC(model, N, int(edge_capacity))
-            self._explicit_capacity = False
-        else:
-            self._explicit_capacity = edge_capacity is not None
-            self.step = GraphedStep(model, (N, self.n_graphs, int(pair_capacity(ptr_host) if edge_capacity is None else edge_capacity)))
-        require_hip(pos, atomic_numbers, masses, ptr, cell, rng_id)
-        dev, dt_ = self.step.pos.device, self.step.pos.dtype
-        if dev.type != "cuda":
-            raise RuntimeError("xequinet_amd ops run on MI355X (HIP) tensors only and have no CPU fallback; the model is on " + str(dev))
-        self.device, self.dtype = dev, dt_
-        self._code = dtype_code(self.step.pos)
+        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, masses, ptr, cell, rng_id))
+        ptr_host, dev, dt_ = self.ptr_host, self.device, self.dtype
 
         u = _units.get_default_units()
         self.energy_unit = energy_unit or u.get(keys.TOTAL_ENERGY, "eV")
@@ -156,9 +117,6 @@ class Dynamics:
         self.rng_id = (on(default_rng_id(ptr_host), torch.int64) if rng_id is None else rng_id.detach().to(torch.int64).contiguous().clone())
         if self.rng_id.shape != (N,):
             raise ValueError("Dynamics: rng_id [N]")
-        a0, cn, gp = chunk_tables(ptr_host)
-        self.n_chunks = len(a0)
-        self._chunk_atom0, self._chunk_n, self._graph_chunk_ptr = on(a0, torch.int32), on(cn, torch.int32), on(gp, torch.int32)
         self._partial = torch.zeros(max(self.n_chunks, 1), dtype=torch.float64, device=dev)
         self._partial_bad = torch.zeros(max(self.n_chunks, 1), dtype=torch.int32, device=dev)
 
@@ -180,20 +138,7 @@ class Dynamics:
         self._no_edges = torch.zeros(1, dtype=torch.int32, device=dev)
         self._run_serial = 0           # (part of the cache key of xeq_md_back's arguments: every run has its own trajectory buffers)
 
-        z = atomic_numbers.detach()
-        if self.periodic:
-            pbc_ = [True, True, True] if pbc is None else [bool(v) for v in (pbc.tolist() if isinstance(pbc, torch.Tensor) else pbc)]
-            self.step._load_cell(cell.detach().to(dt_).to(dev), pbc_)          # once: the box is fixed for the run
-            ops.copy_many([(self.step.pos, pos.detach().to(dt_).contiguous()), (self.step.z, z.to(torch.int32).contiguous())])
-            cell_t = self.step.cell.reshape(3, 3)
-            self._cell_dev = cell_t.double()
-            self._cell_c = (ctypes.c_double * 9)(*[float(v) for v in cell_t.double().cpu().reshape(-1).tolist()])
-            self._pbc_c = (ctypes.c_int32 * 3)(*[int(v) for v in pbc_])
-            self._any_pbc = any(pbc_)
-        else:
-            self.step._load(pos, z, torch.from_numpy(ptr_host).to(dev), None)
-            self._cell_dev, self._cell_c, self._pbc_c, self._any_pbc = None, None, None, False
-        self._pos = self.step.pos[:N]        # THE positions: the step's static buffer (a periodic system's are wrapped into the box)
+        self._load_system(pos, atomic_numbers, cell, pbc)
         call("xeq_md_front", *self._front_tuple(0.0), lib.stream())     # dt = 0: the wrap alone: the search sweeps +- reps images around the box, not around a stray atom
 
     # ------------------------------------------------------------------------------------------------ launches
@@ -210,11 +155,6 @@ class Dynamics:
             call("xeq_md_front", *self._front_args, lib.stream())
         else:
             call("xeq_md_front", *self._front_tuple(dt), lib.stream())
-
-    def _eval(self) -> None:
-        """The whole step on what the static buffers hold, through the step object's own logic (captured on first use, again when the
-        weights moved or the edge arrays grew)."""
-        self.step.replay()
 
     def _back_tuple(self, outputs, frc=None, energy=None, n_edges=None, record=True):
         p = lib.ptr
@@ -266,63 +206,21 @@ class Dynamics:
             if back(*ba):
                 raise RuntimeError(f"xeq_md_back failed: {L.xeq_last_error().decode()}")
 
-    def _read_book(self):
-        """THE read-back: (steps done, largest n_edges since the last check, non-finite flag).  A sync-debug guard of the caller is lifted
-        for exactly this call."""
-        mode = torch.cuda.get_sync_debug_mode()
-        if mode:
-            torch.cuda.set_sync_debug_mode(0)
-        try:
-            vals = self.book.cpu().tolist()
-        finally:
-            if mode:
-                torch.cuda.set_sync_debug_mode(mode)
-        return int(vals[0]), int(vals[1]), bool(vals[2])
-
-    # ------------------------------------------------------------------------------------------------ check / restore
+    # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
     def _state(self):
         return [self._pos, self.image, self.vel, self.frc, self.ke, self.epot, self.book]
 
-    def _save(self) -> None:
-        if self._ck is None:
-            self._ck = [torch.empty_like(t) for t in self._state()]
-        self.book[1:3].zero_()
-        ops.copy_many(list(zip(self._ck, self._state())))
-        self._ck_fresh = self._fresh
-
-    def _restore(self) -> None:
-        ops.copy_many(list(zip(self._state(), self._ck)))
-        self._fresh = self._ck_fresh
-
-    def _window(self, n: int) -> None:
-        """``n`` steps and one check behind them.  A list that outgrew the edge capacity voids the window: back to the checkpoint, more
-        room (GraphedStepPBC.grow), a new capture, the same steps again -- the random stream is a function of (seed, purpose, id, step),
-        so the second pass gives what a run with room from the start gives, bit for bit.  A non-finite force or energy also puts the
-        checkpoint back before it raises: the object stays at the last state that was checked."""
-        first = self._steps_host
+    def _before_window(self) -> None:
         if self._fresh and self._ke_stale:
             self._back_ke()
-        self._save()
-        while True:
-            if not self._fresh:
-                self._eval()
-                self._back(False)
-                self._fresh, self._ke_stale = True, False
-            self._enqueue(n)
-            steps, most, bad = self._read_book()
-            cap = self.step.n_edges
-            if most <= cap:
-                break
-            self._restore()
-            if not self.periodic:
-                raise ValueError(f"Dynamics: the neighbour list reached {most} edges, the edge capacity is {cap}" +
-                                 (" (edge_capacity was given: pass a larger one)" if self._explicit_capacity else ""))
-            self.step.grow(most)
-        if bad:
-            self._restore()
-            self.book[1:3].zero_()
-            raise FloatingPointError(f"Dynamics: non-finite force or energy in steps {first} .. {first + n}; the state is that of step {first}")
-        self._steps_host = steps
+
+    def _first_evaluation(self) -> None:
+        self._eval()
+        self._back(False)
+        self._fresh, self._ke_stale = True, False
+
+    def _bad_message(self, first: int, n: int) -> str:
+        return f"Dynamics: non-finite force or energy in steps {first} .. {first + n}; the state is that of step {first}"
 
     def _settle(self) -> None:
         if not self._fresh:
@@ -384,23 +282,6 @@ class Dynamics:
     @property
     def step_count(self) -> int:
         return self._steps_host
-
-    @property
-    def edge_capacity(self) -> int:
-        return self.step.n_edges
-
-    @property
-    def positions(self) -> torch.Tensor:
-        return self._pos.clone()
-
-    @property
-    def unwrapped_positions(self) -> torch.Tensor:
-        """pos + image . cell, in the operation order of the recorder (csrc/xeq_md.hip): the two agree bit for bit."""
-        if not self._any_pbc:
-            return self._pos.clone()
-        i, c = self.image.double(), self._cell_dev
-        x = self._pos.double()
-        return (x + ((i[:, 0:1] * c[0] + i[:, 1:2] * c[1]) + i[:, 2:3] * c[2])).to(self.dtype)
 
     @property
     def velocities(self) -> torch.Tensor:

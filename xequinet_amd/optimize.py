@@ -1,0 +1,255 @@
+"""Geometry optimisation that stays on the GPU: a batched FIRE minimiser next to the whole-step graphs of runtime.py.
+
+``FIRE`` lives next to a ``runtime.GraphedStep`` (a batch of open-boundary molecules, ``ptr``) or a ``runtime.GraphedStepPBC`` (one periodic
+box with a fixed cell, ``cell``) exactly as ``md.Dynamics`` does, and one iteration is
+
+    xeq_fire_front  (v = c_v v + c_f f, x += d v, wrap: writes the step object's static ``pos``)
+    the step's graph, replayed on its static buffers
+    xeq_fire_back   (per-graph P, ff, vv, fmax in a fixed order; the graph's FIRE state machine; counters; trajectory rows)
+
+enqueued on the current stream with no host synchronisation.  EVERY GRAPH IS ITS OWN FIRE SYSTEM -- its own time step, mixing factor,
+positive-power counter and convergence flag -- where ASE's ``optimize.FIRE`` (which the arithmetic restates; masses are not used) treats
+the whole ``Atoms`` as one; a converged graph is frozen bit for bit while the others go on.  Every ``check_every`` iterations the host
+reads four integers back and stops at the first check that finds no active graph.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional
+
+import torch
+
+from . import keys, lib
+from .lib import call
+from .resident import ResidentDriver
+from .utils import units as _units
+
+
+def time_step_factor(energy_unit: str, length_unit: str) -> float:
+    """sqrt(k), k = (eV / Angstrom per force unit) (length unit per Angstrom): ``dt`` and ``dtmax`` are given for eV and Angstrom as ASE
+    gives them, a move is x += dt^2 f and the mixing is scale-free, so in other units the two are scaled by this once and the kernels
+    see no unit."""
+    e_ev = _units.eval_unit(energy_unit) / _units.eval_unit("eV")               # one energy unit in eV
+    l_a = _units.eval_unit(length_unit) / _units.eval_unit("Angstrom")          # one length unit in Angstrom
+    return math.sqrt((e_ev / l_a) * (1.0 / l_a))
+
+
+class FIRE(ResidentDriver):
+    """``FIRE(model, pos, atomic_numbers, ptr=... | cell=..., fmax=...)``: see the module text and DESIGN.md section 13.  ``fixed``: bool [N],
+    atoms that never move.  ``fmax`` in the model's force unit, ``maxstep`` in its length unit, ``dt`` / ``dtmax`` as ASE gives them."""
+
+    def __init__(self, model, pos: torch.Tensor, atomic_numbers: torch.Tensor, *, ptr: Optional[torch.Tensor] = None, cell: Optional[torch.Tensor] = None,
+                 pbc=None, fixed: Optional[torch.Tensor] = None, fmax: float, dt: float = 0.1, maxstep: float = 0.2, dtmax: float = 1.0, n_min: int = 5,
+                 f_inc: float = 1.1, f_dec: float = 0.5, alpha_start: float = 0.1, f_alpha: float = 0.99, edge_capacity: Optional[int] = None,
+                 energy_unit: Optional[str] = None, length_unit: Optional[str] = None) -> None:
+        for name, v in (("fmax", fmax), ("dt", dt), ("dtmax", dtmax), ("maxstep", maxstep)):
+            if not (math.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError(f"FIRE: {name} {v} (> 0 is needed)")
+        if not 0.0 < float(f_dec) < 1.0:
+            raise ValueError(f"FIRE: f_dec {f_dec} (inside (0, 1))")
+        if not (math.isfinite(float(f_inc)) and float(f_inc) >= 1.0):
+            raise ValueError(f"FIRE: f_inc {f_inc} (>= 1)")
+        if not (0.0 <= float(alpha_start) <= 1.0 and 0.0 < float(f_alpha) <= 1.0 and int(n_min) >= 0):
+            raise ValueError(f"FIRE: alpha_start {alpha_start} (in [0, 1]), f_alpha {f_alpha} (in (0, 1]), n_min {n_min} (>= 0)")
+        N = int(pos.shape[0])
+        if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,):
+            raise ValueError("FIRE: pos [N, 3] and atomic_numbers [N] are needed")
+        if fixed is not None and fixed.shape != (N,):
+            raise ValueError(f"FIRE: fixed {tuple(fixed.shape)}, [N] = [{N}] is needed")
+        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, ptr, cell, fixed))
+        dev, dt_ = self.device, self.dtype
+
+        u = _units.get_default_units()
+        self.energy_unit = energy_unit or u.get(keys.TOTAL_ENERGY, "eV")
+        self.length_unit = length_unit or u.get(keys.POSITIONS, "Angstrom")
+        scale = time_step_factor(self.energy_unit, self.length_unit)
+        self.fmax_tol, self.maxstep = float(fmax), float(maxstep)
+        self.dt0, self.dtmax = float(dt) * scale, float(dtmax) * scale
+        self.n_min, self.f_inc, self.f_dec, self.alpha_start, self.f_alpha = int(n_min), float(f_inc), float(f_dec), float(alpha_start), float(f_alpha)
+
+        G, C = self.n_graphs, max(self.n_chunks, 1)
+        self.fixed = None if fixed is None else fixed.detach().to(torch.bool).contiguous().clone()
+        self._partial = torch.zeros((C, 4), dtype=torch.float64, device=dev)
+        self._partial_bad = torch.zeros(C, dtype=torch.int32, device=dev)
+        self.vel = torch.zeros((N, 3), dtype=dt_, device=dev)
+        self.frc = torch.zeros((N, 3), dtype=dt_, device=dev)
+        self.image = torch.zeros((N, 3), dtype=torch.int32, device=dev)
+        self.epot = torch.zeros(G, dtype=dt_, device=dev)
+        self.fmax = torch.zeros(G, dtype=dt_, device=dev)
+        self.dt = torch.full((G,), self.dt0, dtype=torch.float64, device=dev)
+        self.alpha = torch.full((G,), self.alpha_start, dtype=torch.float64, device=dev)
+        self.n_pos = torch.zeros(G, dtype=torch.int32, device=dev)
+        self.status = torch.full((G,), lib.FIRE_FRESH, dtype=torch.int32, device=dev)
+        self._converged_at = torch.full((G,), -1, dtype=torch.int64, device=dev)
+        self.coef = torch.zeros((G, 3), dtype=torch.float64, device=dev)
+        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # evaluations done, largest n_edges, non-finite flag, graphs not converged
+        self._ck = None
+        self._steps_host = 0           # evaluations done
+        self._active_host = G
+        self._fresh = False            # frc / epot / fmax / coef belong to the current positions
+        self._rec = (0, 0, 0)
+        self.trajectory: Dict[str, torch.Tensor] = {}
+        self._back_args = None
+        self._front_args = None
+        self._run_serial = 0           # (part of the cache key of xeq_fire_back's arguments: every run has its own trajectory buffers)
+
+        self._load_system(pos, atomic_numbers, cell, pbc)
+        if self._any_pbc:              # the wrap alone (c_v = c_f = d = 0 on zero velocities and forces): the search sweeps images around the box
+            p = lib.ptr
+            every = torch.full((G,), lib.FIRE_ACTIVE, dtype=torch.int32, device=dev)
+            call("xeq_fire_front", self._code, N, G, p(self._pos), p(self.vel), p(self.frc), None, p(self.step.batch), p(every), p(self.coef),
+                 self._cell_c, self._pbc_c, p(self.image), lib.stream())
+
+    # ------------------------------------------------------------------------------------------------ launches
+    def _front_tuple(self):
+        p = lib.ptr
+        return (self._code, self.n_atoms, self.n_graphs, p(self._pos), p(self.vel), p(self.frc), p(self.fixed), p(self.step.batch), p(self.status),
+                p(self.coef), self._cell_c, self._pbc_c, p(self.image))
+
+    def _back_tuple(self, outputs):
+        p = lib.ptr
+        frc, en, ne = outputs[keys.FORCES], outputs[keys.TOTAL_ENERGY], outputs["n_edges"]
+        assert frc.is_contiguous() and frc.dtype == self.dtype and en.is_contiguous() and en.dtype == self.dtype and ne.dtype == torch.int32
+        t = self.trajectory
+        every, start, rows = self._rec
+        return (self._code, self.n_atoms, self.n_graphs, self.n_chunks, p(self._pos), p(self.vel), p(self.frc), p(frc), p(en), p(ne), p(self.fixed),
+                p(self.step.batch), p(self._chunk_atom0), p(self._chunk_n), p(self._graph_chunk_ptr), p(self._partial), p(self._partial_bad),
+                p(self.epot), p(self.fmax), p(self.dt), p(self.alpha), p(self.n_pos), p(self.status), p(self._converged_at), p(self.coef),
+                p(self.book), self.fmax_tol, self.maxstep, self.dtmax, self.n_min, self.f_inc, self.f_dec, self.alpha_start, self.f_alpha,
+                self._cell_c, self._pbc_c, p(self.image), every, start, rows, p(t.get("pos")), p(t.get("epot")), p(t.get("fmax")), p(t.get("step")))
+
+    def _args(self):
+        """The two argument tuples, bound once: every buffer named there lives as long as this object, except the step's outputs (a new
+        capture) and the trajectory (a new run)."""
+        if self._front_args is None:
+            self._front_args = self._front_tuple()
+        key = (self.step.captures, self._rec, self._run_serial)
+        if self._back_args is None or self._back_args[0] != key:
+            self._back_args = (key, self._back_tuple(self.step.outputs))
+        return self._front_args, self._back_args[1]
+
+    def _first_evaluation(self) -> None:
+        self._eval()
+        call("xeq_fire_back", *self._args()[1], lib.stream())
+        self._fresh = True
+
+    def _enqueue(self, n: int) -> None:
+        """``n`` iterations on the current stream; nothing here waits for the device.  The first evaluation goes through the step object's
+        logic; nothing can move the weights between that one and the window's check, so the others replay the graph it left."""
+        if n <= 0:
+            return
+        L = lib.load()
+        front, back = L.xeq_fire_front, L.xeq_fire_back
+        stream = lib.stream()
+        for k in range(n):
+            if k == 0:
+                fa = (*self._args()[0], stream)
+            if front(*fa):
+                raise RuntimeError(f"xeq_fire_front failed: {L.xeq_last_error().decode()}")
+            if k == 0:
+                self._eval()
+                ba = (*self._args()[1], stream)          # (behind the evaluation: a new capture has new output buffers)
+                replay = self.step.graph.replay
+            else:
+                replay()
+            if back(*ba):
+                raise RuntimeError(f"xeq_fire_back failed: {L.xeq_last_error().decode()}")
+
+    # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
+    def _state(self):
+        return [self._pos, self.image, self.vel, self.frc, self.epot, self.fmax, self.dt, self.alpha, self.n_pos, self.status, self._converged_at,
+                self.coef, self.book]
+
+    def _bad_message(self, first: int, n: int) -> str:
+        return (f"FIRE: non-finite force or energy in evaluations {first} .. {first + n}; the state is that "
+                + (f"behind evaluation {first - 1}" if first else "of the start"))
+
+    def _window(self, n: int) -> None:
+        super()._window(n)
+        self._active_host = self._book_extra
+
+    # ------------------------------------------------------------------------------------------------ public
+    def run(self, max_steps: int, check_every: int = 20, record_every: int = 0) -> bool:
+        """At most ``max_steps`` iterations in windows of ``check_every``; True when every graph has converged.  With ``record_every`` the
+        state behind every ``record_every``-th evaluation of this run goes to ``trajectory`` (pos, epot, fmax, step; rows the run did not
+        reach stay zero)."""
+        max_steps, check_every, record_every = int(max_steps), max(1, int(check_every)), max(0, int(record_every))
+        if max_steps < 0:
+            raise ValueError("FIRE.run: max_steps < 0")
+        self._run_serial += 1
+        if record_every > 0:
+            rows = max_steps // record_every
+            mk = lambda *shape: torch.zeros(shape, dtype=self.dtype, device=self.device)
+            self.trajectory = {"pos": mk(rows, self.n_atoms, 3), "epot": mk(rows, self.n_graphs), "fmax": mk(rows, self.n_graphs),
+                               "step": torch.zeros(rows, dtype=torch.int64, device=self.device)}
+            self._rec = (record_every, self.step_count, rows)
+        else:
+            self.trajectory, self._rec = {}, (0, 0, 0)
+        if not self._fresh:
+            self._window(0)            # evaluation 0: a start that is already relaxed moves nothing
+        done = 0
+        while done < max_steps and self._active_host > 0:
+            w = min(check_every, max_steps - done)
+            self._window(w)
+            done += w
+        return self._active_host == 0
+
+    def reset(self) -> None:
+        """Every graph fresh and active again, v = 0, from the current positions; the evaluation count starts over."""
+        self.vel.zero_()
+        self.dt.fill_(self.dt0)
+        self.alpha.fill_(self.alpha_start)
+        self.n_pos.zero_()
+        self.status.fill_(lib.FIRE_FRESH)
+        self._converged_at.fill_(-1)
+        self.coef.zero_()
+        self.book.zero_()
+        self._steps_host, self._active_host, self._fresh = 0, self.n_graphs, False
+
+    def _settle(self) -> None:
+        if not self._fresh:
+            self._window(0)
+
+    @property
+    def step_count(self) -> int:
+        """Iterations done: the number of the latest evaluation (the first one is 0)."""
+        return max(self._steps_host - 1, 0)
+
+    @property
+    def forces(self) -> torch.Tensor:
+        self._settle()
+        return self.frc.clone()
+
+    @property
+    def potential_energy(self) -> torch.Tensor:
+        self._settle()
+        return self.epot.clone()
+
+    @property
+    def max_force(self) -> torch.Tensor:
+        self._settle()
+        return self.fmax.clone()
+
+    @property
+    def converged(self) -> torch.Tensor:
+        self._settle()
+        return self.status == lib.FIRE_CONVERGED
+
+    @property
+    def converged_at(self) -> torch.Tensor:
+        self._settle()
+        return self._converged_at.clone()
+
+    @property
+    def time_steps(self) -> torch.Tensor:
+        return self.dt.clone()
+
+
+def minimize(model, data: Dict[str, torch.Tensor], fmax: float, max_steps: int = 500, check_every: int = 20, **kw) -> Dict[str, torch.Tensor]:
+    """``FIRE`` on a data dict (``pos``, ``atomic_numbers``, ``ptr`` or ``cell`` [, ``pbc``]): -> ``pos``, ``energy`` [G], ``forces``,
+    ``converged`` [G] and ``n_steps`` (iterations done)."""
+    cell = data.get(keys.CELL)
+    opt = FIRE(model, data[keys.POSITIONS], data[keys.ATOMIC_NUMBERS], ptr=None if cell is not None else data.get("ptr"), cell=cell,
+               pbc=data.get(keys.PBC) if cell is not None else None, fmax=fmax, **kw)
+    opt.run(max_steps, check_every=check_every)
+    return {"pos": opt.positions, "energy": opt.potential_energy, "forces": opt.forces, "converged": opt.converged, "n_steps": opt.step_count}

@@ -1,0 +1,168 @@
+"""What the drivers that live next to a whole-step graph share (md.Dynamics, optimize.FIRE; DESIGN.md sections 12 and 13): the step object
+and its static buffers, the chunk tables of the fixed-order per-graph sums, the one read-back per window, and the window / checkpoint /
+restore / grow protocol for a neighbour list that outgrows its capacity.  A driver supplies its own two launches and its own state.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import lib, ops
+from .lib import dtype_code, require_hip
+from .runtime import GraphedStep, GraphedStepPBC, pair_capacity
+
+
+def chunk_tables(ptr_host, chunk: int = lib.MD_CHUNK):
+    """(chunk_atom0 int32 [C], chunk_n int32 [C], graph_chunk_ptr int32 [G + 1]): every graph cut into chunks of at most ``chunk`` atoms
+    counted from ITS first atom (an empty graph has none), in graph order."""
+    ptr_host = np.asarray(ptr_host, dtype=np.int64)
+    atom0, count, gptr = [], [], [0]
+    for a, b in zip(ptr_host[:-1], ptr_host[1:]):
+        for s in range(int(a), int(b), chunk):
+            atom0.append(s)
+            count.append(min(chunk, int(b) - s))
+        gptr.append(len(atom0))
+    return np.asarray(atom0, dtype=np.int32), np.asarray(count, dtype=np.int32), np.asarray(gptr, dtype=np.int32)
+
+
+class ResidentDriver:
+    """Base of the device-resident drivers.  A subclass sets, before the first window: ``book`` (int64 [4] on the device: entry 0 its
+    counter, 1 the largest n_edges seen, 2 the non-finite flag, 3 its own), ``_steps_host``, ``_fresh`` (forces and energies belong to
+    the current positions), ``_ck = None``; and defines ``_state()`` (the tensors of a checkpoint), ``_first_evaluation()``,
+    ``_enqueue(n)``, ``_bad_message(first, n)`` and, if it needs one, ``_before_window()``."""
+
+    def _init_system(self, model, N: int, ptr: Optional[torch.Tensor], cell: Optional[torch.Tensor], edge_capacity: Optional[int], tensors) -> None:
+        """The step object FIRST -- it refuses the models the whole-step classes do not take, whatever device the tensors are on -- then
+        the no-CPU-fallback checks, the device, the state type and the chunk tables."""
+        who = type(self).__name__
+        self.periodic = cell is not None
+        ptr_host = np.array([0, N], dtype=np.int64) if ptr is None else np.asarray(ptr.detach().cpu().numpy(), dtype=np.int64)
+        if ptr_host[0] != 0 or ptr_host[-1] != N or np.any(np.diff(ptr_host) < 0):
+            raise ValueError(f"{who}: ptr must rise from 0 to the atom count")
+        if self.periodic and len(ptr_host) != 2:
+            raise ValueError(f"{who}: a periodic system is ONE graph (GraphedStepPBC)")
+        self.ptr_host = ptr_host
+        self.n_atoms, self.n_graphs = N, len(ptr_host) - 1
+        cutoff = float((model if isinstance(model, torch.nn.Module) else model.model).cutoff_radius)
+        if self.periodic:
+            cell_h = np.asarray(cell.detach().double().cpu().numpy()).reshape(3, 3)
+            if edge_capacity is None:       # from the density; a list that outgrows it is met by the restore protocol
+                vol = abs(float(np.linalg.det(cell_h)))
+                edge_capacity = int(1.25 * N * (N / vol if vol > 0 else 0.0) * 4.0 / 3.0 * math.pi * cutoff**3) + 64
+            self.step = GraphedStepPBC(model, N, int(edge_capacity))
+            self._explicit_capacity = False
+        else:
+            self._explicit_capacity = edge_capacity is not None
+            self.step = GraphedStep(model, (N, self.n_graphs, int(pair_capacity(ptr_host) if edge_capacity is None else edge_capacity)))
+        require_hip(*tensors)
+        dev, dt_ = self.step.pos.device, self.step.pos.dtype
+        if dev.type != "cuda":
+            raise RuntimeError("xequinet_amd ops run on MI355X (HIP) tensors only and have no CPU fallback; the model is on " + str(dev))
+        self.device, self.dtype = dev, dt_
+        self._code = dtype_code(self.step.pos)
+        a0, cn, gp = chunk_tables(ptr_host)
+        self.n_chunks = len(a0)
+        on = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32).to(dev)
+        self._chunk_atom0, self._chunk_n, self._graph_chunk_ptr = on(a0), on(cn), on(gp)
+
+    def _load_system(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, cell: Optional[torch.Tensor], pbc) -> None:
+        """Positions, species and (once: the box is fixed for the run) the cell into the step object's static buffers."""
+        N, dev, dt_ = self.n_atoms, self.device, self.dtype
+        z = atomic_numbers.detach()
+        if self.periodic:
+            pbc_ = [True, True, True] if pbc is None else [bool(v) for v in (pbc.tolist() if isinstance(pbc, torch.Tensor) else pbc)]
+            self.step._load_cell(cell.detach().to(dt_).to(dev), pbc_)
+            ops.copy_many([(self.step.pos, pos.detach().to(dt_).contiguous()), (self.step.z, z.to(torch.int32).contiguous())])
+            cell_t = self.step.cell.reshape(3, 3)
+            self._cell_dev = cell_t.double()
+            self._cell_c = (ctypes.c_double * 9)(*[float(v) for v in cell_t.double().cpu().reshape(-1).tolist()])
+            self._pbc_c = (ctypes.c_int32 * 3)(*[int(v) for v in pbc_])
+            self._any_pbc = any(pbc_)
+        else:
+            self.step._load(pos, z, torch.from_numpy(self.ptr_host).to(dev), None)
+            self._cell_dev, self._cell_c, self._pbc_c, self._any_pbc = None, None, None, False
+        self._pos = self.step.pos[:N]        # THE positions: the step's static buffer (a periodic system's are wrapped into the box)
+
+    def _eval(self) -> None:
+        """The whole step on what the static buffers hold, through the step object's own logic (captured on first use, again when the
+        weights moved or the edge arrays grew)."""
+        self.step.replay()
+
+    def _read_book(self):
+        """THE read-back: (counter, largest n_edges since the last check, non-finite flag); the fourth entry is kept in ``_book_extra``.
+        A sync-debug guard of the caller is lifted for exactly this call."""
+        mode = torch.cuda.get_sync_debug_mode()
+        if mode:
+            torch.cuda.set_sync_debug_mode(0)
+        try:
+            vals = self.book.cpu().tolist()
+        finally:
+            if mode:
+                torch.cuda.set_sync_debug_mode(mode)
+        self._book_extra = int(vals[3])
+        return int(vals[0]), int(vals[1]), bool(vals[2])
+
+    # ------------------------------------------------------------------------------------------------ check / restore
+    def _save(self) -> None:
+        if self._ck is None:
+            self._ck = [torch.empty_like(t) for t in self._state()]
+        self.book[1:3].zero_()
+        ops.copy_many(list(zip(self._ck, self._state())))
+        self._ck_fresh = self._fresh
+
+    def _restore(self) -> None:
+        ops.copy_many(list(zip(self._state(), self._ck)))
+        self._fresh = self._ck_fresh
+
+    def _before_window(self) -> None:
+        pass
+
+    def _window(self, n: int) -> None:
+        """``n`` steps and one check behind them.  A list that outgrew the edge capacity voids the window: back to the checkpoint, more
+        room (GraphedStepPBC.grow), a new capture, the same steps again -- everything a step uses is a function of the checkpointed state
+        (the random stream of the dynamics of (seed, purpose, id, step)), so the second pass gives what a run with room from the start
+        gives, bit for bit.  A non-finite force or energy also puts the checkpoint back before it raises: the object stays at the last
+        state that was checked."""
+        who = type(self).__name__
+        first = self._steps_host
+        self._before_window()
+        self._save()
+        while True:
+            if not self._fresh:
+                self._first_evaluation()
+            self._enqueue(n)
+            steps, most, bad = self._read_book()
+            cap = self.step.n_edges
+            if most <= cap:
+                break
+            self._restore()
+            if not self.periodic:
+                raise ValueError(f"{who}: the neighbour list reached {most} edges, the edge capacity is {cap}" +
+                                 (" (edge_capacity was given: pass a larger one)" if self._explicit_capacity else ""))
+            self.step.grow(most)
+        if bad:
+            self._restore()
+            self.book[1:3].zero_()
+            raise FloatingPointError(self._bad_message(first, n))
+        self._steps_host = steps
+
+    @property
+    def edge_capacity(self) -> int:
+        return self.step.n_edges
+
+    @property
+    def positions(self) -> torch.Tensor:
+        return self._pos.clone()
+
+    @property
+    def unwrapped_positions(self) -> torch.Tensor:
+        """pos + image . cell, in the operation order of the recorder (csrc/xeq_md.hip): the two agree bit for bit."""
+        if not self._any_pbc:
+            return self._pos.clone()
+        i, c = self.image.double(), self._cell_dev
+        x = self._pos.double()
+        return (x + ((i[:, 0:1] * c[0] + i[:, 1:2] * c[1]) + i[:, 2:3] * c[2])).to(self.dtype)
