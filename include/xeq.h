@@ -770,7 +770,7 @@ int xeq_mlp2_and_linear(int reverse, const float* x, int64_t ldx, int64_t n, int
                         int n2, float* pre, float* y, int64_t ldy, const float* lin_x, int64_t lin_ldx, int lin_k,
                         const float* lin_w_packed, int lin_n_out, float* lin_y, int64_t lin_ldy, void* stream);
 
-/* ---- first half of XPainnUpdate.forward in one launch (f32; mul_l in {0, 32, 64, 128}, node_dim <= 128, D <= 504) -------
+/* ---- first half of XPainnUpdate.forward in one launch (f32; mul_l in {0, 32, 64, 128}, node_dim % 4 == 0, <= 128, D <= 480) ---
  * nn.LayerNorm(s) and EquivariantLayerNorm(x) (nn/xpainn.py:208-209), U = update_U(xhat), V = update_V(xhat) (o3.Linear,
  * nn/xpainn.py:211-212), v = Invariant(V), p = EquivariantDot(U, V) (nn/xpainn.py:214, :222).  Replaces xeq_norm_fwd + the
  * three GEMMs + xeq_uv_reduce_fwd; outputs as theirs: cat[n, :node_dim] = shat, cat[n, node_dim:node_dim + C] = v (row stride

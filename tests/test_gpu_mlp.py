@@ -144,8 +144,7 @@ def test_update_block_fused_front_matches_the_kernel_chain(monkeypatch, n, irrep
         return so.detach().double(), xo.detach().double(), g[0].double(), g[1].double()
 
     got = run(blk, torch.float32)
-    if node_dim == 128:
-        assert getattr(blk, "_uv_frag", None) is not None, "the fused front did not run"
+    assert getattr(blk, "_uv_frag", None) is not None, "the fused front did not run"
     monkeypatch.setattr(fused, "_packed_uv_frag", lambda module: None)
     chain = run(blk, torch.float32)
     import copy

@@ -12,6 +12,7 @@
 // channels for every m with exact-f32 v_mfma_f32_32x32x2_f32 (weights as the A operand: a lane holds four consecutive
 // channels of one node per register quad, so every store is 16 bytes), from weights packed in fragment order
 // (xeq_mlp_pack of [W_U | W_V] / sqrt(mul), the l = 0 biases as one more k-group).
+// Fixed: with layer norms and no l = 0 block the forward entry point refused the NULL pointer of the empty affine_bias ("null buffer").
 #include <type_traits>
 
 #include "xeq_packed_w.h"
@@ -877,7 +878,8 @@ int xeq_update_uv_fwd(const float* s, const float* x, const float* ln_w, const f
   if (n == 0) return XEQ_OK;
   const float* wp[3] = {w_packed0, w_packed1, w_packed2};
   for (int l = 0; l < 3; ++l) XEQ_CHECK_ARG(mul[l] == 0 || wp[l], "xeq_update_uv_fwd: packed weights of l = %d missing", l);
-  XEQ_CHECK_ARG(s && x && cat && p && uv_bt && stats && (!do_norm || (ln_w && ln_b && eq_w && eq_b)), "xeq_update_uv_fwd: null buffer");
+  XEQ_CHECK_ARG(s && x && cat && p && uv_bt && stats && (!do_norm || (ln_w && ln_b && eq_w && (eq_b || mul[0] == 0))),
+                "xeq_update_uv_fwd: null buffer");   // (l = 0 absent: affine_bias is empty and its pointer NULL; nothing reads it)
   UvFwdArgs a;
   a.s = s; a.x = x; a.lnw = ln_w; a.lnb = ln_b; a.eqw = eq_w; a.eqb = eq_b;
   a.do_norm = do_norm; a.n = n; a.F = node_dim; a.ir = ir;
