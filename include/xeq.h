@@ -1070,6 +1070,42 @@ int xeq_fire_back(int dtype, int64_t n, int64_t n_graphs, int64_t n_chunks, cons
                   const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start, int64_t record_rows, void* traj_pos,
                   void* traj_epot, void* traj_fmax, int64_t* traj_step, void* stream);
 
+/* Batched harmonic analysis behind the Hessian front (xequinet_amd/vibrations.py, csrc/xeq_vib.hip).  Everything is
+ * f64; only the Hessian is read as `dtype` and widened on load.  One workgroup per graph, fixed summation orders, no atomics: a graph's
+ * result has the same bits alone and anywhere in a batch.  Graph g has n = ptr[g + 1] - ptr[g] atoms and m = 3 n coordinates.
+ *
+ * xeq_vib_project: hess holds the graphs' [n, n, 3, 3] blocks at the element offsets hess_off [n_graphs]; pos [N, 3]; mass [N] in amu.
+ *   Writes per graph: mass_tot, moments [3] (ascending) and axes [9] (rows) of the inertia tensor about the centre of mass, rotor
+ *   (XEQ_VIB_ATOM / _LINEAR: smallest moment <= 1e-6 x the largest / _NONLINEAR), n_tr (3 for an atom or with `periodic`, 5 linear, 6
+ *   otherwise), q [6, m] at 18 ptr[g] (rows < n_tr: the orthonormal mass-weighted translations and rotations about the principal axes
+ *   with a non-vanishing moment, modified Gram-Schmidt in that order), sigma = 2 |P S P|_F (1 when that is 0) and, at mat_off[g],
+ *   M [m, m] = P S P + sigma Q Q^T with S = m^-1/2 (H + H^T)/2 m^-1/2, P = I - Q Q^T, formed through the rank-n_tr products.  work: scratch
+ *   of q's shape.  With `periodic` no inertia tensor is formed (moments 0).  No size cap: it works in global memory.
+ * xeq_vib_eigh: n symmetric matrices, matrix g of dimension dim[g] at mat_off[g]; eigenvalues ascending at val_off[g], eigenvectors
+ *   [dim, dim] at mat_off[g] of `eigenvectors`, vector k contiguous, its largest-magnitude component (lowest index on a tie) positive;
+ *   sweeps [n]; status [n]: 0, or 1 when XEQ_VIB_MAX_SWEEPS sweeps did not reach off(A) <= dim 2^-53 |A|_F.  Two-sided cyclic Jacobi in
+ *   round-robin ordering, A and V in LDS sized from max_dim (>= every dim[g]); max_dim > XEQ_VIB_MAX_DIM is refused with
+ *   XEQ_ERR_INVALID_ARGUMENT before any launch.
+ * xeq_vib_finish: from the lowest m - n_tr eigenpairs of graph g (eigenvalues at 3 ptr[g]), at mode_ptr[g] (norm_mode [k, n, 3] at
+ *   mode_off[g]): eigenvalue, norm_mode = m_i^-1/2 v_k, reduced_mass = 1 / sum norm_mode^2, freq_wavenumber = sign(l) sqrt(|l|)
+ *   to_wavenumber, vib_temperature = sign(l) sqrt(|l|) to_kelvin, force_const = reduced_mass l; n_imaginary [n_graphs].
+ * xeq_vib_thermo_sums: sums [n_graphs, 4] over the modes with eigenvalue > 0, x = vib_temperature / temperature:
+ *   theta / 2, theta / (e^x - 1), x / (e^x - 1) - ln(1 - e^-x), x^2 e^x / (e^x - 1)^2. */
+#define XEQ_VIB_MAX_DIM 96
+#define XEQ_VIB_MAX_SWEEPS 30
+enum { XEQ_VIB_ATOM = 0, XEQ_VIB_LINEAR = 1, XEQ_VIB_NONLINEAR = 2 };
+int xeq_vib_project(int dtype, const void* hess, const int64_t* hess_off, const double* pos, const double* mass, const int64_t* ptr,
+                    int64_t n_graphs, int periodic, const int64_t* mat_off, double* mat, double* q, double* work, double* moments, double* axes,
+                    double* mass_tot, int32_t* n_tr, int32_t* rotor, double* sigma, void* stream);
+int xeq_vib_eigh(const double* mat, const int64_t* mat_off, const int64_t* val_off, const int32_t* dim, int64_t n, int max_dim,
+                 double* eigenvalues, double* eigenvectors, int32_t* sweeps, int32_t* status, void* stream);
+int xeq_vib_finish(const double* eigenvalues, const double* eigenvectors, const int64_t* mat_off, const double* mass, const int64_t* ptr,
+                   int64_t n_graphs, const int32_t* n_tr, const int64_t* mode_ptr, const int64_t* mode_off, double to_wavenumber, double to_kelvin,
+                   double* eigenvalue, double* norm_mode, double* reduced_mass, double* freq_wavenumber, double* vib_temperature,
+                   double* force_const, int32_t* n_imaginary, void* stream);
+int xeq_vib_thermo_sums(const double* vib_temperature, const double* eigenvalue, const int64_t* mode_ptr, int64_t n_graphs, double temperature,
+                        double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

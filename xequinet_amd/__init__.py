@@ -22,4 +22,8 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(".optimize", __name__)
+    if name == "vibrations":     # batched harmonic analysis and thermochemistry behind hessian() (vibrations.py), likewise
+        import importlib
+
+        return importlib.import_module(".vibrations", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

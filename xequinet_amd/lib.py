@@ -19,6 +19,8 @@ XEQ_F32, XEQ_F64 = 0, 1
 COPY_MANY_MAX = 16       # XEQ_COPY_MANY_MAX of include/xeq.h
 MD_CHUNK = 256          # XEQ_MD_CHUNK of include/xeq.h: atoms per kinetic-energy chunk (md.py, optimize.py)
 FIRE_FRESH, FIRE_ACTIVE, FIRE_CONVERGED = 0, 1, 2      # XEQ_FIRE_* of include/xeq.h
+VIB_MAX_DIM, VIB_MAX_SWEEPS = 96, 30     # XEQ_VIB_MAX_DIM, XEQ_VIB_MAX_SWEEPS of include/xeq.h (vibrations.py)
+VIB_ROTORS = ("atom", "linear", "nonlinear")      # XEQ_VIB_ATOM, _LINEAR, _NONLINEAR
 SB_ACCUM_VEC = 16        # XEQ_SB_ACCUM_VEC of include/xeq.h: xeq_message_bwd_sb adds dL/dvec to the buffer it is handed
 XHAT_HIGHER_L_ZERO = 2   # XEQ_XHAT_HIGHER_L_ZERO of include/xeq.h: hint bit on the xhat_layout argument of the wq message kernels
 SB_Y0_ZERO = 8           # XEQ_SB_Y0_ZERO / XEQ_SB_Q_ACCUMULATE: the training-pass forms of the sb message kernels (ops.DiffMessage)
@@ -237,6 +239,10 @@ _PROTOS = {
     "xeq_fire_back": [c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                       c_double, c_double, c_double, c_int, c_double, c_double, c_double, c_double, ctypes.POINTER(c_double), _I3, _P, c_int64, c_int64,
                       c_int64, _P, _P, _P, _P, _P],
+    "xeq_vib_project": [c_int, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "xeq_vib_eigh": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],
+    "xeq_vib_finish": [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P],
+    "xeq_vib_thermo_sums": [_P, _P, _P, c_int64, c_double, _P, _P],
 }
 # entry points that return a size, not a status
 _RET_I64 = {"xeq_launch_count", "xeq_launch_names", "xeq_message_wq_packed_weight_floats", "xeq_rowptr_from_degrees_max", "xeq_csr_by_key_workspace", "xeq_message_wq_pcap", "xeq_message_wq_plan_workspace", "xeq_message_wq_win_ints",
