@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libxeq_hip.so")
 SOURCES = ["xeq_graph.hip", "xeq_ops.hip", "xeq_message.hip", "xeq_message_sb.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.hip", "xeq_node.hip", "xeq_mlp.hip", "xeq_linear.hip", "xeq_update.hip", "xeq_nodeblock.hip", "xeq_tp.hip", "xeq_train.hip", "xeq_train_node.hip", "xeq_train_edge.hip", "xeq_electronic.hip", "xeq_painn.hip", "xeq_heads.hip", "xeq_ewald.hip", "xeq_md.hip", "xeq_vib.hip"]
-HEADERS = ["xeq_common.h", "xeq_packed_w.h", "xeq_linear_s.h", os.path.join("..", "..", "include", "xeq.h")]
+HEADERS = ["xeq_common.h", "xeq_packed_w.h", "xeq_linear_s.h", "xeq_message_wq.h", os.path.join("..", "..", "include", "xeq.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # per-source extras.  The matrix-core message kernels: LLVM's max-ILP machine scheduler instead of the default (measured in round 1 on
 # their predecessor: reverse launch 573 -> 544 us, same VGPR budgets).
@@ -29,7 +29,7 @@ MFMA_SOURCES = ["xeq_nodeblock.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.h
 EXTRA_FLAGS = {"xeq_nodeblock.hip": [],
                # wq: explicit fma chains only (its window / global instantiations must round alike)
                "xeq_message_wq.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"],
-               # its reverse half (same text, XEQ_WQ_PART_BWD): the default scheduler orders the unfenced reverse tile better
+               # the reverse kernel (both include xeq_message_wq.h): the default scheduler orders the unfenced reverse tile better
                "xeq_message_wq_bwd.hip": ["-ffp-contract=off"],
                # md: the integrator's double expressions are the ones written, operation by operation (tests/md_oracle.py restates them);
                # an explicit -ffp-contract=fast on the command line overrides a pragma in the source, so the switch is here
@@ -99,8 +99,7 @@ def build(force=False, verbose=True):
         s = os.path.join(HERE, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
-        extra_deps = [os.path.join(HERE, "xeq_message_wq.hip")] if src == "xeq_message_wq_bwd.hip" else []
-        if force or _stale(o, [s] + hdrs + extra_deps):
+        if force or _stale(o, [s] + hdrs):
             jobs.append([hipcc, *FLAGS, *EXTRA_FLAGS.get(src, []), "-c", s, "-o", o])
 
     def run(cmd):

@@ -20,13 +20,8 @@
 namespace xeq {
 
 #define MLP_SB() __builtin_amdgcn_sched_barrier(0)
-#ifdef XEQ_SILU_FAST   // development switch (xeq_packed_w.h: silu_exp), this file's kernels only
-constexpr bool MLP_FAST = true;
-#else
-constexpr bool MLP_FAST = false;
-#endif
-__device__ __forceinline__ float mlp_silu(float x) { return silu_f<MLP_FAST>(x); }
-__device__ __forceinline__ float mlp_silu_grad(float x) { return silu_grad_f<MLP_FAST>(x); }
+__device__ __forceinline__ float mlp_silu(float x) { return silu_f(x); }
+__device__ __forceinline__ float mlp_silu_grad(float x) { return silu_grad_f(x); }
 
 constexpr int MLP_ROWS = 32;
 constexpr int MLP_H = 128;        // hidden width (node_dim of the default and of every shipped configuration)

@@ -9,8 +9,6 @@
 // three ordinary GEMMs without transposes, and channel-on-lane accesses are coalesced.
 // Tensors that cross the module boundary (s, x and their gradients) keep the
 // reference's e3nn mul_ir layout.
-#include <stdlib.h>
-
 #include "xeq_common.h"
 
 namespace xeq {
@@ -787,8 +785,7 @@ int xeq_norm_bwd(int dtype, const void* s, const void* x, const void* ln_w, cons
 #ifndef XEQ_NORM_BWD_NPW
 #define XEQ_NORM_BWD_NPW 4
 #endif
-  const bool fast = do_norm && node_dim <= 128 && ir.D() <= 512 && n * (int64_t)ir.D() < (1ll << 31) &&
-                    getenv("XEQ_NORM_BWD_OLD") == nullptr;
+  const bool fast = do_norm && node_dim <= 128 && ir.D() <= 512 && n * (int64_t)ir.D() < (1ll << 31);
   const int64_t per_wg = n >= 8 * 1024 ? 4 * XEQ_NORM_BWD_NPW : 4;
   const unsigned wgrid = (unsigned)((n + per_wg - 1) / per_wg);
   XEQ_DISPATCH_FLOAT(dtype, {

@@ -57,24 +57,14 @@ constexpr int TILE_U4 = 192;     // one packed weight tile (16 output rows x 32 
 #ifndef XEQ_NB_STAGE
 #define XEQ_NB_STAGE 4
 #endif
-#ifndef XEQ_NB_RING
-#define XEQ_NB_RING 2
-#endif
-constexpr int RING_STAGES = XEQ_NB_RING, STAGE_TILES = XEQ_NB_STAGE;   // tiles per stage: a multiple of 4 (each wave fetches STAGE_TILES / 4 tiles of a stage)
+constexpr int RING_STAGES = 2, STAGE_TILES = XEQ_NB_STAGE;   // tiles per stage: a multiple of 4 (each wave fetches STAGE_TILES / 4 tiles of a stage)
 constexpr int PF = STAGE_TILES / 4;
 constexpr int RING_BYTES = RING_STAGES * STAGE_TILES * TILE_U4 * 16;
 
 #define NB_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-// The stage barrier of the weight stream.  Two ring stages: the slot written behind the barrier is the one whose last tiles this wave
-// has just requested, so its LDS reads are drained first.  Three stages (-DXEQ_NB_RING=3): the slot written behind the barrier held
-// the stage BEFORE the one in flight -- every wave that reaches the barrier has multiplied all of that stage's tiles (their reads were
-// waited for by the products), and the stage published by the barrier was written a whole stage ago by LDS operations older than reads
-// this wave has since consumed (a wave's LDS operations complete in order): no drain.
-#if XEQ_NB_RING >= 3
-#define NB_STAGE_BARRIER() asm volatile("s_barrier" ::: "memory")
-#else
-#define NB_STAGE_BARRIER() NB_LDS_BARRIER()
-#endif
+// It is also the stage barrier of the weight stream.  With the two ring stages the slot written behind the barrier is the one whose last
+// tiles this wave has just requested, so its LDS reads are drained first.  (Three stages and a barrier without the drain, and the stage
+// boundary one tile later, measured inside the noise: profiles/r06_small_experiments.txt lines 27-28.)
 
 // Development aid (-DXEQ_NB_STAMPS): core-clock stamps at the phase boundaries of the forward / reverse kernels, per (workgroup, wave)
 // (cdna_hip_programming.md section 7, in-kernel stamps).  Read back through xeq_node_block_debug_stamps.
@@ -211,19 +201,6 @@ struct WStream {
     const Frag r = cur;
     cur = nxt;
     ++t;
-#ifdef XEQ_NB_SYNC_LATE
-    // development: the stage boundary ONE tile later and IN FRONT of the tile's read -- the youngest LDS read in flight is then a
-    // whole tile old when the drain waits for it (two ring stages)
-    if ((t & (STAGE_TILES - 1)) == STAGE_TILES - 1) {
-      const int j = t / STAGE_TILES + 1;
-      NB_LDS_BARRIER();
-      commit(j + 1);
-      issue(j + 2);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    read(t + 1);
-    return r;
-#endif
     read(t + 1);
     if ((t & (STAGE_TILES - 1)) == STAGE_TILES - 2) {   // tiles t, t + 1 (the last two of their stage) are in registers or on their way
       const int j = t / STAGE_TILES + 1;
@@ -237,7 +214,7 @@ struct WStream {
       t_barrier += b1_ - b0_;
       t_commit += b2_ - b1_;
 #else
-      NB_STAGE_BARRIER();
+      NB_LDS_BARRIER();
       commit(j + 1);
 #endif
       issue(j + 2);
@@ -344,53 +321,21 @@ __device__ __forceinline__ tile_t ld_tile(const float* __restrict__ row, int c0,
   return t;
 }
 // `ok`: the lane's node exists.  Lanes beyond the last node work on the LAST node's row (row = n - 1), so their results are that row's,
-// bit for bit, and -DXEQ_NB_UNCOND_STORES lets them store too (equal values to equal addresses): a store that is not behind a branch is
-// a memory operation the compiler can COUNT, so the waits behind it name the loads they wait for instead of draining everything.
-#ifdef XEQ_NB_UNCOND_STORES
-#define NB_STORE_OK(ok) true
-#else
-#define NB_STORE_OK(ok) (ok)
-#endif
-#ifdef XEQ_NB_UNCOND_PINNED   // development: unconditional stores that the scheduler may not move anything across
-#define NB_PIN() __builtin_amdgcn_sched_barrier(0)
-#else
-#define NB_PIN() do { } while (0)
-#endif
+// bit for bit, but they do not store.  (Letting them store too, so that no store sits behind a branch, with and without scheduling fences
+// around the stores: slower, profiles/r06_small_experiments.txt item 12 d, e.)
 __device__ __forceinline__ void st_tile(float* __restrict__ row, int c0, int h, const tile_t& t, bool ok) {
-  if (!NB_STORE_OK(ok)) return;
-  NB_PIN();
+  if (!ok) return;
 #pragma unroll
   for (int g = 0; g < 2; ++g)
     *reinterpret_cast<float4*>(row + c0 + 16 * g + 4 * h) = make_float4(t[4 * g], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3]);
-  NB_PIN();
 }
-// a 32-channel tile of a PARAMETER vector (norm weights, biases).  -DXEQ_NB_EXP_NOPARAM (development, timing only, wrong results): no
-// memory access -- what the ~80 small parameter loads of a launch, each requested right in front of its use, cost
-__device__ __forceinline__ tile_t ld_par(const float* __restrict__ vec, int c0, int h) {
-#ifdef XEQ_NB_EXP_NOPARAM
-  extern __shared__ uint4 lds_any_[];   // (two 16-byte LDS reads of whatever the ring holds: the cost the values would have from LDS)
-  const float4 u = *reinterpret_cast<const float4*>(lds_any_ + ((c0 >> 5) & 7) * 64 + (threadIdx.x & 63));
-  const float4 v = *reinterpret_cast<const float4*>(lds_any_ + (((c0 >> 5) & 7) + 8) * 64 + (threadIdx.x & 63));
-  tile_t t;
-  t[0] = u.x; t[1] = u.y; t[2] = u.z; t[3] = u.w; t[4] = v.x; t[5] = v.y; t[6] = v.z; t[7] = v.w;
-  (void)vec; (void)h;
-  return t;
-#else
-  return ld_tile(vec, c0, h);
-#endif
-}
+// a 32-channel tile of a PARAMETER vector (norm weights, biases).  (What the ~80 small parameter loads of a launch cost, and the
+// launches without the saved activations or with cache-resident ones: timing-only builds, profiles/r04_nodeblock.txt.)
+__device__ __forceinline__ tile_t ld_par(const float* __restrict__ vec, int c0, int h) { return ld_tile(vec, c0, h); }
 // Tensors that only these kernels read and write (the forward launch's hand-over to the reverse launch, scratch) use a layout in which
 // every wave access is 1 KB of consecutive bytes: [wave block of 16 nodes][tile][register quad][lane][4 floats] (NAT_TILE floats per
 // tile and block).
 constexpr int NAT_TILE = 512;
-// development (timing only, wrong results): -DXEQ_NB_EXP_NOSAVE drops the forward launch's stores that only the reverse launch reads;
-// -DXEQ_NB_EXP_SAVED0 lets every wave of the reverse launch read wave block 0's saved activations (cache-resident: what the
-// launch would cost if recomputing them were free); -DXEQ_NB_EXP_SCRATCH0 folds the reverse launch's scratch onto 256 wave blocks
-#ifdef XEQ_NB_EXP_NOSAVE
-#define NB_SAVE(stmt) do { } while (0)
-#else
-#define NB_SAVE(stmt) do { stmt; } while (0)
-#endif
 __device__ __forceinline__ tile_t ld_nat(const float* __restrict__ wb, int t, int lane) {
   const float4* p = reinterpret_cast<const float4*>(wb + t * NAT_TILE) + lane;
   tile_t r;
@@ -438,8 +383,7 @@ __device__ __forceinline__ void ld_xm(const float* __restrict__ blk, int h, tile
 }
 template <int DL>
 __device__ __forceinline__ void st_xm(float* __restrict__ blk, int h, const tile_t (&X)[DL], bool ok) {
-  if (!NB_STORE_OK(ok)) return;
-  NB_PIN();
+  if (!ok) return;
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
     float* p = blk + DL * (16 * g + 4 * h);
@@ -451,7 +395,6 @@ __device__ __forceinline__ void st_xm(float* __restrict__ blk, int h, const tile
 #pragma unroll
     for (int q = 0; q < DL; ++q) *reinterpret_cast<float4*>(p + 4 * q) = make_float4(flat[4 * q], flat[4 * q + 1], flat[4 * q + 2], flat[4 * q + 3]);
   }
-  NB_PIN();
 }
 
 __device__ __forceinline__ float sum16(const tile_t& t) { return ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7])); }
@@ -636,22 +579,14 @@ __global__ void __launch_bounds__(256, 2) k_nb_linear_test(LinTestArgs a) {
       for (int ot = 0; ot < a.n_ot; ot += 2) {
         tile_t a0 = zero16(), a1 = zero16();
         out_pair<4>(w, a0, a1, fx);
-#ifdef XEQ_NB_TEST_NOSTORE
-        if (a0[0] == 12345.678f) { st_tile(yr, 32 * ot, h, a0, ok); st_tile(yr, 32 * ot + 32, h, a1, ok); }
-#else
         st_tile(yr, 32 * ot, h, a0, ok);
         st_tile(yr, 32 * ot + 32, h, a1, ok);
-#endif
       }
     } else
     for (int ot = 0; ot < a.n_ot; ++ot) {
       tile_t acc = zero16();
       out_tile<4>(w, acc, fx);
-#ifdef XEQ_NB_TEST_NOSTORE
-      if (acc[0] == 12345.678f) st_tile(yr, 32 * ot, h, acc, ok);
-#else
       st_tile(yr, 32 * ot, h, acc, ok);
-#endif
     }
     NB_STAMP(2);
     NB_RSTAMP(5);
@@ -731,7 +666,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
     float q = (sumsq16(X0[0], mean0) + sumsq16(X0[1], mean0)) + (sumsq16(X0[2], mean0) + sumsq16(X0[3], mean0));
     q += sumsq_span<(D - M0) / 16>(xrow + M0, h);   // the l > 0 features: plain squares, no layout needed
     rr = 1.f / sqrtf(row_sum(q) * (1.f / C) + 1e-5f);
-    if (NB_STORE_OK(ok && h == 0)) *reinterpret_cast<float4*>(a.stats + 4 * row) = make_float4(mean, rstd, mean0, rr);
+    if ((ok && h == 0)) *reinterpret_cast<float4*>(a.stats + 4 * row) = make_float4(mean, rstd, mean0, rr);
     NB_STAMP(3);
     // ---- l = 0: normalised features -> parked fragments
 #pragma unroll
@@ -755,7 +690,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
     U += bu;
     V += bv;
     st_nat(uvw, uv_tile(0, 0, 0, c), lane, U);
-    NB_SAVE(st_nat(uvw, uv_tile(0, 0, 1, c), lane, V));
+    st_nat(uvw, uv_tile(0, 0, 1, c), lane, V);
     tile_t v, p;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -787,7 +722,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
         tile_t U = zero16(), V = zero16();
         out_pair_p<2>(w, U, V, pk);
         st_nat(uvw, uv_tile(1, m, 0, c), lane, U);
-        NB_SAVE(st_nat(uvw, uv_tile(1, m, 1, c), lane, V));
+        st_nat(uvw, uv_tile(1, m, 1, c), lane, V);
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
           VSQ[c][r] = __builtin_fmaf(V[r], V[r], VSQ[c][r]);
@@ -820,7 +755,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
       tile_t U = zero16(), V = zero16();
       out_pair_p<1>(w, U, V, pk);
       st_nat(uvw, uv_tile(2, m, 0, 0), lane, U);
-      NB_SAVE(st_nat(uvw, uv_tile(2, m, 1, 0), lane, V));
+      st_nat(uvw, uv_tile(2, m, 1, 0), lane, V);
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         VSQ[r] = __builtin_fmaf(V[r], V[r], VSQ[r]);
@@ -838,7 +773,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     HID[t] += ld_par(a.b3, 32 * t, h);
-    NB_SAVE(st_nat(prew, t, lane, HID[t]));
+    st_nat(prew, t, lane, HID[t]);
     tile_t hv;
 #pragma unroll
     for (int r = 0; r < 8; ++r) hv[r] = silu_f(HID[t][r]);
@@ -859,7 +794,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
     tile_t av = zero16();
     out_tile_p<4>(w, av, pk);
     av += b4v;
-    NB_SAVE(st_nat(aw, c, lane, av));
+    st_nat(aw, c, lane, av);
     if (wx) {
       tile_t xn;
 #pragma unroll
@@ -875,7 +810,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
     tile_t av = zero16();
     out_tile_p<4>(w, av, pk);
     av += b4v;
-    NB_SAVE(st_nat(aw, 4 + c, lane, av));
+    st_nat(aw, 4 + c, lane, av);
     if (wx) {
       tile_t U[3];   // (this lane's own stores; fetched behind the products: two waves share the SIMD, the registers are worth more than the latency)
 #pragma unroll
@@ -896,7 +831,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
     tile_t av = zero16();
     out_tile_p<4>(w, av, pk);
     av += b4v;
-    NB_SAVE(st_nat(aw, 6, lane, av));
+    st_nat(aw, 6, lane, av);
     if (wx) {
       tile_t U[5];
 #pragma unroll
@@ -927,13 +862,13 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const tile_t bsv = ld_par(a.b4, C + 32 * c, h), bss = ld_par(a.b4, C + F + 32 * c, h), S = ld_tile(srow, 32 * c, h);
-    NB_SAVE(st_nat(ipw, c, lane, IP[c]));
+    st_nat(ipw, c, lane, IP[c]);
     tile_t asv = zero16(), ass = zero16();
     out_pair_p<4>(w, asv, ass, pk);
     asv += bsv;
     ass += bss;
-    NB_SAVE(st_nat(aw, 7 + c, lane, asv));
-    NB_SAVE(st_nat(aw, 11 + c, lane, ass));
+    st_nat(aw, 7 + c, lane, asv);
+    st_nat(aw, 11 + c, lane, ass);
 #pragma unroll
     for (int r = 0; r < 8; ++r) SN[c][r] = (S[r] + asv[r] * IP[c][r]) + ass[r];
     st_tile(sor, 32 * c, h, SN[c], ok);
@@ -962,7 +897,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
   NB_STAMP(10);
   const float qn = q2 + ((sumsq16(XN0[0], mean0_n) + sumsq16(XN0[1], mean0_n)) + (sumsq16(XN0[2], mean0_n) + sumsq16(XN0[3], mean0_n)));
   const float rr_n = 1.f / sqrtf(row_sum(qn) * (1.f / C) + 1e-5f);
-  if (NB_STORE_OK(ok && h == 0)) *reinterpret_cast<float4*>(a.stats2 + 4 * row) = make_float4(mean_n, rstd_n, mean0_n, rr_n);
+  if ((ok && h == 0)) *reinterpret_cast<float4*>(a.stats2 + 4 * row) = make_float4(mean_n, rstd_n, mean0_n, rr_n);
   // xhat of the next block, BT layout (block l at N base_l, row (node, m), channels contiguous)
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -977,7 +912,7 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_fwd(FwdArgs a)
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     HN[t] += ld_par(a.b1n, 32 * t, h);
-    NB_SAVE(st_nat(a.pre2 + wblk * (S_TILES * NAT_TILE), t, lane, HN[t]));
+    st_nat(a.pre2 + wblk * (S_TILES * NAT_TILE), t, lane, HN[t]);
     tile_t hv;
 #pragma unroll
     for (int r = 0; r < 8; ++r) hv[r] = silu_f(HN[t][r]);
@@ -1111,20 +1046,12 @@ __global__ void __launch_bounds__(64 * MAX_WAVES, 1) k_node_block_bwd(BwdArgs a)
   const Park pk{ring + RING_BYTES / 16 + wave * PARK_U4 + lane};
   const float e2 = a.eps * a.eps;
   const int64_t wblk = (int64_t)blockIdx.x * n_waves + wave;   // this wave's block of 16 nodes in the internal layout (= node / 16)
-#ifdef XEQ_NB_EXP_SCRATCH0
-  const int64_t cblk = wblk & 255;
-#else
   const int64_t cblk = wblk;
-#endif
   float* __restrict__ gxow = a.gxo + cblk * (X_TILES * NAT_TILE);   // total dL/dx_out (GX)
   float* __restrict__ gww = a.gw + cblk * (X_TILES * NAT_TILE);
   float* __restrict__ gpw = a.gp + cblk * (P_TILES * NAT_TILE);
   float* __restrict__ gvw = a.gv + cblk * (P_TILES * NAT_TILE);
-#ifdef XEQ_NB_EXP_SAVED0
-  const int64_t sblk = 0;
-#else
   const int64_t sblk = wblk;
-#endif
   const float* __restrict__ uvw = a.uv + sblk * (UV_TILES * NAT_TILE);
   const float* __restrict__ aw = a.a + sblk * (A_TILES * NAT_TILE);
   const float* __restrict__ prew = a.pre + sblk * (S_TILES * NAT_TILE);

@@ -19,20 +19,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // workgroup barrier that orders LDS traffic only: __syncthreads() also drains this wave's global stores and prefetches (vmcnt(0))
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// exp: the library's expf (<= 1 ulp, what the reference's SiLU evaluates); FAST: the hardware exp2 path (~2 ulp + the rounding of
-// x log2 e), kept as a development switch for the accuracy / time comparison of DESIGN section 2 (xeq_mlp.hip under -DXEQ_SILU_FAST,
-// nowhere else)
-template <bool FAST = false>
-__device__ __forceinline__ float silu_exp(float x) {
-  return FAST ? __expf(x) : expf(x);
-}
-template <bool FAST = false>
+// exp: the library's expf (<= 1 ulp, what the reference's SiLU evaluates).  (The hardware exp2 path, ~2 ulp + the rounding of x log2 e:
+// the accuracy / time comparison of DESIGN section 2.)
 __device__ __forceinline__ float silu_f(float x) {
-  return x / (1.f + silu_exp<FAST>(-x));
+  return x / (1.f + expf(-x));
 }
-template <bool FAST = false>
 __device__ __forceinline__ float silu_grad_f(float x) {  // aten silu_backward: sig (1 + x (1 - sig))
-  const float sig = 1.f / (1.f + silu_exp<FAST>(-x));
+  const float sig = 1.f / (1.f + expf(-x));
   return sig * (1.f + x * (1.f - sig));
 }
 __device__ __forceinline__ float4 silu4(const float4& v) { return make_float4(silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w)); }

@@ -8,8 +8,6 @@
 // of (l1, l2, l3) (xequinet_amd/data/wigner3j_lmax4.npz).  A thread owns one output element (n, w, k); launches of the
 // paths of one product run in stream order and accumulate into `out`, so the sum over paths has a fixed order
 // (deterministic, no atomics).  The contraction is small and ragged (2l+1 <= 9): this op is HBM / latency bound, not a GEMM.
-#include <stdlib.h>
-
 #include "xeq_common.h"
 
 namespace xeq {
@@ -442,7 +440,7 @@ int xeq_tensor_product(int dtype, const void* x1, const void* x2, int64_t n, int
     for (int p = a.slot[s].p0; p < a.slot[s].p1; ++p)
       XEQ_CHECK_ARG(!a.slot[s].blocked || a.path[p].mode == TP_UVW || a.path[p].mode == TP_UUW, "xeq_tensor_product: an output block mixes 'uvw' / 'uuw' with other modes");
   XEQ_CHECK_ARG(!any_w || weight, "xeq_tensor_product: weighted paths need the weight buffer");
-  bool tied = getenv("XEQ_TP_GENERIC") == nullptr;   // (development: XEQ_TP_GENERIC forces the element-per-thread form)
+  bool tied = true;
   for (int s = 0; s < a.n_slots && tied; ++s)
     for (int p = a.slot[s].p0; p < a.slot[s].p1; ++p) {
       const int m = a.path[p].mode;

@@ -159,23 +159,15 @@ constexpr int PG_CH = 16;        // edges a wave stages at a time
 #define XEQ_PG_STEPS 2
 #endif
 constexpr int PG_STEPS = XEQ_PG_STEPS;   // edge pairs whose gathers are in flight together (measured 1 / 2 / 4 / 8: 859 / 719 / 871 / 901 us; 148 VGPRs at 2)
-#ifdef XEQ_PG_WPE
-#define XEQ_PG_OCC __attribute__((amdgpu_waves_per_eu(XEQ_PG_WPE, XEQ_PG_WPE)))
-#else
-#define XEQ_PG_OCC
-#endif
 constexpr int PG_LD = 96;        // floats per staged row: 64 used; odd and even edges land in different bank halves
-#ifndef XEQ_PG_ABLATE            // development switch (scratch/bench_param_grad.py): bit 0 no center rows, 1 no xhat rows, 3 no h, 4 no MFMA
-#define XEQ_PG_ABLATE 0
-#endif
 
 // What bounds this kernel is the NUMBER of vector-memory instructions, not their bytes: a dword-per-lane load costs the CU ~20-25
-// cycles whatever its alignment (ablation, scratch/bench_param_grad.py: 8.3 loads per edge pair -> 0.97 ms without a single MFMA,
+// cycles whatever its alignment (ablation builds, profiles/r03_train_findings.txt: 8.3 loads per edge pair -> 0.97 ms without a single MFMA,
 // 0.21 ms with the MFMAs and the index loads only).  So: the table rows and the edge indices of 16 edges come in with FOUR 16-byte
 // loads per lane and go through (wave-private) LDS; per edge pair that leaves the row gathers -- h (1), the center's dL/ds_out or
 // dL/dx_out (1-5: L1 hits, ~17 consecutive edges share a center) and, for gate_state tiles, xhat (1-5) -- all of a round requested
 // together.
-__global__ void __launch_bounds__(256) XEQ_PG_OCC k_message_param_grad_mc(PgArgs a, const float* __restrict__ tab, const float* __restrict__ h,
+__global__ void __launch_bounds__(256) k_message_param_grad_mc(PgArgs a, const float* __restrict__ tab, const float* __restrict__ h,
                                                                const float* __restrict__ xhat, const float* __restrict__ grad_s,
                                                                const float* __restrict__ grad_x, float* __restrict__ parts) {
   // staging rows of the four waves; reused for the cross-wave sum at the end (3 x 64 x 33 floats fit)
@@ -257,17 +249,17 @@ __global__ void __launch_bounds__(256) XEQ_PG_OCC k_message_param_grad_mc(PgArgs
       for (int u = 0; u < PG_STEPS; ++u) {
         const int j = 2 * PG_STEPS * half + 2 * u + kh;
         const int64_t c = sC[wave][j], n = sN[wave][j];
-        hv[u] = (XEQ_PG_ABLATE & 8) ? 1.f : h[n * a.H + row];
+        hv[u] = h[n * a.H + row];
         if (role == 2) {
-          gc[u][0] = (XEQ_PG_ABLATE & 1) ? 1.f : grad_s[c * a.F + ch];
+          gc[u][0] = grad_s[c * a.F + ch];
         } else {
           const float* gx = grad_x + ga.off + c * ga.node;
           const float* xn = xhat + xa.off + n * xa.node;
 #pragma unroll
           for (int m = 0; m < 5; ++m) {
             if (m < nm) {
-              gc[u][m] = (XEQ_PG_ABLATE & 1) ? 1.f : gx[(int64_t)m * ga.comp];
-              if (role == 0) xo[u][m] = (XEQ_PG_ABLATE & 2) ? 1.f : xn[(int64_t)m * xa.comp];
+              gc[u][m] = gx[(int64_t)m * ga.comp];
+              if (role == 0) xo[u][m] = xn[(int64_t)m * xa.comp];
             }
           }
         }
@@ -292,11 +284,6 @@ __global__ void __launch_bounds__(256) XEQ_PG_OCC k_message_param_grad_mc(PgArgs
       }
 #pragma unroll
       for (int u = 0; u < PG_STEPS; ++u) {
-        if (XEQ_PG_ABLATE & 16) {
-          acc0[0] += G[u] * b0[u];
-          acc1[0] += G[u] * b1[u];
-          continue;
-        }
         acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(G[u], b0[u], acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(G[u], b1[u], acc1, 0, 0, 0);
       }
