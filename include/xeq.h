@@ -125,6 +125,14 @@ int xeq_radius_graph_fill_cl(int dtype, const void* pos, const int64_t* ptr, int
 int xeq_pbc_image_counts(int dtype, const void* cell_host, int64_t n_graphs, const int32_t pbc[3], double cutoff, int32_t reps[3]);
 int xeq_pbc_tables_host(int dtype, const void* cell_host, int64_t n_graphs, const int32_t reps[3], double cutoff, void* out_host,
                         int64_t out_count);
+/* The same table for ONE cell that lives on the device (a box that a barostat moves: runtime.GraphedStepPBC(device_cell=True)), one
+ * launch on `stream`: cell [1, 3, 3] of `dtype` in device memory, reps / pbc on the host (read at the call), out[] = grid | offs |
+ * recip | thr in device memory, 6 n_cells + 12 values.  The arithmetic is the host function's own statement (csrc/xeq_pbc_tables.h)
+ * in an object built without contraction: the values are the host function's bit for bit, f32 and f64.  reps_needed [3] (int32, device,
+ * optional): what xeq_pbc_image_counts gives for this cell and periodicity -- a caller whose image counts are fixed (a captured graph)
+ * compares. */
+int xeq_pbc_tables_device(int dtype, const void* cell, const int32_t reps[3], const int32_t pbc[3], double cutoff, void* out, int64_t out_count,
+                          int32_t* reps_needed, void* stream);
 
 /* wrap_positions (data/radius_graph.py:6-32) for every atom: fractional = pos cell_inv[g], shift = floor(fractional) on the periodic
  * axes (pbc[a] != 0), pos_wrap = (fractional - shift) cell[g].  cell / cell_inv [G, 3, 3] row-major (rows = lattice vectors). */
@@ -980,7 +988,7 @@ int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const 
  *
  * Per-atom inputs, all of `dtype`: inv_mass [n] = A / m_i (A: the factor from force / mass to length / fs^2; 0: a FIXED atom, which
  * neither moves nor keeps a velocity), half_mass [n] = m_i / (2 A) (kinetic energy per squared velocity; 0 for a fixed atom).  batch [n]:
- * the atom's graph.  book: int64 [4] on the device = {steps done, largest n_edges seen, non-finite flag, unused}, maintained by
+ * the atom's graph.  book: int64 [4] on the device = {steps done, largest n_edges seen, non-finite flag, xeq_npt_back's image flag}, maintained by
  * xeq_md_back with plain stores of one lane; the host resets entries 1 and 2 when it has read them.
  *
  * Generator: Philox4x32-10 with key = (seed low word, seed high word) and counter
@@ -1026,6 +1034,43 @@ int xeq_md_back(int dtype, int advance, int64_t n, int64_t n_graphs, int64_t n_c
                 const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* ke, void* epot, int64_t* book,
                 double half_dt, const double* cell, const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start,
                 int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* stream);
+
+/* Constant pressure: the Berendsen barostat next to the Berendsen thermostat (ASE's NPTBerendsen.step in the front / back split above)
+ * for ONE periodic box, all three axes periodic, whose cell lives on the device.  One step is xeq_npt_front, the step's graph (whose first
+ * node forms the cell tables from the step's static cell: xeq_pbc_tables_device), xeq_npt_back.  Per-atom and per-box arithmetic runs in
+ * double and is rounded once where it is stored.
+ *
+ * box: the record, XEQ_NPT_BOX doubles on the device: the current cell [9] (rows = lattice vectors; holds `dtype` values) and its
+ * inverse [9] (frac_k = sum_j x_j inv[3 j + k]), the PENDING cell and its inverse, mu, P, V.  The host fills current = pending = the
+ * start cell, the inverse by xeq_md_inverse_cell, mu = 1.
+ *
+ * xeq_npt_back: everything xeq_md_back does for one graph; then the lane that keeps the books copies virial_step [9] (the step's
+ * virial W = -dE/dstrain, `dtype`) to virial and forms, from the CURRENT cell c,
+ *   V = |det c| (operation order of xeq_md_inverse_cell), P = (2 ke[0] + (W00 + W11) + W22) / (3 V) from the STORED ke[0],
+ *   mu = 1 - kappa (p0 - P), kappa = (dt / taup) (beta / 3)   (ASE's linear form: no cube root, no clamp),
+ *   pending cell = (dtype)(mu c) and its inverse.
+ * A mu that is not finite or not positive, or a pending cell without an inverse, sets book[2] and leaves mu = 1, pending = current.
+ * reps_needed [3] (device, the step graph's output; NULL: no check): book[3] = 1 when an entry exceeds reps [3] (host: the captured
+ * counts); reps_seen [3] (device) keeps the largest seen.  Energies per volume are in the caller's energy / length^3; p_unit converts P
+ * for the recorder alone.  Recorder: as xeq_md_back, the positions unwrapped by the current cell, and traj_cell [rows, 3, 3] (`dtype`),
+ * traj_pressure [rows] (double, P p_unit).
+ *
+ * xeq_npt_front, dt > 0: the Berendsen lambda of xeq_md_front; x <- mu x for EVERY atom, fixed ones included (ASE's
+ * set_cell(scale_atoms=True)); the half kick with the forces of the unscaled geometry and the drift for the free atoms; the wrap against
+ * the PENDING cell.  Thread 0 alone commits the pending cell to the record's current cell and to step_cell [9] (`dtype`, the step's
+ * static cell); no other thread reads those two in this launch.  dt = 0: the wrap against the current cell, nothing is committed.
+ * So wherever the host can look, positions, images and step_cell belong together and mu is a function of the current state. */
+#define XEQ_NPT_BOX 40
+enum { XEQ_NPT_CELL = 0, XEQ_NPT_INV = 9, XEQ_NPT_CELL_NEXT = 18, XEQ_NPT_INV_NEXT = 27, XEQ_NPT_MU = 36, XEQ_NPT_P = 37, XEQ_NPT_V = 38 };
+int xeq_npt_front(int dtype, int64_t n, void* pos, void* vel, const void* frc, const void* inv_mass, const int64_t* batch, const void* ke,
+                  const void* tfac, double dt, double dt_over_tau, double t0, double* box, void* step_cell, int32_t* image, void* stream);
+int xeq_npt_back(int dtype, int advance, int64_t n, int64_t n_chunks, const void* pos, void* vel, void* frc, const void* frc_step,
+                 const void* energy_step, const int32_t* n_edges_step, const void* virial_step, const int32_t* reps_needed, const int32_t* reps,
+                 const void* inv_mass, const void* half_mass, const int32_t* chunk_atom0, const int32_t* chunk_n, const int32_t* graph_chunk_ptr,
+                 double* partial, int32_t* partial_bad, void* ke, void* epot, void* virial, int32_t* reps_seen, int64_t* book, double* box,
+                 double half_dt, double kappa, double p0, double p_unit, const int32_t* image, int64_t record_every, int64_t record_start,
+                 int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* traj_cell, double* traj_pressure,
+                 void* stream);
 
 /* Device-resident batched geometry optimisation (FIRE) around a whole-step graph (xequinet_amd/optimize.py, csrc/xeq_md.hip, DESIGN.md
  * section 13), f32 / f64.  One iteration is xeq_fire_front, the step's graph on the step object's static buffers, xeq_fire_back; nothing

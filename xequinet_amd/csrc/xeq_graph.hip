@@ -8,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "xeq_common.h"
+#include "xeq_pbc_tables.h"
 
 namespace xeq {
 
@@ -664,46 +665,9 @@ __global__ void k_rowptr_guard(const int32_t* __restrict__ raw, int64_t n, int32
 using namespace xeq;
 
 // ---- host-side cell tables of the periodic search (xeq_pbc_image_counts / xeq_pbc_tables_host, include/xeq.h) ----
-// Every operation is rounded once in T, in the order written (volatile temporaries keep the host compiler from contracting or
-// re-associating under -ffp-contract=fast): the Python front and the registered operator both call these, so the search
-// kernels see the same bits from either.
+// The arithmetic is stated once, in xeq_pbc_tables.h (every operation rounded once in T, in the order written): the Python front, the
+// registered operator and the device kernel xeq_pbc_tables_device all go through it, so the search kernels see the same bits from each.
 namespace xeq {
-template <typename T>
-struct CellGeom {
-  T cross[3][3];   // a_1 x a_2, a_2 x a_0, a_0 x a_1
-  T vol;
-  T recip[3][3];   // cross[ax] / vol
-  T inv_min[3];    // |recip[ax]|
-};
-template <typename T>
-static inline T rnd(T v) {
-  volatile T t = v;
-  return t;
-}
-template <typename T>
-static void cell_geom(const T* c, CellGeom<T>& g) {   // c: [3][3] row-major, rows = lattice vectors
-  const int jj[3] = {1, 2, 0}, kk[3] = {2, 0, 1};
-  for (int ax = 0; ax < 3; ++ax) {
-    const T* a = c + 3 * jj[ax];
-    const T* b = c + 3 * kk[ax];
-    g.cross[ax][0] = rnd<T>(rnd<T>(a[1] * b[2]) - rnd<T>(a[2] * b[1]));
-    g.cross[ax][1] = rnd<T>(rnd<T>(a[2] * b[0]) - rnd<T>(a[0] * b[2]));
-    g.cross[ax][2] = rnd<T>(rnd<T>(a[0] * b[1]) - rnd<T>(a[1] * b[0]));
-  }
-  T v = rnd<T>(c[0] * g.cross[0][0]);
-  v = rnd<T>(v + rnd<T>(c[1] * g.cross[0][1]));
-  v = rnd<T>(v + rnd<T>(c[2] * g.cross[0][2]));
-  g.vol = v;
-  for (int ax = 0; ax < 3; ++ax) {
-    T q = T(0);
-    for (int j = 0; j < 3; ++j) {
-      g.recip[ax][j] = rnd<T>(g.cross[ax][j] / g.vol);
-      const T sq = rnd<T>(g.recip[ax][j] * g.recip[ax][j]);
-      q = j == 0 ? sq : rnd<T>(q + sq);
-    }
-    g.inv_min[ax] = rnd<T>(std::sqrt(q));
-  }
-}
 template <typename T>
 static void image_counts(const T* cell, int64_t G, const int32_t pbc[3], double cutoff, int32_t reps[3]) {
   for (int ax = 0; ax < 3; ++ax) reps[ax] = 0;
@@ -712,42 +676,24 @@ static void image_counts(const T* cell, int64_t G, const int32_t pbc[3], double 
     cell_geom<T>(cell + 9 * g, cg);
     for (int ax = 0; ax < 3; ++ax) {
       if (!pbc[ax]) continue;
-      const T r = std::ceil(rnd<T>((T)cutoff * cg.inv_min[ax]));
-      const int32_t ri = (r > T(0) && r < T(1 << 20)) ? (int32_t)r : (r > T(0) ? (1 << 20) : 0);   // (a degenerate cell: caught by the caller's size check)
+      const int32_t ri = cell_image_count<T>(cg, ax, cutoff);
       if (ri > reps[ax]) reps[ax] = ri;
     }
   }
 }
 template <typename T>
 static void tables_host(const T* cell, int64_t G, const int32_t reps[3], double cutoff, T* out) {
-  const int64_t n0 = 2 * reps[0] + 1, n1 = 2 * reps[1] + 1, n2 = 2 * reps[2] + 1, nc = n0 * n1 * n2;
-  T* grid = out;
+  const int64_t nc = (int64_t)(2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1);
+  T* grid = out;   // (the same for every graph)
   T* offs = grid + 3 * nc;
   T* recip = offs + 3 * nc * G;
   T* thr = recip + 9 * G;
-  int64_t c = 0;
-  for (int64_t i0 = -reps[0]; i0 <= reps[0]; ++i0)
-    for (int64_t i1 = -reps[1]; i1 <= reps[1]; ++i1)
-      for (int64_t i2 = -reps[2]; i2 <= reps[2]; ++i2, ++c) {
-        grid[3 * c] = (T)i0;
-        grid[3 * c + 1] = (T)i1;
-        grid[3 * c + 2] = (T)i2;
-      }
   for (int64_t g = 0; g < G; ++g) {
     const T* a = cell + 9 * g;
-    for (int64_t k = 0; k < nc; ++k)
-      for (int j = 0; j < 3; ++j) {
-        T v = rnd<T>(grid[3 * k] * a[j]);
-        v = rnd<T>(v + rnd<T>(grid[3 * k + 1] * a[3 + j]));
-        v = rnd<T>(v + rnd<T>(grid[3 * k + 2] * a[6 + j]));
-        offs[(g * nc + k) * 3 + j] = v;
-      }
+    for (int64_t k = 0; k < nc; ++k) cell_table_image<T>(a, reps, k, grid + 3 * k, offs + (g * nc + k) * 3);
     CellGeom<T> cg;
     cell_geom<T>(a, cg);
-    for (int ax = 0; ax < 3; ++ax) {
-      for (int j = 0; j < 3; ++j) recip[9 * g + 3 * ax + j] = cg.recip[ax][j];
-      thr[3 * g + ax] = rnd<T>(rnd<T>((T)cutoff * cg.inv_min[ax]) + (T)1e-3);
-    }
+    cell_table_prune<T>(cg, cutoff, recip + 9 * g, thr + 3 * g);
   }
 }
 }  // namespace xeq

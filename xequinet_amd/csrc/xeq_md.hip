@@ -1,7 +1,9 @@
 // Device-resident molecular dynamics around the whole-step graphs (xequinet_amd/md.py): the integrator's two
 // halves -- xeq_md_front in front of the step's graph, xeq_md_back behind it -- and the counter-based generator they share with
 // xeq_md_normals; behind them the two halves of the batched FIRE minimiser (xequinet_amd/optimize.py), which share
-// the wrap, the chunk sums and the join.  Plain vector code, f32 and f64 state.
+// the wrap, the chunk sums and the join; the Berendsen barostat's two halves (xeq_npt_front / xeq_npt_back), which
+// are the MD halves with a box that lives on the device, and the kernel that forms the periodic search's cell tables from that box
+// (xeq_pbc_tables_device).  Plain vector code, f32 and f64 state.
 //
 // Arithmetic.  Every per-atom update is evaluated in double whatever the state's type and rounded ONCE when it is stored: the state of an
 // f32 run is within half an ulp of the f64 value of the same expression on the same stored inputs, and no result depends on how the compiler
@@ -13,6 +15,7 @@
 // workgroup per chunk: lanes, then a butterfly, then the four waves in order), joined in chunk order (k_md_join): no float atomic, and the
 // order depends on the graph's own atom count alone, so a graph has the same bits alone and anywhere in a batch.
 #include "xeq_common.h"
+#include "xeq_pbc_tables.h"
 
 namespace xeq {
 
@@ -123,10 +126,10 @@ __device__ __forceinline__ void md_wrap(const MdBox& b, double x[3], int32_t img
   }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) k_md_front(MdFrontArgs<T> a) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.n) return;
+// One atom's front half against `box`.  SCALE (the barostat, k_npt_front): x <- mu x for EVERY atom, fixed ones included, between the
+// thermostat's scaling and the half kick.
+template <typename T, bool SCALE>
+__device__ __forceinline__ void md_front_atom(const MdFrontArgs<T>& a, int64_t i, const MdBox& box, double mu) {
   const double im = (double)a.inv_mass[i];
   double v[3], x[3], f[3];
   for (int k = 0; k < 3; ++k) {
@@ -144,6 +147,9 @@ __global__ void __launch_bounds__(256) k_md_front(MdFrontArgs<T> a) {
       lam = fmin(fmax(lam, 0.9), 1.1);
     }
     for (int k = 0; k < 3; ++k) v[k] = lam * v[k];
+  }
+  if (SCALE) {
+    for (int k = 0; k < 3; ++k) x[k] = mu * x[k];
   }
   const double h = 0.5 * a.dt;
   if (im > 0.0) {   // (a fixed atom keeps its position and a zero velocity whatever its force holds)
@@ -167,14 +173,48 @@ __global__ void __launch_bounds__(256) k_md_front(MdFrontArgs<T> a) {
   } else {
     for (int k = 0; k < 3; ++k) v[k] = 0.0;
   }
-  if (a.box.any) {
+  if (box.any) {
     int32_t img[3] = {a.image[3 * i], a.image[3 * i + 1], a.image[3 * i + 2]};
-    md_wrap<T>(a.box, x, img);
+    md_wrap<T>(box, x, img);
     for (int k = 0; k < 3; ++k) a.image[3 * i + k] = img[k];
   }
   for (int k = 0; k < 3; ++k) {
     a.vel[3 * i + k] = (T)v[k];
     a.pos[3 * i + k] = (T)x[k];
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_md_front(MdFrontArgs<T> a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  md_front_atom<T, false>(a, i, a.box, 1.0);
+}
+
+// The barostat's front (xeq_npt_front): the box is the f64 record on the device (include/xeq.h: XEQ_NPT_*).  With dt > 0 every thread
+// reads the PENDING cell, its inverse and mu, which nobody writes here; thread 0 alone commits the pending cell to the record's current
+// cell and to the step's static cell, which nobody reads here.  dt = 0: the wrap against the current cell, nothing is committed.
+template <typename T>
+__global__ void __launch_bounds__(256) k_npt_front(MdFrontArgs<T> a, double* rec, T* step_cell) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const bool moves = a.dt > 0.0;
+  const double* c = rec + (moves ? XEQ_NPT_CELL_NEXT : XEQ_NPT_CELL);
+  const double* m = rec + (moves ? XEQ_NPT_INV_NEXT : XEQ_NPT_INV);
+  MdBox box;
+  for (int k = 0; k < 9; ++k) {
+    box.cell[k] = c[k];
+    box.inv[k] = m[k];
+  }
+  box.periodic[0] = box.periodic[1] = box.periodic[2] = box.any = 1;
+  const double mu = moves ? rec[XEQ_NPT_MU] : 1.0;
+  md_front_atom<T, true>(a, i, box, mu);
+  if (i == 0 && moves) {
+    for (int k = 0; k < 9; ++k) {
+      rec[XEQ_NPT_CELL + k] = box.cell[k];
+      rec[XEQ_NPT_INV + k] = box.inv[k];
+      step_cell[k] = (T)box.cell[k];
+    }
   }
 }
 
@@ -289,9 +329,102 @@ __device__ __forceinline__ void md_join_store(const MdBackArgs<T>& a, int64_t g,
   }
 }
 
-// The MD join; then ONE lane does the bookkeeping with plain stores.
+// What the NVT ensembles add to the back half: nothing; the recorder's cell is the launch's own.
+struct MdNoBox {
+  template <typename T>
+  __device__ __forceinline__ const double* cell(const MdBackArgs<T>& a) const {
+    return a.box.cell;
+  }
+  template <typename T>
+  __device__ __forceinline__ void finish(const MdBackArgs<T>&, int64_t) const {}
+};
+
+__host__ __device__ __forceinline__ double md_det(const double* c) {
+  return c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+}
+
+// inv [9] with frac_k = sum_j x_j inv[3 j + k] by the adjugate; -> the determinant (inv is not written unless it is finite and not zero).
+__host__ __device__ __forceinline__ double md_inverse(const double* c, double* m) {
+  const double det = md_det(c);
+  if (!(det != 0.0) || !(det - det == 0.0)) return det;
+  m[0] = (c[4] * c[8] - c[5] * c[7]) / det;
+  m[1] = (c[2] * c[7] - c[1] * c[8]) / det;
+  m[2] = (c[1] * c[5] - c[2] * c[4]) / det;
+  m[3] = (c[5] * c[6] - c[3] * c[8]) / det;
+  m[4] = (c[0] * c[8] - c[2] * c[6]) / det;
+  m[5] = (c[2] * c[3] - c[0] * c[5]) / det;
+  m[6] = (c[3] * c[7] - c[4] * c[6]) / det;
+  m[7] = (c[1] * c[6] - c[0] * c[7]) / det;
+  m[8] = (c[0] * c[4] - c[1] * c[3]) / det;
+  return det;
+}
+
+// The Berendsen barostat (xeq_npt_back), run by the ONE lane that keeps the books, behind them: the pressure of the state this launch
+// leaves, the scale factor of the NEXT step and the cell it will have, into the f64 record.  All in double, in the order written.
 template <typename T>
-__device__ __forceinline__ void md_join(const MdBackArgs<T>& a) {
+struct NptBox {
+  const T* virial_step;
+  T* virial;
+  double* rec;
+  const int32_t* reps_needed;
+  int32_t* reps_seen;
+  int32_t reps[3];
+  double kappa, p0, p_unit;
+  T* traj_cell;
+  double* traj_pressure;
+  __device__ __forceinline__ const double* cell(const MdBackArgs<T>&) const { return rec + XEQ_NPT_CELL; }
+  __device__ __forceinline__ void finish(const MdBackArgs<T>& a, int64_t row) const {
+    const double* c = rec + XEQ_NPT_CELL;
+    double w[9];
+    for (int k = 0; k < 9; ++k) {
+      const T wk = virial_step[k];
+      virial[k] = wk;
+      w[k] = (double)wk;
+    }
+    const double vol = fabs(md_det(c));
+    const double p = (2.0 * (double)a.ke[0] + ((w[0] + w[4]) + w[8])) / (3.0 * vol);
+    double mu = 1.0 - kappa * (p0 - p);
+    int bad = 0;
+    if (!(mu > 0.0) || !isfinite(mu)) {
+      bad = 1;
+      mu = 1.0;
+    }
+    double cn[9], in[9];
+    for (int k = 0; k < 9; ++k) cn[k] = (double)(T)(mu * c[k]);
+    const double dn = md_inverse(cn, in);
+    if (!(dn != 0.0) || !isfinite(dn)) {   // (a box the next step could not wrap against: it stays, the window is void)
+      bad = 1;
+      mu = 1.0;
+      for (int k = 0; k < 9; ++k) {
+        cn[k] = c[k];
+        in[k] = rec[XEQ_NPT_INV + k];
+      }
+    }
+    for (int k = 0; k < 9; ++k) {
+      rec[XEQ_NPT_CELL_NEXT + k] = cn[k];
+      rec[XEQ_NPT_INV_NEXT + k] = in[k];
+    }
+    rec[XEQ_NPT_MU] = mu;
+    rec[XEQ_NPT_P] = p;
+    rec[XEQ_NPT_V] = vol;
+    if (bad) a.book[2] = 1;
+    if (reps_needed) {
+      for (int k = 0; k < 3; ++k) {
+        const int32_t r = reps_needed[k];
+        if (r > reps[k]) a.book[3] = 1;
+        if (r > reps_seen[k]) reps_seen[k] = r;
+      }
+    }
+    if (row >= 0) {
+      for (int k = 0; k < 9; ++k) traj_cell[9 * row + k] = (T)c[k];
+      traj_pressure[row] = p * p_unit;
+    }
+  }
+};
+
+// The MD join; then ONE lane does the bookkeeping with plain stores.
+template <typename T, typename Box>
+__device__ __forceinline__ void md_join(const MdBackArgs<T>& a, const Box& bx) {
   const int64_t step_after = a.book[0] + (a.advance ? 1 : 0);
   const int64_t row = md_record_row(a, step_after);
   int bad = 0;
@@ -308,18 +441,24 @@ __device__ __forceinline__ void md_join(const MdBackArgs<T>& a) {
     if (ne > a.book[1]) a.book[1] = ne;
     if (any_bad) a.book[2] = 1;
     if (row >= 0) a.traj_step[row] = step_after;
+    bx.finish(a, row);
   }
 }
 
 template <typename T>
 __global__ void __launch_bounds__(MD_JOIN_THREADS) k_md_join(MdBackArgs<T> a) {
-  md_join(a);
+  md_join(a, MdNoBox{});
+}
+
+template <typename T>
+__global__ void __launch_bounds__(MD_JOIN_THREADS) k_npt_join(MdBackArgs<T> a, NptBox<T> bx) {
+  md_join(a, bx);
 }
 
 // One workgroup per chunk: second half kick, the step's forces into the driver's own copy, the chunk's kinetic energy and non-finite flag.
 // (Behind md_join in this file because a lone chunk's workgroup runs it itself.)
-template <typename T>
-__global__ void __launch_bounds__(MD_CHUNK) k_md_back(MdBackArgs<T> a) {
+template <typename T, typename Box>
+__device__ __forceinline__ void md_back_chunk(const MdBackArgs<T>& a, const Box& bx) {
   __shared__ double wsum[MD_CHUNK / 64];
   const int c = blockIdx.x;
   const int tid = threadIdx.x;
@@ -345,11 +484,11 @@ __global__ void __launch_bounds__(MD_CHUNK) k_md_back(MdBackArgs<T> a) {
     e = (double)a.half_mass[i] * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);   // of the STORED velocity: a function of the state alone
     const int64_t row = md_record_row(a, a.book[0] + 1);
     if (row >= 0) {
+      const double* cell = bx.cell(a);
       for (int j = 0; j < 3; ++j) {
         double x = (double)a.pos[3 * i + j];
         if (a.box.any)
-          x = x + (((double)a.image[3 * i] * a.box.cell[j] + (double)a.image[3 * i + 1] * a.box.cell[3 + j]) +
-                   (double)a.image[3 * i + 2] * a.box.cell[6 + j]);
+          x = x + (((double)a.image[3 * i] * cell[j] + (double)a.image[3 * i + 1] * cell[3 + j]) + (double)a.image[3 * i + 2] * cell[6 + j]);
         a.traj_pos[(row * a.n + i) * 3 + j] = (T)x;
       }
     }
@@ -367,7 +506,50 @@ __global__ void __launch_bounds__(MD_CHUNK) k_md_back(MdBackArgs<T> a) {
   if (a.n_chunks == 1) {   // the only chunk (a small molecule, a small box): its workgroup joins and keeps the books itself, one launch less
     __threadfence_block();
     __syncthreads();
-    md_join(a);
+    md_join(a, bx);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(MD_CHUNK) k_md_back(MdBackArgs<T> a) {
+  md_back_chunk(a, MdNoBox{});
+}
+
+template <typename T>
+__global__ void __launch_bounds__(MD_CHUNK) k_npt_back(MdBackArgs<T> a, NptBox<T> bx) {
+  md_back_chunk(a, bx);
+}
+
+// ------------------------------------------------------------------------------------------------------------- cell tables
+// xeq_pbc_tables_device: the flat table grid | offs | recip | thr of ONE cell that lives on the device, by the statement the host
+// function uses (xeq_pbc_tables.h); this file is built without contraction.  Thread k forms image k; thread 0 also the cell's geometry.
+struct Reps3 {
+  int32_t reps[3], pbc[3];
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_pbc_tables(const T* __restrict__ cell, Reps3 r, int64_t nc, double cutoff, T* __restrict__ out,
+                                                    int32_t* __restrict__ reps_needed) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= nc) return;
+  T a[9];
+  for (int j = 0; j < 9; ++j) a[j] = cell[j];
+  T grid[3], offs[3];
+  cell_table_image<T>(a, r.reps, k, grid, offs);
+  for (int j = 0; j < 3; ++j) {
+    out[3 * k + j] = grid[j];
+    out[3 * (nc + k) + j] = offs[j];
+  }
+  if (k == 0) {
+    CellGeom<T> cg;
+    cell_geom<T>(a, cg);
+    T recip[9], thr[3];
+    cell_table_prune<T>(cg, cutoff, recip, thr);
+    for (int j = 0; j < 9; ++j) out[6 * nc + j] = recip[j];
+    for (int j = 0; j < 3; ++j) out[6 * nc + 9 + j] = thr[j];
+    if (reps_needed) {
+      for (int ax = 0; ax < 3; ++ax) reps_needed[ax] = r.pbc[ax] ? cell_image_count<T>(cg, ax, cutoff) : 0;
+    }
   }
 }
 
@@ -634,20 +816,9 @@ static bool md_box(const double* cell, const int32_t* pbc, MdBox* b) {
   for (int k = 0; k < 9; ++k) b->cell[k] = b->inv[k] = 0.0;
   for (int k = 0; k < 3; ++k) b->periodic[k] = (cell && pbc && pbc[k]) ? 1 : 0;
   if (!cell || !(b->periodic[0] || b->periodic[1] || b->periodic[2])) return true;
-  const double* c = cell;
-  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+  const double det = md_inverse(cell, b->inv);
   if (!(det != 0.0) || !md_finite(det)) return false;
-  for (int k = 0; k < 9; ++k) b->cell[k] = c[k];
-  double* m = b->inv;
-  m[0] = (c[4] * c[8] - c[5] * c[7]) / det;
-  m[1] = (c[2] * c[7] - c[1] * c[8]) / det;
-  m[2] = (c[1] * c[5] - c[2] * c[4]) / det;
-  m[3] = (c[5] * c[6] - c[3] * c[8]) / det;
-  m[4] = (c[0] * c[8] - c[2] * c[6]) / det;
-  m[5] = (c[2] * c[3] - c[0] * c[5]) / det;
-  m[6] = (c[3] * c[7] - c[4] * c[6]) / det;
-  m[7] = (c[1] * c[6] - c[0] * c[7]) / det;
-  m[8] = (c[0] * c[4] - c[1] * c[3]) / det;
+  for (int k = 0; k < 9; ++k) b->cell[k] = cell[k];
   b->any = 1;
   return true;
 }
@@ -747,6 +918,88 @@ int xeq_md_back(int dtype, int advance, int64_t n, int64_t n_graphs, int64_t n_c
     if (n_chunks != 1) hipLaunchKernelGGL(k_md_join<T>, dim3(1), dim3(n_graphs > 64 ? MD_JOIN_THREADS : 256), 0, (hipStream_t)stream, a);
   });
   XEQ_CHECK_LAUNCH("xeq_md_back");
+  return XEQ_OK;
+}
+
+int xeq_pbc_tables_device(int dtype, const void* cell, const int32_t reps[3], const int32_t pbc[3], double cutoff, void* out, int64_t out_count,
+                          int32_t* reps_needed, void* stream) {
+  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_pbc_tables_device: dtype %d (0 f32, 1 f64)", dtype);
+  XEQ_CHECK_ARG(cell && out && reps && pbc, "xeq_pbc_tables_device: null pointer");
+  XEQ_CHECK_ARG(md_finite(cutoff) && cutoff > 0.0, "xeq_pbc_tables_device: cutoff %g", cutoff);
+  XEQ_CHECK_ARG(reps[0] >= 0 && reps[1] >= 0 && reps[2] >= 0 && reps[0] <= 64 && reps[1] <= 64 && reps[2] <= 64,
+                "xeq_pbc_tables_device: %d x %d x %d images per axis (0 .. 64 each)", reps[0], reps[1], reps[2]);
+  const int64_t nc = (int64_t)(2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1);
+  XEQ_CHECK_ARG(out_count == 6 * nc + 12, "xeq_pbc_tables_device: out[] holds %lld values, need %lld", (long long)out_count, (long long)(6 * nc + 12));
+  Reps3 r;
+  for (int k = 0; k < 3; ++k) {
+    r.reps[k] = reps[k];
+    r.pbc[k] = pbc[k] ? 1 : 0;
+  }
+  XEQ_DISPATCH_FLOAT(dtype, {
+    hipLaunchKernelGGL(k_pbc_tables<T>, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)cell, r, nc, cutoff, (T*)out,
+                       reps_needed);
+  });
+  XEQ_CHECK_LAUNCH("xeq_pbc_tables_device");
+  return XEQ_OK;
+}
+
+int xeq_npt_front(int dtype, int64_t n, void* pos, void* vel, const void* frc, const void* inv_mass, const int64_t* batch, const void* ke,
+                  const void* tfac, double dt, double dt_over_tau, double t0, double* box, void* step_cell, int32_t* image, void* stream) {
+  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_npt_front: dtype %d (0 f32, 1 f64)", dtype);
+  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3, "xeq_npt_front: %lld atoms", (long long)n);
+  XEQ_CHECK_ARG(md_finite(dt) && dt >= 0.0, "xeq_npt_front: time step %g", dt);
+  XEQ_CHECK_ARG(md_finite(dt_over_tau) && dt_over_tau >= 0.0 && md_finite(t0) && t0 >= 0.0,
+                "xeq_npt_front: berendsen needs dt / tau >= 0 and a target temperature >= 0 (got %g, %g)", dt_over_tau, t0);
+  XEQ_CHECK_ARG(box && step_cell, "xeq_npt_front: null box record or cell");
+  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && inv_mass && image), "xeq_npt_front: null state buffer");
+  XEQ_CHECK_ARG(n == 0 || (batch && ke && tfac), "xeq_npt_front: berendsen needs batch, ke and tfac");
+  if (n == 0) return XEQ_OK;
+  XEQ_DISPATCH_FLOAT(dtype, {
+    MdFrontArgs<T> a{n, 1, dt == 0.0 ? XEQ_MD_NVE : XEQ_MD_BERENDSEN, (T*)pos, (T*)vel, (const T*)frc, (const T*)inv_mass, batch, (const T*)ke,
+                     (const T*)tfac, nullptr, nullptr, 0, dt, 1.0, 0.0, dt_over_tau, t0, image, MdBox{}};
+    hipLaunchKernelGGL(k_npt_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, box, (T*)step_cell);
+  });
+  XEQ_CHECK_LAUNCH("xeq_npt_front");
+  return XEQ_OK;
+}
+
+int xeq_npt_back(int dtype, int advance, int64_t n, int64_t n_chunks, const void* pos, void* vel, void* frc, const void* frc_step,
+                 const void* energy_step, const int32_t* n_edges_step, const void* virial_step, const int32_t* reps_needed, const int32_t* reps,
+                 const void* inv_mass, const void* half_mass, const int32_t* chunk_atom0, const int32_t* chunk_n, const int32_t* graph_chunk_ptr,
+                 double* partial, int32_t* partial_bad, void* ke, void* epot, void* virial, int32_t* reps_seen, int64_t* book, double* box,
+                 double half_dt, double kappa, double p0, double p_unit, const int32_t* image, int64_t record_every, int64_t record_start,
+                 int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* traj_cell, double* traj_pressure,
+                 void* stream) {
+  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_npt_back: dtype %d (0 f32, 1 f64)", dtype);
+  XEQ_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 31) / 3 && n_chunks >= 1 && n_chunks < ((int64_t)1 << 31), "xeq_npt_back: %lld atoms, %lld chunks",
+                (long long)n, (long long)n_chunks);
+  XEQ_CHECK_ARG(n_chunks <= n && n_chunks * XEQ_MD_CHUNK >= n, "xeq_npt_back: %lld chunks of at most %d atoms cannot hold %lld atoms", (long long)n_chunks,
+                XEQ_MD_CHUNK, (long long)n);
+  XEQ_CHECK_ARG(md_finite(half_dt) && half_dt >= 0.0, "xeq_npt_back: half time step %g", half_dt);
+  XEQ_CHECK_ARG(md_finite(kappa) && kappa >= 0.0 && md_finite(p0) && md_finite(p_unit),
+                "xeq_npt_back: barostat (dt / taup * beta / 3 = %g >= 0, target pressure %g, pressure unit %g)", kappa, p0, p_unit);
+  XEQ_CHECK_ARG(record_every >= 0 && record_rows >= 0 && record_start >= 0, "xeq_npt_back: recorder (%lld, %lld, %lld)", (long long)record_every,
+                (long long)record_start, (long long)record_rows);
+  XEQ_CHECK_ARG(book && n_edges_step && box && virial_step && virial, "xeq_npt_back: null step counter, edge count, box record or virial");
+  XEQ_CHECK_ARG(!reps_needed || (reps && reps_seen), "xeq_npt_back: image counts of the step without the captured counts or the running maximum");
+  XEQ_CHECK_ARG(pos && vel && frc && frc_step && inv_mass && half_mass && chunk_atom0 && chunk_n && partial && partial_bad,
+                "xeq_npt_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(energy_step && graph_chunk_ptr && ke && epot, "xeq_npt_back: null per-graph buffer");
+  const bool rec = advance && record_every > 0 && record_rows > 0;
+  XEQ_CHECK_ARG(!rec || (traj_pos && traj_epot && traj_ekin && traj_step && traj_cell && traj_pressure && image), "xeq_npt_back: null trajectory buffer");
+  XEQ_DISPATCH_FLOAT(dtype, {
+    MdBox any{};
+    any.any = any.periodic[0] = any.periodic[1] = any.periodic[2] = 1;   // (the recorder's cell is the record's: NptBox::cell)
+    MdBackArgs<T> a{n, 1, n_chunks, advance ? 1 : 0, (const T*)pos, (T*)vel, (T*)frc, (const T*)frc_step, (const T*)energy_step, n_edges_step,
+                    (const T*)inv_mass, (const T*)half_mass, chunk_atom0, chunk_n, graph_chunk_ptr, partial, partial_bad, (T*)ke, (T*)epot, book, half_dt,
+                    image, any, rec ? record_every : 0, record_start, record_rows, (T*)traj_pos, (T*)traj_epot, (T*)traj_ekin, traj_step};
+    NptBox<T> bx{(const T*)virial_step, (T*)virial, box, reps_needed, reps_seen, {reps ? reps[0] : 0, reps ? reps[1] : 0, reps ? reps[2] : 0},
+                 kappa, p0, p_unit, (T*)traj_cell, traj_pressure};
+    hipLaunchKernelGGL(k_npt_back<T>, dim3((unsigned)n_chunks), dim3(MD_CHUNK), 0, (hipStream_t)stream, a, bx);
+    XEQ_CHECK_LAUNCH("xeq_npt_back");
+    if (n_chunks != 1) hipLaunchKernelGGL(k_npt_join<T>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, bx);
+  });
+  XEQ_CHECK_LAUNCH("xeq_npt_back");
   return XEQ_OK;
 }
 

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("XEQ_LIB_PATH") or os.path.join(_HERE, "libxeq_hip.so"
 XEQ_F32, XEQ_F64 = 0, 1
 COPY_MANY_MAX = 16       # XEQ_COPY_MANY_MAX of include/xeq.h
 MD_CHUNK = 256          # XEQ_MD_CHUNK of include/xeq.h: atoms per kinetic-energy chunk (md.py, optimize.py)
+NPT_BOX, NPT_CELL, NPT_INV, NPT_CELL_NEXT, NPT_INV_NEXT, NPT_MU, NPT_P, NPT_V = 40, 0, 9, 18, 27, 36, 37, 38      # XEQ_NPT_* of include/xeq.h (md.py)
 FIRE_FRESH, FIRE_ACTIVE, FIRE_CONVERGED = 0, 1, 2      # XEQ_FIRE_* of include/xeq.h
 VIB_MAX_DIM, VIB_MAX_SWEEPS = 96, 30     # XEQ_VIB_MAX_DIM, XEQ_VIB_MAX_SWEEPS of include/xeq.h (vibrations.py)
 VIB_ROTORS = ("atom", "linear", "nonlinear")      # XEQ_VIB_ATOM, _LINEAR, _NONLINEAR
@@ -235,6 +236,10 @@ _PROTOS = {
                      ctypes.POINTER(c_double), _I3, _P, _P],
     "xeq_md_back": [c_int, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_double,
                     ctypes.POINTER(c_double), _I3, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P],
+    "xeq_pbc_tables_device": [c_int, _P, _I3, _I3, c_double, _P, c_int64, _P, _P],
+    "xeq_npt_front": [c_int, c_int64, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_double, _P, _P, _P, _P],
+    "xeq_npt_back": [c_int, c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _I3, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                     c_double, c_double, c_double, c_double, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P],
     "xeq_fire_front": [c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(c_double), _I3, _P, _P],
     "xeq_fire_back": [c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                       c_double, c_double, c_double, c_int, c_double, c_double, c_double, c_double, ctypes.POINTER(c_double), _I3, _P, c_int64, c_int64,

@@ -14,11 +14,17 @@ without a re-capture.  Measured (profiles/md_timing.txt): with its arguments bou
 aspirin step that takes the GPU 0.38 ms, and 0.02-0.03 ms for 1 024 molecules; one captured graph per MD step was tried and gave the
 same device time and the same 0.13 ms, so it was not kept.
 
+``ensemble="npt_berendsen"`` adds ASE's Berendsen barostat for one box periodic along all three axes.  The box then
+lives on the device: the step is built with ``compute_virial=True, device_cell=True`` (its graph starts with the kernel that forms the cell
+tables from the static cell), ``xeq_npt_back`` forms pressure, scale factor and the pending cell from the step's virial, ``xeq_npt_front``
+applies them; a box that shrank until the cutoff reaches a further image voids the window as an outgrown edge capacity does (resident.py).
+
 A batch of independent open-boundary molecules (``ptr``) runs on GraphedStep, one periodic box (``cell``) on GraphedStepPBC; the models
 those classes refuse are refused here by constructing them.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, Optional
 
@@ -30,20 +36,23 @@ from .lib import call, dtype_code, require_hip
 from .resident import ResidentDriver, chunk_tables  # noqa: F401  (chunk_tables: part of this module's interface)
 from .utils import units as _units
 
-ENSEMBLES = {"nve": 0, "langevin": 1, "berendsen": 2}        # XEQ_MD_NVE / _LANGEVIN / _BERENDSEN of include/xeq.h
+ENSEMBLES = {"nve": 0, "langevin": 1, "berendsen": 2,        # XEQ_MD_NVE / _LANGEVIN / _BERENDSEN of include/xeq.h
+             "npt_berendsen": 2}                              # (its thermostat; the barostat has entries of its own: xeq_npt_front / _back)
+NPT = "npt_berendsen"
 PURPOSE_LANGEVIN, PURPOSE_MAXWELL = 0, 1                     # XEQ_MD_PURPOSE_*
 BOLTZMANN_J_PER_K = 1.380649e-23                             # exact (SI 2019)
 
 
 def unit_factors(energy_unit: str, length_unit: str) -> Dict[str, float]:
-    """``accel``: (energy / length) / (g / mol) in length / fs^2; ``kB``: the Boltzmann constant in energy / K -- from the constants of
-    utils/units.py (the table holds every unit in atomic units) and k_B in J / K."""
+    """``accel``: (energy / length) / (g / mol) in length / fs^2; ``kB``: the Boltzmann constant in energy / K; ``GPa``: one GPa
+    (1e9 J / m^3) in energy / length^3 -- from the constants of utils/units.py (the table holds every unit in atomic units) and k_B in
+    J / K."""
     joule, metre = _units.eval_unit("J"), _units.eval_unit("m")
     e_j = _units.eval_unit(energy_unit) / joule                  # one energy unit in J
     l_m = _units.eval_unit(length_unit) / metre                  # one length unit in m
     kg_per_gmol = 1.0e-3 / _units.eval_unit("mol")               # one g / mol in kg
     fs = 1.0e-15
-    return {"accel": e_j / (l_m * kg_per_gmol) * fs * fs / l_m, "kB": BOLTZMANN_J_PER_K / e_j}
+    return {"accel": e_j / (l_m * kg_per_gmol) * fs * fs / l_m, "kB": BOLTZMANN_J_PER_K / e_j, "GPa": 1.0e9 * l_m**3 / e_j}
 
 
 def default_rng_id(ptr_host) -> np.ndarray:
@@ -68,12 +77,17 @@ def normals(seed: int, purpose: int, step: int, rng_id: torch.Tensor, dtype=torc
 class Dynamics(ResidentDriver):
     """``Dynamics(model, pos, atomic_numbers, masses, ptr=... | cell=..., timestep_fs=..., ensemble=...)``: see the module text and
     DESIGN.md section 12.  ``masses`` [N] in g / mol (0 or inf: a fixed atom); ``ensemble``: "nve" (velocity Verlet), "langevin" (BAOAB;
-    ``temperature_K``, ``friction_per_fs``), "berendsen" (``temperature_K``, ``taut_fs``)."""
+    ``temperature_K``, ``friction_per_fs``), "berendsen" (``temperature_K``, ``taut_fs``), "npt_berendsen" (one box periodic along all
+    three axes; the Berendsen thermostat and ASE's NPTBerendsen barostat: ``temperature_K``, ``taut_fs``, ``pressure_GPa``, ``taup_fs``,
+    ``compressibility_per_GPa``).  The box of an NPT run lives on the device: ``cell``, ``volume``, ``pressure``
+    and ``virial`` read it; ``min_images`` (three ints) captures the step's graph with more periodic images than the first cell needs."""
 
     def __init__(self, model, pos: torch.Tensor, atomic_numbers: torch.Tensor, masses: torch.Tensor, *, ptr: Optional[torch.Tensor] = None,
                  cell: Optional[torch.Tensor] = None, pbc=None, timestep_fs: float, ensemble: str = "nve", temperature_K: Optional[float] = None,
                  friction_per_fs: Optional[float] = None, taut_fs: Optional[float] = None, seed: int = 0, rng_id: Optional[torch.Tensor] = None,
-                 edge_capacity: Optional[int] = None, energy_unit: Optional[str] = None, length_unit: Optional[str] = None) -> None:
+                 edge_capacity: Optional[int] = None, energy_unit: Optional[str] = None, length_unit: Optional[str] = None,
+                 pressure_GPa: Optional[float] = None, taup_fs: Optional[float] = None, compressibility_per_GPa: Optional[float] = None,
+                 min_images=None) -> None:
         if ensemble not in ENSEMBLES:
             raise ValueError(f"Dynamics: ensemble {ensemble!r} (one of {sorted(ENSEMBLES)})")
         self.ensemble = ensemble
@@ -84,12 +98,28 @@ class Dynamics(ResidentDriver):
             raise ValueError(f"Dynamics: ensemble {ensemble!r} needs temperature_K >= 0")
         if ensemble == "langevin" and (friction_per_fs is None or not friction_per_fs >= 0.0):
             raise ValueError("Dynamics: ensemble 'langevin' needs friction_per_fs >= 0")
-        if ensemble == "berendsen" and (taut_fs is None or not taut_fs > 0.0):
-            raise ValueError("Dynamics: ensemble 'berendsen' needs taut_fs > 0")
+        if ensemble in ("berendsen", NPT) and (taut_fs is None or not taut_fs > 0.0):
+            raise ValueError(f"Dynamics: ensemble {ensemble!r} needs taut_fs > 0")
+        self._npt = ensemble == NPT
+        if self._npt:
+            if ptr is not None or cell is None:
+                raise ValueError("Dynamics: ensemble 'npt_berendsen' needs ONE periodic box: a cell and no ptr")
+            open_axes = [] if pbc is None else [k for k, v in enumerate(pbc.tolist() if isinstance(pbc, torch.Tensor) else pbc) if not v]
+            if open_axes:
+                raise ValueError(f"Dynamics: ensemble 'npt_berendsen' needs all three axes periodic (pbc is open along {open_axes})")
+            if taup_fs is None or not (taup_fs > 0.0 and math.isfinite(taup_fs)):
+                raise ValueError("Dynamics: ensemble 'npt_berendsen' needs taup_fs > 0")
+            if pressure_GPa is None or not math.isfinite(pressure_GPa):
+                raise ValueError("Dynamics: ensemble 'npt_berendsen' needs a finite pressure_GPa")
+            if compressibility_per_GPa is None or not (compressibility_per_GPa >= 0.0 and math.isfinite(compressibility_per_GPa)):
+                raise ValueError("Dynamics: ensemble 'npt_berendsen' needs compressibility_per_GPa >= 0")
+        elif not (pressure_GPa is None and taup_fs is None and compressibility_per_GPa is None and min_images is None):
+            raise ValueError(f"Dynamics: pressure_GPa, taup_fs, compressibility_per_GPa and min_images belong to ensemble 'npt_berendsen', not {ensemble!r}")
         N = int(pos.shape[0])
         if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,) or masses.shape != (N,):
             raise ValueError("Dynamics: pos [N, 3], atomic_numbers [N] and masses [N] are needed")
-        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, masses, ptr, cell, rng_id))
+        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, masses, ptr, cell, rng_id),
+                          dict(compute_virial=True, device_cell=True, min_images=min_images) if self._npt else None)
         ptr_host, dev, dt_ = self.ptr_host, self.device, self.dtype
 
         u = _units.get_default_units()
@@ -103,6 +133,10 @@ class Dynamics(ResidentDriver):
         self._c1 = math.exp(-gamma * self.dt)
         self._noise2 = (1.0 - self._c1 * self._c1) * self.kB * (self.temperature_K or 0.0)
         self._dt_over_tau = 0.0 if taut_fs is None else self.dt / float(taut_fs)
+        if self._npt:       # mu = 1 - kappa (P0 - P) with P in energy / length^3
+            self._p_unit = 1.0 / fac["GPa"]
+            self._p0 = float(pressure_GPa) * fac["GPa"]
+            self._kappa = (self.dt / float(taup_fs)) * (float(compressibility_per_GPa) / fac["GPa"] / 3.0)
 
         m = masses.detach().double().cpu().numpy()
         free = np.isfinite(m) & (m > 0.0)
@@ -126,7 +160,7 @@ class Dynamics(ResidentDriver):
         self.image = torch.zeros((N, 3), dtype=torch.int32, device=dev)
         self.ke = torch.zeros(G, dtype=dt_, device=dev)
         self.epot = torch.zeros(G, dtype=dt_, device=dev)
-        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # steps done, largest n_edges, non-finite flag, unused
+        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # steps done, largest n_edges, non-finite flag, (NPT) more images needed
         self._ck = None
         self._steps_host = 0
         self._fresh = False            # frc / ke / epot belong to the current positions and velocities
@@ -139,11 +173,27 @@ class Dynamics(ResidentDriver):
         self._run_serial = 0           # (part of the cache key of xeq_md_back's arguments: every run has its own trajectory buffers)
 
         self._load_system(pos, atomic_numbers, cell, pbc)
-        call("xeq_md_front", *self._front_tuple(0.0), lib.stream())     # dt = 0: the wrap alone: the search sweeps +- reps images around the box, not around a stray atom
+        if self._npt:
+            # the box record of include/xeq.h (XEQ_NPT_*): current = pending = the cell the step object holds, mu = 1
+            c = (ctypes.c_double * 9)(*self._cell_c)
+            inv = (ctypes.c_double * 9)()
+            call("xeq_md_inverse_cell", c, inv)
+            rec = np.zeros(lib.NPT_BOX)
+            rec[lib.NPT_CELL : lib.NPT_CELL + 9] = rec[lib.NPT_CELL_NEXT : lib.NPT_CELL_NEXT + 9] = np.array(c)
+            rec[lib.NPT_INV : lib.NPT_INV + 9] = rec[lib.NPT_INV_NEXT : lib.NPT_INV_NEXT + 9] = np.array(inv)
+            rec[lib.NPT_MU] = 1.0
+            self.box = on(rec, torch.float64)
+            self.vir = torch.zeros(9, dtype=dt_, device=dev)
+            self.reps_seen = torch.zeros(3, dtype=torch.int32, device=dev)
+        self._front_name, self._back_name = ("xeq_npt_front", "xeq_npt_back") if self._npt else ("xeq_md_front", "xeq_md_back")
+        call(self._front_name, *self._front_tuple(0.0), lib.stream())     # dt = 0: the wrap alone: the search sweeps +- reps images around the box, not around a stray atom
 
     # ------------------------------------------------------------------------------------------------ launches
     def _front_tuple(self, dt: float):
         p = lib.ptr
+        if self._npt:
+            return (self._code, self.n_atoms, p(self._pos), p(self.vel), p(self.frc), p(self.inv_mass), p(self.step.batch), p(self.ke), p(self.tfac),
+                    dt, self._dt_over_tau, self.temperature_K or 0.0, p(self.box), p(self.step.cell), p(self.image))
         return (self._code, ENSEMBLES[self.ensemble], self.n_atoms, self.n_graphs, p(self._pos), p(self.vel), p(self.frc), p(self.inv_mass),
                 p(self.step.batch), p(self.ke), p(self.tfac), p(self.rng_id), p(self.book), self.seed, dt, self._c1, self._noise2,
                 self._dt_over_tau, self.temperature_K or 0.0, self._cell_c, self._pbc_c, p(self.image))
@@ -152,11 +202,12 @@ class Dynamics(ResidentDriver):
         if dt == self.dt:
             if self._front_args is None:
                 self._front_args = self._front_tuple(dt)          # (every buffer named here lives as long as this object)
-            call("xeq_md_front", *self._front_args, lib.stream())
+            call(self._front_name, *self._front_args, lib.stream())
         else:
-            call("xeq_md_front", *self._front_tuple(dt), lib.stream())
+            call(self._front_name, *self._front_tuple(dt), lib.stream())
 
     def _back_tuple(self, outputs, frc=None, energy=None, n_edges=None, record=True):
+        """The arguments of the back entry behind (dtype, advance); ``outputs`` None: the driver's own copies (``_back_ke``)."""
         p = lib.ptr
         frc = outputs[keys.FORCES] if frc is None else frc
         en = outputs[keys.TOTAL_ENERGY] if energy is None else energy
@@ -164,6 +215,15 @@ class Dynamics(ResidentDriver):
         assert frc.is_contiguous() and frc.dtype == self.dtype and en.is_contiguous() and en.dtype == self.dtype and ne.dtype == torch.int32
         t = self.trajectory if record else {}
         every, start, rows = self._rec if record else (0, 0, 0)
+        if self._npt:
+            vir = self.vir if outputs is None else outputs[keys.VIRIAL]
+            needed = None if outputs is None else outputs["reps_needed"]
+            assert vir.is_contiguous() and vir.dtype == self.dtype and vir.numel() == 9
+            return (self.n_atoms, self.n_chunks, p(self._pos), p(self.vel), p(self.frc), p(frc), p(en), p(ne), p(vir), p(needed), lib.mul3(self.step.reps),
+                    p(self.inv_mass), p(self.half_mass), p(self._chunk_atom0), p(self._chunk_n), p(self._graph_chunk_ptr), p(self._partial),
+                    p(self._partial_bad), p(self.ke), p(self.epot), p(self.vir), p(self.reps_seen), p(self.book), p(self.box), 0.5 * self.dt, self._kappa,
+                    self._p0, self._p_unit, p(self.image), every, start, rows, p(t.get("pos")), p(t.get("epot")), p(t.get("ekin")), p(t.get("step")),
+                    p(t.get("cell")), p(t.get("pressure")))
         return (self.n_atoms, self.n_graphs, self.n_chunks, p(self._pos), p(self.vel), p(self.frc), p(frc), p(en), p(ne), p(self.inv_mass),
                 p(self.half_mass), p(self._chunk_atom0), p(self._chunk_n), p(self._graph_chunk_ptr), p(self._partial), p(self._partial_bad),
                 p(self.ke), p(self.epot), p(self.book), 0.5 * self.dt, self._cell_c, self._pbc_c, p(self.image), every, start, rows,
@@ -173,12 +233,12 @@ class Dynamics(ResidentDriver):
         key = (self.step.captures, self._rec, self._run_serial)
         if self._back_args is None or self._back_args[0] != key:
             self._back_args = (key, self._back_tuple(self.step.outputs))
-        call("xeq_md_back", self._code, int(advance), *self._back_args[1], lib.stream())
+        call(self._back_name, self._code, int(advance), *self._back_args[1], lib.stream())
 
     def _back_ke(self) -> None:
         """The kinetic energies of new velocities: the back kernel without a kick on the forces and energies this object holds (they
         depend on the positions alone); no evaluation, no read-back."""
-        call("xeq_md_back", self._code, 0, *self._back_tuple(None, self.frc, self.epot, self._no_edges, record=False), lib.stream())
+        call(self._back_name, self._code, 0, *self._back_tuple(None, self.frc, self.epot, self._no_edges, record=False), lib.stream())
         self._ke_stale = False
 
     def _enqueue(self, n: int) -> None:
@@ -188,27 +248,36 @@ class Dynamics(ResidentDriver):
         # the step's own graph between two launches.  The first evaluation goes through the step object's logic; nothing can move the
         # weights between that one and the window's check, so the others replay the graph it left.  Arguments are bound once.
         L = lib.load()
-        front, back = L.xeq_md_front, L.xeq_md_back
+        front, back = getattr(L, self._front_name), getattr(L, self._back_name)
         if self._front_args is None:
             self._front_args = self._front_tuple(self.dt)
         stream = lib.stream()
         fa = (*self._front_args, stream)
         if front(*fa):
-            raise RuntimeError(f"xeq_md_front failed: {L.xeq_last_error().decode()}")
+            raise RuntimeError(f"{self._front_name} failed: {L.xeq_last_error().decode()}")
         self._eval()
         self._back(True)
         ba = (self._code, 1, *self._back_args[1], stream)
         replay = self.step.graph.replay
         for _ in range(n - 1):
             if front(*fa):
-                raise RuntimeError(f"xeq_md_front failed: {L.xeq_last_error().decode()}")
+                raise RuntimeError(f"{self._front_name} failed: {L.xeq_last_error().decode()}")
             replay()
             if back(*ba):
-                raise RuntimeError(f"xeq_md_back failed: {L.xeq_last_error().decode()}")
+                raise RuntimeError(f"{self._back_name} failed: {L.xeq_last_error().decode()}")
 
     # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
     def _state(self):
-        return [self._pos, self.image, self.vel, self.frc, self.ke, self.epot, self.book]
+        state = [self._pos, self.image, self.vel, self.frc, self.ke, self.epot, self.book]
+        return state + [self.step.cell, self.box, self.vir, self.reps_seen] if self._npt else state
+
+    def _images_wanted(self):
+        if not (self._npt and self._book_extra):
+            return None
+        return [int(v) for v in self._to_host(self.reps_seen)]         # (read BEFORE the checkpoint comes back)
+
+    def _current_cell(self) -> torch.Tensor:
+        return self.box[lib.NPT_CELL : lib.NPT_CELL + 9].view(3, 3) if self._npt else self._cell_dev
 
     def _before_window(self) -> None:
         if self._fresh and self._ke_stale:
@@ -240,6 +309,9 @@ class Dynamics(ResidentDriver):
                                "epot": torch.zeros((rows, self.n_graphs), dtype=self.dtype, device=self.device),
                                "ekin": torch.zeros((rows, self.n_graphs), dtype=self.dtype, device=self.device),
                                "step": torch.zeros(rows, dtype=torch.int64, device=self.device)}
+            if self._npt:
+                self.trajectory["cell"] = torch.zeros((rows, 3, 3), dtype=self.dtype, device=self.device)
+                self.trajectory["pressure"] = torch.zeros(rows, dtype=torch.float64, device=self.device)          # GPa
             self._rec = (record_every, self._steps_host, rows)
         else:
             self.trajectory, self._rec = {}, (0, 0, 0)
@@ -307,3 +379,31 @@ class Dynamics(ResidentDriver):
         """T_g = 2 KE_g / (3 n_free,g k_B); 0 for a graph without a free atom."""
         self._settle()
         return self.ke * self.tfac
+
+    # ------------------------------------------------------------------------------------------------ the box of an NPT run
+    def _box_entry(self, k: int) -> torch.Tensor:
+        if not self._npt:
+            raise AttributeError(f"Dynamics: ensemble {self.ensemble!r} keeps no pressure, volume or virial (ensemble 'npt_berendsen' does)")
+        self._settle()
+        return self.box[k].clone()
+
+    @property
+    def cell(self) -> torch.Tensor:
+        """[3, 3], rows = lattice vectors: the box the positions and images belong to."""
+        return self.step.cell.reshape(3, 3).clone() if self.periodic else None
+
+    @property
+    def volume(self) -> torch.Tensor:
+        """|det cell| in length^3 (f64, on the device)."""
+        return self._box_entry(lib.NPT_V)
+
+    @property
+    def pressure(self) -> torch.Tensor:
+        """(2 KE + tr W) / (3 V) in GPa (f64, on the device)."""
+        return self._box_entry(lib.NPT_P) * self._p_unit
+
+    @property
+    def virial(self) -> torch.Tensor:
+        """[1, 3, 3]: minus dE/dstrain of the current positions and box."""
+        self._box_entry(lib.NPT_V)
+        return self.vir.view(1, 3, 3).clone()

@@ -35,7 +35,8 @@ class ResidentDriver:
     the current positions), ``_ck = None``; and defines ``_state()`` (the tensors of a checkpoint), ``_first_evaluation()``,
     ``_enqueue(n)``, ``_bad_message(first, n)`` and, if it needs one, ``_before_window()``."""
 
-    def _init_system(self, model, N: int, ptr: Optional[torch.Tensor], cell: Optional[torch.Tensor], edge_capacity: Optional[int], tensors) -> None:
+    def _init_system(self, model, N: int, ptr: Optional[torch.Tensor], cell: Optional[torch.Tensor], edge_capacity: Optional[int], tensors,
+                     step_kwargs=None) -> None:
         """The step object FIRST -- it refuses the models the whole-step classes do not take, whatever device the tensors are on -- then
         the no-CPU-fallback checks, the device, the state type and the chunk tables."""
         who = type(self).__name__
@@ -53,7 +54,7 @@ class ResidentDriver:
             if edge_capacity is None:       # from the density; a list that outgrows it is met by the restore protocol
                 vol = abs(float(np.linalg.det(cell_h)))
                 edge_capacity = int(1.25 * N * (N / vol if vol > 0 else 0.0) * 4.0 / 3.0 * math.pi * cutoff**3) + 64
-            self.step = GraphedStepPBC(model, N, int(edge_capacity))
+            self.step = GraphedStepPBC(model, N, int(edge_capacity), **(step_kwargs or {}))
             self._explicit_capacity = False
         else:
             self._explicit_capacity = edge_capacity is not None
@@ -95,16 +96,25 @@ class ResidentDriver:
     def _read_book(self):
         """THE read-back: (counter, largest n_edges since the last check, non-finite flag); the fourth entry is kept in ``_book_extra``.
         A sync-debug guard of the caller is lifted for exactly this call."""
+        vals = self._to_host(self.book)
+        self._book_extra = int(vals[3])
+        return int(vals[0]), int(vals[1]), bool(vals[2])
+
+    @staticmethod
+    def _to_host(t: torch.Tensor) -> list:
         mode = torch.cuda.get_sync_debug_mode()
         if mode:
             torch.cuda.set_sync_debug_mode(0)
         try:
-            vals = self.book.cpu().tolist()
+            return t.cpu().tolist()
         finally:
             if mode:
                 torch.cuda.set_sync_debug_mode(mode)
-        self._book_extra = int(vals[3])
-        return int(vals[0]), int(vals[1]), bool(vals[2])
+
+    def _images_wanted(self):
+        """The image counts per axis a box that moved on the device needs, if the window met more than the step's graph was captured for
+        (md.Dynamics with a barostat); None otherwise."""
+        return None
 
     # ------------------------------------------------------------------------------------------------ check / restore
     def _save(self) -> None:
@@ -125,8 +135,9 @@ class ResidentDriver:
         """``n`` steps and one check behind them.  A list that outgrew the edge capacity voids the window: back to the checkpoint, more
         room (GraphedStepPBC.grow), a new capture, the same steps again -- everything a step uses is a function of the checkpointed state
         (the random stream of the dynamics of (seed, purpose, id, step)), so the second pass gives what a run with room from the start
-        gives, bit for bit.  A non-finite force or energy also puts the checkpoint back before it raises: the object stays at the last
-        state that was checked."""
+        gives, bit for bit.  A box that shrank until the cutoff reaches a further image voids the window the same way (more images:
+        GraphedStepPBC.grow_images), and the two compose.  A non-finite force or energy also puts the checkpoint back before it raises:
+        the object stays at the last state that was checked."""
         who = type(self).__name__
         first = self._steps_host
         self._before_window()
@@ -137,9 +148,14 @@ class ResidentDriver:
             self._enqueue(n)
             steps, most, bad = self._read_book()
             cap = self.step.n_edges
-            if most <= cap:
+            images = self._images_wanted()
+            if most <= cap and images is None:
                 break
             self._restore()
+            if images is not None:
+                self.step.grow_images(images)
+            if most <= cap:
+                continue
             if not self.periodic:
                 raise ValueError(f"{who}: the neighbour list reached {most} edges, the edge capacity is {cap}" +
                                  (" (edge_capacity was given: pass a larger one)" if self._explicit_capacity else ""))
@@ -158,11 +174,15 @@ class ResidentDriver:
     def positions(self) -> torch.Tensor:
         return self._pos.clone()
 
+    def _current_cell(self) -> torch.Tensor:
+        """The box as f64 [3, 3] on the device (fixed for the run unless a driver moves it)."""
+        return self._cell_dev
+
     @property
     def unwrapped_positions(self) -> torch.Tensor:
         """pos + image . cell, in the operation order of the recorder (csrc/xeq_md.hip): the two agree bit for bit."""
         if not self._any_pbc:
             return self._pos.clone()
-        i, c = self.image.double(), self._cell_dev
+        i, c = self.image.double(), self._current_cell()
         x = self._pos.double()
         return (x + ((i[:, 0:1] * c[0] + i[:, 1:2] * c[1]) + i[:, 2:3] * c[2])).to(self.dtype)

@@ -804,12 +804,21 @@ class GraphedStepPBC:
     results the caller reads anyway: a list that outgrew the capacity (``n_edges > capacity``: the kernels cut it, nothing is
     written out of bounds) re-captures with half as much room again and re-runs the step.
 
-    Same kernels in the same order as the eager GROMACS-style model: bit-identical results (tests/test_gpu_interface.py)."""
+    Same kernels in the same order as the eager GROMACS-style model: bit-identical results (tests/test_gpu_interface.py).
+
+    ``compute_virial=True`` asks the model for the virial too: ``outputs["virial"]`` [1, 3, 3], minus dE/dstrain (the reference's
+    convention).  ``device_cell=True`` makes the static ``cell`` THE box (a barostat on the device rescales it between replays,
+    md.Dynamics(ensemble="npt_berendsen")): the host loads the first cell and chooses the image counts once, and the first node of the
+    graph is ``xeq_pbc_tables_device``, which fills the table buffer from ``cell`` for those counts -- the host function's values bit
+    for bit -- and writes what the cell would need into ``outputs["reps_needed"]`` (int32 [3]); a caller that sees an entry above
+    ``reps`` calls ``grow_images``.  ``min_images`` (three ints) raises the counts above what the first cell needs; a larger image
+    table yields the same edge list in the same order.  The defaults are the path described above, launch for launch."""
 
     GROWTH = 1.5
 
     def __init__(self, model, n_atoms: int, edge_capacity: int, cutoff: Optional[float] = None,
-                 compute_forces: bool = True, warmup: int = 2) -> None:
+                 compute_forces: bool = True, warmup: int = 2, compute_virial: bool = False, device_cell: bool = False,
+                 min_images=None) -> None:
         """``model``: a BaseModel, or any callable ``(data, compute_forces, compute_virial) -> results`` that wraps one in ``.model``
         (the MD front ends' unit-free core)."""
         refuse_electronic(model, "GraphedStepPBC")
@@ -818,9 +827,15 @@ class GraphedStepPBC:
         self.n_atoms, self.n_edges = int(n_atoms), int(edge_capacity)
         self.cutoff = float(net.cutoff_radius if cutoff is None else cutoff)
         self.compute_forces = compute_forces
+        self.compute_virial = bool(compute_virial)
+        self.device_cell = bool(device_cell)
+        self.min_images = [0, 0, 0] if min_images is None else [int(v) for v in min_images]
+        if len(self.min_images) != 3 or min(self.min_images) < 0 or max(self.min_images) > 64:
+            raise ValueError(f"GraphedStepPBC: min_images {min_images} (three counts in 0 .. 64)")
         p = next(net.parameters())
         self.device, self.dtype = p.device, p.dtype
         N = self.n_atoms
+        self.reps_needed = torch.zeros(3, dtype=torch.int32, device=self.device) if self.device_cell else None
         self.pos = torch.zeros((N, 3), dtype=self.dtype, device=self.device)
         self.shift = torch.zeros((N, 3), dtype=self.dtype, device=self.device)          # positions are not wrapped (jit_model.py:189-195)
         self.z = torch.zeros(N, dtype=torch.int32, device=self.device)
@@ -846,6 +861,9 @@ class GraphedStepPBC:
         from .data.radius_graph import split_cell_tables
 
         n_cells = (2 * self._reps[0] + 1) * (2 * self._reps[1] + 1) * (2 * self._reps[2] + 1)
+        if self.device_cell:                                # the tables follow the device's cell: the first node of the graph
+            lib.call("xeq_pbc_tables_device", lib.dtype_code(self.cell), lib.ptr(self.cell), lib.mul3(self._reps), lib.mul3(self._pbc),
+                     self.cutoff, lib.ptr(self._tab_flat), int(self._tab_flat.numel()), lib.ptr(self.reps_needed), lib.stream())
         tab = split_cell_tables(self._tab_flat, 1, n_cells, False)
         rowptr, count = ops.radius_graph_pbc_capacity(self.pos, self.ptr, tab["pbc_offsets"], tab["cell_offsets"], self.shift, self.cutoff,
                                                       (tab["recip"], tab["thr"], self._reps), self.edge_index, self.cell_offsets)
@@ -855,9 +873,11 @@ class GraphedStepPBC:
                 keys.CELL_OFFSETS: self.cell_offsets, keys.BATCH: self.batch, keys.BATCH_PTR: self.ptr, keys.EDGE_GRAPH: eg}
         _offer_zero_start(self, data)
         with torch.enable_grad():
-            out = self.model(data, compute_forces=self.compute_forces, compute_virial=False)
+            out = self.model(data, compute_forces=self.compute_forces, compute_virial=self.compute_virial)
         res = {k: v.detach() for k, v in out.items() if isinstance(v, torch.Tensor)}
         res["n_edges"] = count                              # device-side edge count of the FULL list (above the capacity: see check)
+        if self.device_cell:
+            res["reps_needed"] = self.reps_needed
         return res
 
     def _load_cell(self, cell: torch.Tensor, pbc) -> None:
@@ -878,6 +898,9 @@ class GraphedStepPBC:
         if self._cell_host is not None and pbc_ == self._pbc and np.array_equal(c, self._cell_host):
             return
         reps, n_cells, flat_h = host_cell_tables_np(c, pbc_, self.cutoff, False, dtype_code_of=self.cell)
+        more = [max(r, m) if per else r for r, m, per in zip(reps, self.min_images, pbc_)]
+        if more != reps:
+            reps, flat_h = more, self._host_tables(c, more)
         flat = torch.from_numpy(flat_h)
         if self._tab_flat is None or reps != self._reps or flat.numel() != self._tab_flat.numel():
             self._tab_flat = flat.to(self.device)
@@ -886,6 +909,40 @@ class GraphedStepPBC:
             self._tab_flat.copy_(flat, non_blocking=False)
         self._reps, self._pbc, self._cell_host = reps, pbc_, c
         self.cell.copy_(torch.from_numpy(c))
+
+    def _host_tables(self, c, reps):
+        """The host table of cell ``c`` (numpy [1, 3, 3]) for GIVEN image counts."""
+        import ctypes
+
+        import numpy as np
+
+        n_tab = 6 * (2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1) + 12
+        flat_h = np.empty(n_tab, dtype=c.dtype)
+        lib.call("xeq_pbc_tables_host", lib.dtype_code(self.cell), ctypes.c_void_p(c.ctypes.data), 1, lib.mul3(reps), float(self.cutoff),
+                 ctypes.c_void_p(flat_h.ctypes.data), n_tab)
+        return flat_h
+
+    def grow_images(self, reps_needed) -> None:
+        """More images per axis for a device cell that shrank (``outputs["reps_needed"]`` went above ``reps``): at least ``reps_needed``
+        on every axis, at least one more on some axis; the next replay captures again.  The table buffer is filled by the graph."""
+        if self._reps is None:
+            raise ValueError("GraphedStepPBC.grow_images: no cell was loaded")
+        want = [max(r, int(n)) if per else r for r, n, per in zip(self._reps, reps_needed, self._pbc)]
+        if want == self._reps:
+            want = [r + 1 if per else r for r, per in zip(self._reps, self._pbc)]
+        if max(want) > 64:
+            raise ValueError(f"GraphedStepPBC.grow_images: {want} images per axis (degenerate cell?)")
+        self._reps, self.min_images = want, [max(a, b) for a, b in zip(want, self.min_images)]
+        n_tab = 6 * (2 * want[0] + 1) * (2 * want[1] + 1) * (2 * want[2] + 1) + 12
+        self._tab_flat = torch.zeros(n_tab, dtype=self.dtype, device=self.device)
+        if not self.device_cell:                             # (a host-owned box: its table comes from the host)
+            self._tab_flat.copy_(torch.from_numpy(self._host_tables(self._cell_host, want)))
+        self.graph = None
+
+    @property
+    def reps(self):
+        """Images per axis of the captured table."""
+        return None if self._reps is None else list(self._reps)
 
     def _run(self) -> None:
         state = _params_state(self)
