@@ -982,14 +982,71 @@ int xeq_ewald_layernorm_fwd(const void* x, int64_t n, int node_dim, const void* 
 int xeq_ewald_layernorm_bwd(const void* g, const void* x, const void* stats, const void* weight, int64_t n, int node_dim, void* g_x, void* stream);
 int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const void* pre, int64_t count, void* out, void* stream);
 
-/* Device-resident molecular dynamics around a whole-step graph (xequinet_amd/md.py, csrc/xeq_md.hip), f32 / f64.
- * One MD step is xeq_md_front, the step's graph on the step object's static buffers, xeq_md_back; nothing reaches the host between them.
- * Per-atom arithmetic runs in double whatever `dtype` is and is rounded once where it is stored.
+/* Device-resident drivers around a whole-step graph (xequinet_amd/resident.py, csrc/xeq_md.hip): molecular dynamics (md.py, DESIGN.md
+ * sections 12 and 15) and batched FIRE geometry optimisation (optimize.py, section 13), f32 / f64.  One step is a FRONT entry, the step's
+ * graph on the step object's static buffers, a BACK entry; nothing reaches the host between them.
  *
- * Per-atom inputs, all of `dtype`: inv_mass [n] = A / m_i (A: the factor from force / mass to length / fs^2; 0: a FIXED atom, which
- * neither moves nor keeps a velocity), half_mass [n] = m_i / (2 A) (kinetic energy per squared velocity; 0 for a fixed atom).  batch [n]:
- * the atom's graph.  book: int64 [4] on the device = {steps done, largest n_edges seen, non-finite flag, xeq_npt_back's image flag}, maintained by
- * xeq_md_back with plain stores of one lane; the host resets entries 1 and 2 when it has read them.
+ * The six entries take their arguments as RECORDS, by pointer: what every driver has (the system, the step graph's outputs, the chunk
+ * tables, the recorder) and one record of parameters per driver.  Every member is 8 bytes wide -- a pointer, int64_t, uint64_t or double
+ * -- so a record's layout is its field order, without padding, on any ABI; xeq_record_bytes(which) gives the library's sizeof for a
+ * binding to compare with its own (-1: no such record).  A record is read during the call and not retained.  Pointers are device
+ * pointers unless marked HOST; `dtype` below: a buffer of the system record's floating type. */
+enum { XEQ_REC_SYSTEM = 0, XEQ_REC_STEP = 1, XEQ_REC_CHUNKS = 2, XEQ_REC_RECORDER = 3, XEQ_REC_MD = 4, XEQ_REC_NPT = 5, XEQ_REC_FIRE = 6 };
+int64_t xeq_record_bytes(int which);
+
+typedef struct xeq_res_system {
+  int64_t dtype;        /* XEQ_F32 / XEQ_F64 */
+  int64_t n;            /* atoms */
+  int64_t n_graphs;     /* graphs (the barostat's entries serve ONE box and do not read it) */
+  int64_t n_chunks;     /* entries of the chunk tables (xeq_res_chunks) */
+  void* pos;            /* [n, 3] `dtype`: the step object's static positions; a front updates pos, vel and image in place */
+  void* vel;            /* [n, 3] `dtype` */
+  void* frc;            /* [n, 3] `dtype`: the driver's forces, written by a back from frc_step */
+  int32_t* image;       /* [n, 3]: the periodic images an atom has crossed, kept by the wrap; needed with a cell and a periodic axis */
+  const int64_t* batch; /* [n]: the atom's graph */
+  int64_t* book;        /* int64 [4] = {steps done (FIRE: evaluations done), largest n_edges seen, non-finite flag, xeq_npt_back's image flag
+                           (FIRE: graphs not converged)}, maintained by the back entries with plain stores of one lane; the host resets
+                           entries 1 and 2 when it has read them */
+  const double* cell;   /* HOST: 9 doubles, rows = lattice vectors; NULL for open boundaries (the barostat's box is on the device:
+                           xeq_npt_params.box, and its entries read neither this nor pbc) */
+  const int32_t* pbc;   /* HOST: 3 int32; NULL for open boundaries */
+} xeq_res_system;
+
+/* The step graph's outputs and what it was captured with: the part that changes on a re-capture. */
+typedef struct xeq_res_step {
+  const void* frc_step;        /* [n, 3] `dtype` */
+  const void* energy_step;     /* [n_graphs] `dtype` */
+  const int32_t* n_edges_step; /* [1]: edges of the full list (above the capacity when it did not fit) */
+  const void* virial_step;     /* xeq_npt_back alone: [9] `dtype`, the step's virial W = -dE/dstrain */
+  const int32_t* reps_needed;  /* xeq_npt_back alone: [3], the images per axis the device's cell needs; NULL: no check */
+  int64_t reps[3];             /* xeq_npt_back alone: the images per axis the graph was captured with */
+} xeq_res_step;
+
+/* The fixed-order per-graph sums.  chunk_atom0 / chunk_n [n_chunks] name at most XEQ_MD_CHUNK consecutive atoms of ONE graph, counted
+ * from the graph's first atom; graph_chunk_ptr [n_graphs + 1] gives a graph's chunks.  The caller builds the three once from ptr. */
+typedef struct xeq_res_chunks {
+  const int32_t* chunk_atom0;
+  const int32_t* chunk_n;
+  const int32_t* graph_chunk_ptr;
+  double* partial;      /* [n_chunks] (FIRE: [n_chunks, 4]): the chunks' sums */
+  int32_t* partial_bad; /* [n_chunks]: the chunks' non-finite-force flags */
+} xeq_res_chunks;
+
+/* The trajectory a back entry writes.  A NULL record, every = 0 or rows = 0: nothing is recorded.  When d = book[0] - start behind the
+ * step (FIRE: book[0] read BEFORE the increment: this evaluation's number) is a positive multiple of `every`, row d / every - 1 (< rows)
+ * is written; the MD backs record with `advance` alone. */
+typedef struct xeq_res_recorder {
+  int64_t every, start, rows;
+  void* traj_pos;         /* [rows, n, 3] `dtype`, unwrapped: pos + image . cell (xeq_npt_back: by the current cell) */
+  void* traj_epot;        /* [rows, n_graphs] `dtype` */
+  void* traj_second;      /* [rows, n_graphs] `dtype`: the kinetic energy (dynamics), fmax (FIRE) */
+  int64_t* traj_step;     /* [rows] */
+  void* traj_cell;        /* xeq_npt_back alone: [rows, 3, 3] `dtype` */
+  double* traj_pressure;  /* xeq_npt_back alone: [rows], P p_unit */
+} xeq_res_recorder;
+
+/* Molecular dynamics (xequinet_amd/md.py).  Per-atom arithmetic runs in double whatever `dtype` is and is rounded
+ * once where it is stored.
  *
  * Generator: Philox4x32-10 with key = (seed low word, seed high word) and counter
  *   c0 = rng_id low word, c1 = rng_id high word, c2 = step low word, c3 = step bits 32 .. 61 | purpose << 30
@@ -1000,15 +1057,12 @@ int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const 
  *
  * xeq_md_front, per atom: [berendsen: v *= lambda_g, lambda_g = sqrt(1 + dt_over_tau (t0 / T_g - 1)) clamped to [0.9, 1.1] with
  * T_g = ke[g] tfac[g], and 1 where T_g is not positive]; v += dt / 2 * frc * inv_mass; [nve, berendsen: x += dt v] [langevin:
- * v' = c1 v + sqrt(noise2 inv_mass) z with z from (seed, 0, rng_id[i], book[0]); x += dt / 2 * (v + v'); v = v'] (noise2 = (1 - c1^2) k_B T);
+ * v' = c1 v + sqrt(noise2 inv_mass) z with z from (seed, 0, rng_id[i], book[0]); x += dt / 2 * (v + v'); v = v'];
  * then, with a cell and a periodic axis, the wrap: s = floor(x . inv(cell)) along the periodic axes, x -= s . cell, image [n, 3] += s
- * (applied twice: rounding to `dtype` can put an atom exactly on the far face).  cell: 9 doubles ON THE HOST (rows = lattice vectors),
- * pbc: 3 int32 on the host; both NULL for open boundaries.  pos, vel, image are updated in place.  dt = 0 is the wrap alone,
- * whatever the ensemble (no kick, no drift, no thermostat).
+ * (applied twice: rounding to `dtype` can put an atom exactly on the far face).  dt = 0 is the wrap alone, whatever the ensemble (no
+ * kick, no drift, no thermostat).
  *
  * xeq_md_back: the second half of a step.
- *   Chunks: chunk_atom0 / chunk_n [n_chunks] name at most XEQ_MD_CHUNK consecutive atoms of ONE graph, counted from the graph's first
- *   atom; graph_chunk_ptr [n_graphs + 1] gives a graph's chunks.  The caller builds the three once from ptr.
  *   First launch, one workgroup per chunk: frc = frc_step; with `advance`, v += half_dt * frc * inv_mass; the chunk's kinetic energy
  *   sum_i half_mass_i |v_i|^2 in double (lanes, butterfly, the four waves in order) into partial [n_chunks]; its non-finite-force flag
  *   into partial_bad [n_chunks]; the recorder's positions.
@@ -1016,72 +1070,70 @@ int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const 
  *   beyond), epot[g] = energy_step[g]; then one lane: book[0] += advance, book[1] = max(book[1], n_edges_step[0]), book[2] = 1 on a
  *   non-finite force or energy.  With a single chunk the first launch's workgroup does this part itself and there is no second launch.
  *   No atomics; a graph's ke has the same bits alone and anywhere in a batch.
- *   Recorder (record_every > 0 and advance): when d = book[0] - record_start behind this step is a positive multiple of record_every,
- *   row d / record_every - 1 (< record_rows) of traj_pos [rows, n, 3] (unwrapped: pos + image . cell), traj_epot / traj_ekin
- *   [rows, n_graphs] and traj_step [rows] is written.
  * xeq_md_inverse_cell: the inverse the wrap uses (host only; inv [9] with frac_k = sum_j x_j inv[3 j + k]). */
 #define XEQ_MD_CHUNK 256
 enum { XEQ_MD_NVE = 0, XEQ_MD_LANGEVIN = 1, XEQ_MD_BERENDSEN = 2 };
 enum { XEQ_MD_PURPOSE_LANGEVIN = 0, XEQ_MD_PURPOSE_MAXWELL = 1 };
+typedef struct xeq_md_params {
+  int64_t ensemble;        /* XEQ_MD_* (the barostat's entries run the Berendsen thermostat and do not read it) */
+  const void* inv_mass;    /* [n] `dtype` = A / m_i (A: the factor from force / mass to length / fs^2; 0: a FIXED atom, which neither
+                              moves nor keeps a velocity) */
+  const void* half_mass;   /* [n] `dtype` = m_i / (2 A) (kinetic energy per squared velocity; 0 for a fixed atom) */
+  void* ke;                /* [n_graphs] `dtype`: written by the back, read by the Berendsen thermostat */
+  void* epot;              /* [n_graphs] `dtype` */
+  const void* tfac;        /* [n_graphs] `dtype`: T_g = ke[g] tfac[g] */
+  const int64_t* rng_id;   /* [n]: the atoms' generator ids (langevin) */
+  uint64_t seed;
+  double c1;               /* langevin: exp(-friction dt) */
+  double noise2;           /* langevin: (1 - c1^2) k_B T */
+  double dt_over_tau;      /* berendsen */
+  double t0;               /* berendsen: the target temperature */
+  double half_dt;          /* the back's kick */
+} xeq_md_params;
 int xeq_md_inverse_cell(const double* cell, double* inv);
 int xeq_md_normals(int dtype, uint64_t seed, int purpose, uint64_t step, const int64_t* rng_id, int64_t n, uint32_t* words, void* normals,
                    void* stream);
-int xeq_md_front(int dtype, int ensemble, int64_t n, int64_t n_graphs, void* pos, void* vel, const void* frc, const void* inv_mass,
-                 const int64_t* batch, const void* ke, const void* tfac, const int64_t* rng_id, const int64_t* book, uint64_t seed, double dt,
-                 double c1, double noise2, double dt_over_tau, double t0, const double* cell, const int32_t* pbc, int32_t* image, void* stream);
-int xeq_md_back(int dtype, int advance, int64_t n, int64_t n_graphs, int64_t n_chunks, const void* pos, void* vel, void* frc, const void* frc_step,
-                const void* energy_step, const int32_t* n_edges_step, const void* inv_mass, const void* half_mass, const int32_t* chunk_atom0,
-                const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* ke, void* epot, int64_t* book,
-                double half_dt, const double* cell, const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start,
-                int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* stream);
+int xeq_md_front(const xeq_res_system* sys, const xeq_md_params* md, double dt, void* stream);
+int xeq_md_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
+                const xeq_res_recorder* rec, int advance, void* stream);
 
 /* Constant pressure: the Berendsen barostat next to the Berendsen thermostat (ASE's NPTBerendsen.step in the front / back split above)
  * for ONE periodic box, all three axes periodic, whose cell lives on the device.  One step is xeq_npt_front, the step's graph (whose first
  * node forms the cell tables from the step's static cell: xeq_pbc_tables_device), xeq_npt_back.  Per-atom and per-box arithmetic runs in
  * double and is rounded once where it is stored.
  *
- * box: the record, XEQ_NPT_BOX doubles on the device: the current cell [9] (rows = lattice vectors; holds `dtype` values) and its
- * inverse [9] (frac_k = sum_j x_j inv[3 j + k]), the PENDING cell and its inverse, mu, P, V.  The host fills current = pending = the
- * start cell, the inverse by xeq_md_inverse_cell, mu = 1.
- *
- * xeq_npt_back: everything xeq_md_back does for one graph; then the lane that keeps the books copies virial_step [9] (the step's
- * virial W = -dE/dstrain, `dtype`) to virial and forms, from the CURRENT cell c,
+ * xeq_npt_back: everything xeq_md_back does for one graph; then the lane that keeps the books copies virial_step to virial and forms,
+ * from the CURRENT cell c,
  *   V = |det c| (operation order of xeq_md_inverse_cell), P = (2 ke[0] + (W00 + W11) + W22) / (3 V) from the STORED ke[0],
- *   mu = 1 - kappa (p0 - P), kappa = (dt / taup) (beta / 3)   (ASE's linear form: no cube root, no clamp),
+ *   mu = 1 - kappa (p0 - P)   (ASE's linear form: no cube root, no clamp),
  *   pending cell = (dtype)(mu c) and its inverse.
  * A mu that is not finite or not positive, or a pending cell without an inverse, sets book[2] and leaves mu = 1, pending = current.
- * reps_needed [3] (device, the step graph's output; NULL: no check): book[3] = 1 when an entry exceeds reps [3] (host: the captured
- * counts); reps_seen [3] (device) keeps the largest seen.  Energies per volume are in the caller's energy / length^3; p_unit converts P
- * for the recorder alone.  Recorder: as xeq_md_back, the positions unwrapped by the current cell, and traj_cell [rows, 3, 3] (`dtype`),
- * traj_pressure [rows] (double, P p_unit).
+ * With reps_needed: book[3] = 1 when an entry exceeds reps; reps_seen keeps the largest seen.
  *
  * xeq_npt_front, dt > 0: the Berendsen lambda of xeq_md_front; x <- mu x for EVERY atom, fixed ones included (ASE's
  * set_cell(scale_atoms=True)); the half kick with the forces of the unscaled geometry and the drift for the free atoms; the wrap against
- * the PENDING cell.  Thread 0 alone commits the pending cell to the record's current cell and to step_cell [9] (`dtype`, the step's
- * static cell); no other thread reads those two in this launch.  dt = 0: the wrap against the current cell, nothing is committed.
+ * the PENDING cell.  Thread 0 alone commits the pending cell to the record's current cell and to step_cell; no other thread reads those
+ * two in this launch.  dt = 0: the wrap against the current cell, nothing is committed.
  * So wherever the host can look, positions, images and step_cell belong together and mu is a function of the current state. */
 #define XEQ_NPT_BOX 40
 enum { XEQ_NPT_CELL = 0, XEQ_NPT_INV = 9, XEQ_NPT_CELL_NEXT = 18, XEQ_NPT_INV_NEXT = 27, XEQ_NPT_MU = 36, XEQ_NPT_P = 37, XEQ_NPT_V = 38 };
-int xeq_npt_front(int dtype, int64_t n, void* pos, void* vel, const void* frc, const void* inv_mass, const int64_t* batch, const void* ke,
-                  const void* tfac, double dt, double dt_over_tau, double t0, double* box, void* step_cell, int32_t* image, void* stream);
-int xeq_npt_back(int dtype, int advance, int64_t n, int64_t n_chunks, const void* pos, void* vel, void* frc, const void* frc_step,
-                 const void* energy_step, const int32_t* n_edges_step, const void* virial_step, const int32_t* reps_needed, const int32_t* reps,
-                 const void* inv_mass, const void* half_mass, const int32_t* chunk_atom0, const int32_t* chunk_n, const int32_t* graph_chunk_ptr,
-                 double* partial, int32_t* partial_bad, void* ke, void* epot, void* virial, int32_t* reps_seen, int64_t* book, double* box,
-                 double half_dt, double kappa, double p0, double p_unit, const int32_t* image, int64_t record_every, int64_t record_start,
-                 int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* traj_cell, double* traj_pressure,
-                 void* stream);
+typedef struct xeq_npt_params {
+  double* box;          /* the record, XEQ_NPT_BOX doubles: the current cell [9] (rows = lattice vectors; holds `dtype` values) and its
+                           inverse [9] (frac_k = sum_j x_j inv[3 j + k]), the PENDING cell and its inverse, mu, P, V.  The host fills
+                           current = pending = the start cell, the inverse by xeq_md_inverse_cell, mu = 1 */
+  void* step_cell;      /* [9] `dtype`: the step's static cell */
+  void* virial;         /* [9] `dtype`: the virial of the current positions and box */
+  int32_t* reps_seen;   /* [3]: the largest reps_needed seen */
+  double kappa;         /* (dt / taup) (beta / 3) */
+  double p0;            /* the target pressure; energies per volume are in the caller's energy / length^3 */
+  double p_unit;        /* converts P for the recorder alone */
+} xeq_npt_params;
+int xeq_npt_front(const xeq_res_system* sys, const xeq_md_params* md, const xeq_npt_params* npt, double dt, void* stream);
+int xeq_npt_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
+                 const xeq_npt_params* npt, const xeq_res_recorder* rec, int advance, void* stream);
 
-/* Device-resident batched geometry optimisation (FIRE) around a whole-step graph (xequinet_amd/optimize.py, csrc/xeq_md.hip, DESIGN.md
- * section 13), f32 / f64.  One iteration is xeq_fire_front, the step's graph on the step object's static buffers, xeq_fire_back; nothing
- * reaches the host between them.  Every graph is its own FIRE system.  Per-atom and per-graph arithmetic runs in double whatever `dtype`
- * is and is rounded once where it is stored; dt, alpha [n_graphs] and coef [n_graphs, 3] = (c_v, c_f, d) are double.
- *
- * Per-graph state: status int32 (XEQ_FIRE_FRESH: no velocity yet, ASE's `v is None`; _ACTIVE; _CONVERGED), n_pos int32 (evaluations with
- * P > 0 in a row), converged_at int64 (the evaluation at which the graph converged, counted from 0; the caller starts it at -1), epot and
- * fmax of `dtype`.  fixed: uint8 [n] or NULL, nonzero = the atom never moves, keeps v = 0, its force is left out of every sum and its
- * entry in frc is 0.  batch [n]: the atom's graph.  book: int64 [4] on the device = {evaluations done, largest n_edges seen, non-finite
- * flag, graphs not converged}, kept by xeq_fire_back with plain stores of one lane; the host resets entries 1 and 2 when it has read them.
+/* Batched geometry optimisation (FIRE; xequinet_amd/optimize.py).  Every graph is its own FIRE system.  Per-atom
+ * and per-graph arithmetic runs in double whatever `dtype` is and is rounded once where it is stored.
  *
  * xeq_fire_back, behind evaluation number book[0]:
  *   First launch, one workgroup per chunk (chunk tables as for xeq_md_back): frc = frc_step (0 for a fixed atom; untouched for a converged
@@ -1099,21 +1151,27 @@ int xeq_npt_back(int dtype, int advance, int64_t n, int64_t n_chunks, const void
  *   Then one lane: book[0] += 1, book[1] = max(book[1], n_edges_step[0]), book[2] = 1 on a non-finite force or energy of a graph that
  *   is not converged, book[3] = graphs not converged.  With a single chunk the first launch's workgroup does this part itself and
  *   there is no second launch.  No atomics; a graph's sums and state have the same bits alone and anywhere in a batch.
- *   Recorder (record_every > 0): when d = book[0] - record_start (book[0] read BEFORE the increment: this evaluation's number) is a
- *   positive multiple of record_every, row d / record_every - 1 (< record_rows) of traj_pos [rows, n, 3] (unwrapped), traj_epot /
- *   traj_fmax [rows, n_graphs] and traj_step [rows] is written.
- * xeq_fire_front, per free atom of an ACTIVE graph: v = c_v v + c_f frc, x += d v, then the wrap of xeq_md_front (cell, pbc on the
- * host, NULL for open boundaries).  Atoms of fresh or converged graphs and fixed atoms are not written. */
+ * xeq_fire_front, per free atom of an ACTIVE graph: v = c_v v + c_f frc, x += d v, then the wrap of xeq_md_front.  Atoms of fresh or
+ * converged graphs and fixed atoms are not written. */
 enum { XEQ_FIRE_FRESH = 0, XEQ_FIRE_ACTIVE = 1, XEQ_FIRE_CONVERGED = 2 };
-int xeq_fire_front(int dtype, int64_t n, int64_t n_graphs, void* pos, void* vel, const void* frc, const uint8_t* fixed, const int64_t* batch,
-                   const int32_t* status, const double* coef, const double* cell, const int32_t* pbc, int32_t* image, void* stream);
-int xeq_fire_back(int dtype, int64_t n, int64_t n_graphs, int64_t n_chunks, const void* pos, const void* vel, void* frc, const void* frc_step,
-                  const void* energy_step, const int32_t* n_edges_step, const uint8_t* fixed, const int64_t* batch, const int32_t* chunk_atom0,
-                  const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* epot, void* fmax, double* dt,
-                  double* alpha, int32_t* n_pos, int32_t* status, int64_t* converged_at, double* coef, int64_t* book, double fmax_tol,
-                  double maxstep, double dtmax, int n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, const double* cell,
-                  const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start, int64_t record_rows, void* traj_pos,
-                  void* traj_epot, void* traj_fmax, int64_t* traj_step, void* stream);
+typedef struct xeq_fire_params {
+  const uint8_t* fixed;    /* [n] or NULL; nonzero = the atom never moves, keeps v = 0, its force is left out of every sum and its entry
+                              in frc is 0 */
+  void* epot;              /* [n_graphs] `dtype` */
+  void* fmax;              /* [n_graphs] `dtype` */
+  double* dt;              /* [n_graphs] */
+  double* alpha;           /* [n_graphs] */
+  int32_t* n_pos;          /* [n_graphs]: evaluations with P > 0 in a row */
+  int32_t* status;         /* [n_graphs]: XEQ_FIRE_FRESH (no velocity yet, ASE's `v is None`), _ACTIVE, _CONVERGED */
+  int64_t* converged_at;   /* [n_graphs]: the evaluation at which the graph converged, counted from 0; the caller starts it at -1 */
+  double* coef;            /* [n_graphs, 3] = (c_v, c_f, d) */
+  double fmax_tol, maxstep, dtmax;
+  int64_t n_min;
+  double f_inc, f_dec, alpha_start, f_alpha;
+} xeq_fire_params;
+int xeq_fire_front(const xeq_res_system* sys, const xeq_fire_params* fire, void* stream);
+int xeq_fire_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_fire_params* fire,
+                  const xeq_res_recorder* rec, void* stream);
 
 /* Batched harmonic analysis behind the Hessian front (xequinet_amd/vibrations.py, csrc/xeq_vib.hip).  Everything is
  * f64; only the Hessian is read as `dtype` and widened on load.  One workgroup per graph, fixed summation orders, no atomics: a graph's

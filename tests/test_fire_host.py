@@ -132,7 +132,7 @@ def test_fire_entries_exist_with_their_signatures():
 
     L = lib.load()
     assert "xeq_fire_front" in lib.EXPORTS and "xeq_fire_back" in lib.EXPORTS
-    assert len(lib._PROTOS["xeq_fire_front"]) == 14 and len(lib._PROTOS["xeq_fire_back"]) == 45
+    # (the records these take, member for member against include/xeq.h: tests/test_resident_records_host.py)
     assert L.xeq_fire_front.argtypes == lib._PROTOS["xeq_fire_front"] and L.xeq_fire_back.argtypes == lib._PROTOS["xeq_fire_back"]
     assert (lib.FIRE_FRESH, lib.FIRE_ACTIVE, lib.FIRE_CONVERGED) == (fo.FRESH, fo.ACTIVE, fo.CONVERGED)
 
@@ -145,8 +145,10 @@ def test_fire_entries_report_argument_errors_without_a_gpu():
     L = lib.load()
     N = None
 
+    ref, fill = ctypes.byref, lib.fill
+
     def front(dtype=0, n=4, g=1, cell=None, pbc=None):
-        return L.xeq_fire_front(dtype, n, g, N, N, N, N, N, N, N, cell, pbc, N, N)
+        return L.xeq_fire_front(ref(fill(lib.ResSystem(), dtype=dtype, n=n, n_graphs=g, cell=cell, pbc=pbc)), ref(lib.FireParams()), N)
 
     assert front(dtype=2) == 1 and b"dtype" in L.xeq_last_error()
     assert front(n=-1) == 1 and b"atoms" in L.xeq_last_error()
@@ -157,7 +159,9 @@ def test_fire_entries_report_argument_errors_without_a_gpu():
     assert front(n=0) == 0                                          # nothing to do: no launch
 
     def back(dtype=0, n=4, g=1, c=1, fmax=0.05, maxstep=0.2, dtmax=1.0, n_min=5, f_inc=1.1, f_dec=0.5, a0=0.1, fa=0.99, every=0):
-        return L.xeq_fire_back(dtype, n, g, c, *([N] * 22), fmax, maxstep, dtmax, n_min, f_inc, f_dec, a0, fa, None, None, N, every, 0, 0, N, N, N, N, N)
+        fire = fill(lib.FireParams(), fmax_tol=fmax, maxstep=maxstep, dtmax=dtmax, n_min=n_min, f_inc=f_inc, f_dec=f_dec, alpha_start=a0, f_alpha=fa)
+        return L.xeq_fire_back(ref(fill(lib.ResSystem(), dtype=dtype, n=n, n_graphs=g, n_chunks=c)), ref(lib.ResStep()), ref(lib.ResChunks()), ref(fire),
+                               ref(fill(lib.ResRecorder(), every=every)), N)
 
     assert back(dtype=-1) == 1 and b"dtype" in L.xeq_last_error()
     assert back(g=-1) == 1 and b"graphs" in L.xeq_last_error()

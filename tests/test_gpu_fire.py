@@ -40,10 +40,6 @@ def _t(a, dtype=None):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _np(t):
     return t.detach().double().cpu().numpy()
 
@@ -149,10 +145,13 @@ def _back_call(dtype, ptr, st, v, f_step, fixed, energy, n_edges, book, frc0=Non
          "partial": torch.zeros((max(C, 1), 4), dtype=torch.float64, device=DEV), "pbad": torch.zeros(max(C, 1), dtype=torch.int32, device=DEV),
          "book": _t(book), **_device_state(st, tdt)}
     g = {k: gb.guarded_copy(t) for k, t in g.items()}
-    lib.call("xeq_fire_back", code, n, G, C, _p(g["pos"]), _p(g["v"]), _p(g["frc"]), _p(g["fs"]), _p(g["en"]), _p(g["ne"]), _p(g["fixed"]), _p(g["batch"]),
-             _p(g["a0"]), _p(g["cn"]), _p(g["gp"]), _p(g["partial"]), _p(g["pbad"]), _p(g["epot"]), _p(g["fmax"]), _p(g["dt"]), _p(g["alpha"]),
-             _p(g["n_pos"]), _p(g["status"]), _p(g["converged_at"]), _p(g["coef"]), _p(g["book"]), FMAX, PAR["maxstep"], PAR["dtmax"], PAR["n_min"],
-             PAR["f_inc"], PAR["f_dec"], PAR["alpha_start"], PAR["f_alpha"], None, None, None, 0, 0, 0, None, None, None, None, lib.stream())
+    system = lib.fill(lib.ResSystem(), dtype=code, n=n, n_graphs=G, n_chunks=C, pos=g["pos"], vel=g["v"], frc=g["frc"], batch=g["batch"], book=g["book"])
+    step = lib.fill(lib.ResStep(), frc_step=g["fs"], energy_step=g["en"], n_edges_step=g["ne"])
+    chunks = lib.fill(lib.ResChunks(), chunk_atom0=g["a0"], chunk_n=g["cn"], graph_chunk_ptr=g["gp"], partial=g["partial"], partial_bad=g["pbad"])
+    par = lib.fill(lib.FireParams(), fixed=g["fixed"], epot=g["epot"], fmax=g["fmax"], dt=g["dt"], alpha=g["alpha"], n_pos=g["n_pos"], status=g["status"],
+                   converged_at=g["converged_at"], coef=g["coef"], fmax_tol=FMAX, maxstep=PAR["maxstep"], dtmax=PAR["dtmax"], n_min=PAR["n_min"],
+                   f_inc=PAR["f_inc"], f_dec=PAR["f_dec"], alpha_start=PAR["alpha_start"], f_alpha=PAR["f_alpha"])
+    lib.call("xeq_fire_back", ctypes.byref(system), ctypes.byref(step), ctypes.byref(chunks), ctypes.byref(par), None, lib.stream())
     torch.cuda.synchronize()
     gb.check(*g.values())
     return {k: t.cpu().numpy() for k, t in g.items()}
@@ -224,8 +223,10 @@ def test_front_kernel_alone(n, dtype):
                                                         image=np.zeros((N, 3), np.int32)).items()}
         cell_c = (ctypes.c_double * 9)(*cell.reshape(-1)) if periodic else None
         pbc_c = (ctypes.c_int32 * 3)(*[int(b) for b in periodic]) if periodic else None
-        lib.call("xeq_fire_front", code, N, G, _p(g["x"]), _p(g["v"]), _p(g["f"]), _p(g["fixed"]), _p(g["batch"]), _p(g["status"]), _p(g["coef"]),
-                 cell_c, pbc_c, _p(g["image"]), lib.stream())
+        system = lib.fill(lib.ResSystem(), dtype=code, n=N, n_graphs=G, pos=g["x"], vel=g["v"], frc=g["f"], image=g["image"], batch=g["batch"], cell=cell_c,
+                          pbc=pbc_c)
+        lib.call("xeq_fire_front", ctypes.byref(system), ctypes.byref(lib.fill(lib.FireParams(), fixed=g["fixed"], status=g["status"], coef=g["coef"])),
+                 lib.stream())
         torch.cuda.synchronize()
         gb.check(*g.values())
         xg, vg, ig = g["x"].cpu().numpy(), g["v"].cpu().numpy(), g["image"].cpu().numpy()

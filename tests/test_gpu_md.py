@@ -175,10 +175,6 @@ def _call(name, *args):
     lib.call(name, *args)
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 @pytest.mark.parametrize("n", [1, 63, 65, 1537])
 def test_front_kernel_alone(n, dtype):
@@ -216,8 +212,11 @@ def test_front_kernel_alone(n, dtype):
                                                                 book=book_h, image=np.zeros((n, 3), np.int32)).items()}
                 cell_c = (ctypes.c_double * 9)(*cell.reshape(-1)) if periodic else None
                 pbc_c = (ctypes.c_int32 * 3)(*[int(b) for b in periodic]) if periodic else None
-                _call("xeq_md_front", code, ens, n, G, _p(g["x"]), _p(g["v"]), _p(g["f"]), _p(g["im"]), _p(g["batch"]), _p(g["ke"]), _p(g["tfac"]),
-                      _p(g["ids"]), _p(g["book"]), 5, DT_FS, c1, noise2, DT_FS / TAUT, T_K, cell_c, pbc_c, _p(g["image"]), lib.stream())
+                system = lib.fill(lib.ResSystem(), dtype=code, n=n, n_graphs=G, pos=g["x"], vel=g["v"], frc=g["f"], image=g["image"], batch=g["batch"],
+                                  book=g["book"], cell=cell_c, pbc=pbc_c)
+                par = lib.fill(lib.MdParams(), ensemble=ens, inv_mass=g["im"], ke=g["ke"], tfac=g["tfac"], rng_id=g["ids"], seed=5, c1=c1, noise2=noise2,
+                               dt_over_tau=DT_FS / TAUT, t0=T_K)
+                _call("xeq_md_front", ctypes.byref(system), ctypes.byref(par), DT_FS, lib.stream())
                 torch.cuda.synchronize()
                 gb.check(*g.values())
                 tag = (lname, ens, periodic)
@@ -248,9 +247,11 @@ def _back_call(dtype, ptr, v, f_step, inv_mass, half_mass, energy, n_edges, book
          "hm": gb.guarded_copy(_t(half_mass)), "a0": gb.guarded_copy(_t(a0)), "cn": gb.guarded_copy(_t(cn)), "gp": gb.guarded_copy(_t(gp)),
          "partial": gb.guarded((max(C, 1),), torch.float64, DEV), "pbad": gb.guarded((max(C, 1),), torch.int32, DEV), "ke": gb.guarded((G,), tdt, DEV),
          "epot": gb.guarded((G,), tdt, DEV), "book": gb.guarded_copy(_t(book))}
-    _call("xeq_md_back", code, advance, n, G, C, _p(g["pos"]), _p(g["v"]), _p(g["frc"]), _p(g["fs"]), _p(g["en"]), _p(g["ne"]), _p(g["im"]), _p(g["hm"]),
-          _p(g["a0"]), _p(g["cn"]), _p(g["gp"]), _p(g["partial"]), _p(g["pbad"]), _p(g["ke"]), _p(g["epot"]), _p(g["book"]), half_dt, None, None, None,
-          0, 0, 0, None, None, None, None, lib.stream())
+    system = lib.fill(lib.ResSystem(), dtype=code, n=n, n_graphs=G, n_chunks=C, pos=g["pos"], vel=g["v"], frc=g["frc"], book=g["book"])
+    step = lib.fill(lib.ResStep(), frc_step=g["fs"], energy_step=g["en"], n_edges_step=g["ne"])
+    chunks = lib.fill(lib.ResChunks(), chunk_atom0=g["a0"], chunk_n=g["cn"], graph_chunk_ptr=g["gp"], partial=g["partial"], partial_bad=g["pbad"])
+    par = lib.fill(lib.MdParams(), inv_mass=g["im"], half_mass=g["hm"], ke=g["ke"], epot=g["epot"], half_dt=half_dt)
+    _call("xeq_md_back", ctypes.byref(system), ctypes.byref(step), ctypes.byref(chunks), ctypes.byref(par), None, advance, lib.stream())
     torch.cuda.synchronize()
     gb.check(*g.values())
     return g

@@ -269,8 +269,10 @@ def test_npt_front_kernel_alone(n, dtype):
                 vr = np.where(free[:, None], v, 0.0).astype(dtype)
             g = {k: gb.guarded_copy(_t(a)) for k, a in dict(x=x, v=v, f=f, im=inv_mass, batch=np.zeros(n, np.int64), ke=ke, tfac=tfac, rec=rec,
                                                             cell=np.full(9, -7.0, dtype), image=np.zeros((n, 3), np.int32)).items()}
-            lib.call("xeq_npt_front", code, n, _p(g["x"]), _p(g["v"]), _p(g["f"]), _p(g["im"]), _p(g["batch"]), _p(g["ke"]), _p(g["tfac"]), dt, dt / TAUT, T_K,
-                     _p(g["rec"]), _p(g["cell"]), _p(g["image"]), lib.stream())
+            system = lib.fill(lib.ResSystem(), dtype=code, n=n, n_graphs=1, pos=g["x"], vel=g["v"], frc=g["f"], image=g["image"], batch=g["batch"])
+            par = lib.fill(lib.MdParams(), inv_mass=g["im"], ke=g["ke"], tfac=g["tfac"], dt_over_tau=dt / TAUT, t0=T_K)
+            lib.call("xeq_npt_front", ctypes.byref(system), ctypes.byref(par), ctypes.byref(lib.fill(lib.NptParams(), box=g["rec"], step_cell=g["cell"])), dt,
+                     lib.stream())
             torch.cuda.synchronize()
             gb.check(*g.values())
             tag = (mu, dt)
@@ -319,10 +321,12 @@ def _npt_back_call(dtype, v, f_step, inv_mass, half_mass, virial, rec, *, kappa,
          "a0": gb.guarded_copy(_t(a0)), "cn": gb.guarded_copy(_t(cn)), "gp": gb.guarded_copy(_t(gp)), "partial": gb.guarded((C,), torch.float64, DEV),
          "pbad": gb.guarded((C,), torch.int32, DEV), "ke": gb.guarded((1,), tdt, DEV), "epot": gb.guarded((1,), tdt, DEV), "w": gb.guarded((9,), tdt, DEV),
          "seen": gb.guarded_copy(_t(np.zeros(3, np.int32))), "book": gb.guarded_copy(_t(book)), "rec": gb.guarded_copy(_t(rec))}
-    lib.call("xeq_npt_back", code, advance, n, C, _p(g["pos"]), _p(g["v"]), _p(g["frc"]), _p(g["fs"]), _p(g["en"]), _p(g["ne"]), _p(g["ws"]), _p(g["needed"]),
-             _i3(reps), _p(g["im"]), _p(g["hm"]), _p(g["a0"]), _p(g["cn"]), _p(g["gp"]), _p(g["partial"]), _p(g["pbad"]), _p(g["ke"]), _p(g["epot"]),
-             _p(g["w"]), _p(g["seen"]), _p(g["book"]), _p(g["rec"]), 0.5 * DT_FS, kappa, p0, 1.0 / GPA, None, 0, 0, 0, None, None, None, None, None, None,
-             lib.stream())
+    system = lib.fill(lib.ResSystem(), dtype=code, n=n, n_graphs=1, n_chunks=C, pos=g["pos"], vel=g["v"], frc=g["frc"], book=g["book"])
+    step = lib.fill(lib.ResStep(), frc_step=g["fs"], energy_step=g["en"], n_edges_step=g["ne"], virial_step=g["ws"], reps_needed=g["needed"], reps=tuple(reps))
+    chunks = lib.fill(lib.ResChunks(), chunk_atom0=g["a0"], chunk_n=g["cn"], graph_chunk_ptr=g["gp"], partial=g["partial"], partial_bad=g["pbad"])
+    par = lib.fill(lib.MdParams(), inv_mass=g["im"], half_mass=g["hm"], ke=g["ke"], epot=g["epot"], half_dt=0.5 * DT_FS)
+    box = lib.fill(lib.NptParams(), box=g["rec"], virial=g["w"], reps_seen=g["seen"], kappa=kappa, p0=p0, p_unit=1.0 / GPA)
+    lib.call("xeq_npt_back", ctypes.byref(system), ctypes.byref(step), ctypes.byref(chunks), ctypes.byref(par), ctypes.byref(box), None, advance, lib.stream())
     torch.cuda.synchronize()
     gb.check(*g.values())
     return g

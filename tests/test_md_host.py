@@ -130,8 +130,11 @@ def test_md_entries_report_argument_errors_without_a_gpu():
     assert L.xeq_md_normals(0, 0, 0, 0, N, -1, N, N, N) == 1
     assert L.xeq_md_normals(0, 0, 0, 0, N, 0, N, N, N) == 0                        # nothing to do: no launch
 
+    ref, fill = ctypes.byref, lib.fill
+
     def front(dtype=0, ens=0, n=4, g=1, dt=0.5, c1=1.0, noise2=0.0, r=0.0, t0=0.0, cell=None, pbc=None):
-        return L.xeq_md_front(dtype, ens, n, g, N, N, N, N, N, N, N, N, N, 0, dt, c1, noise2, r, t0, cell, pbc, N, N)
+        system = fill(lib.ResSystem(), dtype=dtype, n=n, n_graphs=g, cell=cell, pbc=pbc)          # (every buffer NULL)
+        return L.xeq_md_front(ref(system), ref(fill(lib.MdParams(), ensemble=ens, c1=c1, noise2=noise2, dt_over_tau=r, t0=t0)), dt, N)
 
     assert front(dtype=3) == 1 and b"dtype" in L.xeq_last_error()
     assert front(ens=3) == 1 and b"ensemble" in L.xeq_last_error()
@@ -146,7 +149,9 @@ def test_md_entries_report_argument_errors_without_a_gpu():
     assert front(n=0) == 0
 
     def back(dtype=0, n=4, g=1, c=1, half_dt=0.25, every=0, start=0, rows=0):
-        return L.xeq_md_back(dtype, 1, n, g, c, N, N, N, N, N, N, N, N, N, N, N, N, N, N, N, N, half_dt, None, None, N, every, start, rows, N, N, N, N, N)
+        system = fill(lib.ResSystem(), dtype=dtype, n=n, n_graphs=g, n_chunks=c)
+        return L.xeq_md_back(ref(system), ref(lib.ResStep()), ref(lib.ResChunks()), ref(fill(lib.MdParams(), half_dt=half_dt)),
+                             ref(fill(lib.ResRecorder(), every=every, start=start, rows=rows)), 1, N)
 
     assert back(dtype=-1) == 1 and b"dtype" in L.xeq_last_error()
     assert back(g=-1) == 1 and b"graphs" in L.xeq_last_error()
@@ -155,6 +160,7 @@ def test_md_entries_report_argument_errors_without_a_gpu():
     assert back(half_dt=-1.0) == 1 and b"half time step" in L.xeq_last_error()
     assert back(every=-2) == 1 and b"recorder" in L.xeq_last_error()
     assert back() == 1 and b"null" in L.xeq_last_error()
+    assert L.xeq_md_back(ref(lib.ResSystem()), N, N, N, N, 1, N) == 1 and b"null argument record" in L.xeq_last_error()
 
 
 def _tiny(n=3):

@@ -97,8 +97,11 @@ def test_npt_entries_report_argument_errors_without_a_gpu():
     assert tables(reps=(65, 0, 0), count=6 * 131 + 12) == 1 and b"images per axis" in L.xeq_last_error()
     assert tables(count=6 * 27) == 1 and b"need 174" in L.xeq_last_error()
 
+    ref, fill = ctypes.byref, lib.fill
+
     def front(dtype=0, n=4, dt=0.5, r=0.1, t0=300.0, box=1, cell=1):
-        return L.xeq_npt_front(dtype, n, N, N, N, N, N, N, N, dt, r, t0, box, cell, N, N)
+        return L.xeq_npt_front(ref(fill(lib.ResSystem(), dtype=dtype, n=n)), ref(fill(lib.MdParams(), dt_over_tau=r, t0=t0)),
+                               ref(fill(lib.NptParams(), box=box, step_cell=cell)), dt, N)
 
     assert front(dtype=3) == 1 and b"dtype" in L.xeq_last_error()
     assert front(n=-1) == 1 and b"atoms" in L.xeq_last_error()
@@ -109,9 +112,11 @@ def test_npt_entries_report_argument_errors_without_a_gpu():
     assert front() == 1 and b"null state buffer" in L.xeq_last_error()
     assert front(n=0) == 0                                                          # nothing to do: no launch
 
-    def back(dtype=0, n=4, c=1, half_dt=0.25, kappa=0.0, p0=0.0, unit=160.2, every=0, box=1, needed=None, reps=None):
-        return L.xeq_npt_back(dtype, 1, n, c, N, N, N, N, N, 1, 1, needed, reps, N, N, N, N, N, N, N, N, N, 1, N, 1, box, half_dt, kappa, p0, unit, N,
-                              every, 0, 0, N, N, N, N, N, N, N)
+    def back(dtype=0, n=4, c=1, half_dt=0.25, kappa=0.0, p0=0.0, unit=160.2, every=0, box=1, needed=None):
+        system = fill(lib.ResSystem(), dtype=dtype, n=n, n_chunks=c, book=1)
+        step = fill(lib.ResStep(), n_edges_step=1, virial_step=1, reps_needed=needed)
+        return L.xeq_npt_back(ref(system), ref(step), ref(lib.ResChunks()), ref(fill(lib.MdParams(), half_dt=half_dt)),
+                              ref(fill(lib.NptParams(), box=box, virial=1, kappa=kappa, p0=p0, p_unit=unit)), ref(fill(lib.ResRecorder(), every=every)), 1, N)
 
     assert back(dtype=-1) == 1 and b"dtype" in L.xeq_last_error()
     assert back(n=0) == 1 and b"atoms" in L.xeq_last_error()

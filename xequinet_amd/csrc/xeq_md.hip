@@ -823,6 +823,76 @@ static bool md_box(const double* cell, const int32_t* pbc, MdBox* b) {
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------------------- argument records
+// The checks the six front / back entries share (include/xeq.h: the records), each under the entry's own name `who`.
+#define RES_TRY(check)               \
+  do {                               \
+    if (int e_ = (check)) return e_; \
+  } while (0)
+
+static int res_dtype(const char* who, const xeq_res_system* s, bool records) {
+  XEQ_CHECK_ARG(s && records, "%s: null argument record", who);
+  XEQ_CHECK_ARG(s->dtype == XEQ_F32 || s->dtype == XEQ_F64, "%s: dtype %lld (0 f32, 1 f64)", who, (long long)s->dtype);
+  return XEQ_OK;
+}
+
+static const int64_t RES_MAX_ATOMS = ((int64_t)1 << 31) / 3;
+
+// A front's sizes.
+static int res_atoms_graphs(const char* who, const xeq_res_system* s) {
+  XEQ_CHECK_ARG(s->n >= 0 && s->n < RES_MAX_ATOMS && s->n_graphs >= 0, "%s: %lld atoms, %lld graphs", who, (long long)s->n, (long long)s->n_graphs);
+  return XEQ_OK;
+}
+
+static int res_chunks_hold(const char* who, const xeq_res_system* s) {
+  XEQ_CHECK_ARG(s->n_chunks <= s->n && s->n_chunks * XEQ_MD_CHUNK >= s->n, "%s: %lld chunks of at most %d atoms cannot hold %lld atoms", who,
+                (long long)s->n_chunks, XEQ_MD_CHUNK, (long long)s->n);
+  return XEQ_OK;
+}
+
+// A batch's back: its sizes (fewer than `chunk_cap` chunks), then the chunk count against the atom count.
+static int res_back_sizes(const char* who, const xeq_res_system* s, int64_t chunk_cap) {
+  XEQ_CHECK_ARG(s->n >= 0 && s->n < RES_MAX_ATOMS && s->n_graphs >= 0 && s->n_chunks >= 0 && s->n_chunks < chunk_cap,
+                "%s: %lld atoms, %lld graphs, %lld chunks", who, (long long)s->n, (long long)s->n_graphs, (long long)s->n_chunks);
+  return res_chunks_hold(who, s);
+}
+
+static int res_recorder(const char* who, const xeq_res_recorder* r) {
+  XEQ_CHECK_ARG(r->every >= 0 && r->rows >= 0 && r->start >= 0, "%s: recorder (%lld, %lld, %lld)", who, (long long)r->every, (long long)r->start,
+                (long long)r->rows);
+  return XEQ_OK;
+}
+
+static int res_box(const char* who, const xeq_res_system* s, MdBox* box) {
+  XEQ_CHECK_ARG(md_box(s->cell, s->pbc, box), "%s: the cell is singular or not finite", who);
+  return XEQ_OK;
+}
+
+// The buffers every back reads or writes per atom and per chunk.
+static bool res_back_buffers(const xeq_res_system* s, const xeq_res_step* st, const xeq_res_chunks* c) {
+  return s->pos && s->vel && s->frc && st->frc_step && c->chunk_atom0 && c->chunk_n && c->partial && c->partial_bad;
+}
+
+// The rows of a batch's recorder that is on (xeq_md_back, xeq_fire_back).
+static int res_trajectory(const char* who, const xeq_res_system* s, const xeq_res_recorder* r, const MdBox& box) {
+  XEQ_CHECK_ARG((s->n == 0 || r->traj_pos) && (s->n_graphs == 0 || (r->traj_epot && r->traj_second)) && r->traj_step, "%s: null trajectory buffer", who);
+  XEQ_CHECK_ARG(s->n == 0 || !box.any || s->image, "%s: a periodic system's recorder needs the image counts", who);
+  return XEQ_OK;
+}
+
+static const xeq_res_recorder RES_NO_RECORDER = {};
+
+// The kernel arguments of xeq_md_back and xeq_npt_back from the records; `on`: the recorder records in this call.
+template <typename T>
+static MdBackArgs<T> md_back_args(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
+                                  const xeq_res_recorder* rec, int64_t n_graphs, int advance, const MdBox& box, bool on) {
+  return MdBackArgs<T>{sys->n, n_graphs, sys->n_chunks, advance ? 1 : 0, (const T*)sys->pos, (T*)sys->vel, (T*)sys->frc, (const T*)step->frc_step,
+                       (const T*)step->energy_step, step->n_edges_step, (const T*)md->inv_mass, (const T*)md->half_mass, chunks->chunk_atom0,
+                       chunks->chunk_n, chunks->graph_chunk_ptr, chunks->partial, chunks->partial_bad, (T*)md->ke, (T*)md->epot, sys->book, md->half_dt,
+                       sys->image, box, on ? rec->every : 0, rec->start, rec->rows, (T*)rec->traj_pos, (T*)rec->traj_epot, (T*)rec->traj_second,
+                       rec->traj_step};
+}
+
 }  // namespace xeq
 
 using namespace xeq;
@@ -855,62 +925,69 @@ int xeq_md_normals(int dtype, uint64_t seed, int purpose, uint64_t step, const i
   return XEQ_OK;
 }
 
-int xeq_md_front(int dtype, int ensemble, int64_t n, int64_t n_graphs, void* pos, void* vel, const void* frc, const void* inv_mass,
-                 const int64_t* batch, const void* ke, const void* tfac, const int64_t* rng_id, const int64_t* book, uint64_t seed, double dt,
-                 double c1, double noise2, double dt_over_tau, double t0, const double* cell, const int32_t* pbc, int32_t* image, void* stream) {
-  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_md_front: dtype %d (0 f32, 1 f64)", dtype);
-  XEQ_CHECK_ARG(ensemble == XEQ_MD_NVE || ensemble == XEQ_MD_LANGEVIN || ensemble == XEQ_MD_BERENDSEN,
-                "xeq_md_front: ensemble %d (0 nve, 1 langevin, 2 berendsen)", ensemble);
-  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3 && n_graphs >= 0, "xeq_md_front: %lld atoms, %lld graphs", (long long)n, (long long)n_graphs);
+int64_t xeq_record_bytes(int which) {
+  switch (which) {
+    case XEQ_REC_SYSTEM: return sizeof(xeq_res_system);
+    case XEQ_REC_STEP: return sizeof(xeq_res_step);
+    case XEQ_REC_CHUNKS: return sizeof(xeq_res_chunks);
+    case XEQ_REC_RECORDER: return sizeof(xeq_res_recorder);
+    case XEQ_REC_MD: return sizeof(xeq_md_params);
+    case XEQ_REC_NPT: return sizeof(xeq_npt_params);
+    case XEQ_REC_FIRE: return sizeof(xeq_fire_params);
+  }
+  return -1;
+}
+
+int xeq_md_front(const xeq_res_system* sys, const xeq_md_params* md, double dt, void* stream) {
+  const char* who = "xeq_md_front";
+  RES_TRY(res_dtype(who, sys, md));
+  XEQ_CHECK_ARG(md->ensemble == XEQ_MD_NVE || md->ensemble == XEQ_MD_LANGEVIN || md->ensemble == XEQ_MD_BERENDSEN,
+                "xeq_md_front: ensemble %lld (0 nve, 1 langevin, 2 berendsen)", (long long)md->ensemble);
+  int ensemble = (int)md->ensemble;
+  const int64_t n = sys->n, n_graphs = sys->n_graphs;
+  RES_TRY(res_atoms_graphs(who, sys));
   XEQ_CHECK_ARG(md_finite(dt) && dt >= 0.0, "xeq_md_front: time step %g", dt);
-  XEQ_CHECK_ARG(ensemble != XEQ_MD_LANGEVIN || (c1 >= 0.0 && c1 <= 1.0 && md_finite(noise2) && noise2 >= 0.0),
-                "xeq_md_front: langevin needs 0 <= c1 <= 1 and a finite noise2 >= 0 (got %g, %g)", c1, noise2);
-  XEQ_CHECK_ARG(ensemble != XEQ_MD_BERENDSEN || (md_finite(dt_over_tau) && dt_over_tau >= 0.0 && md_finite(t0) && t0 >= 0.0 && n_graphs >= 1),
-                "xeq_md_front: berendsen needs dt / tau >= 0, a target temperature >= 0 and a graph (got %g, %g, %lld)", dt_over_tau, t0,
+  XEQ_CHECK_ARG(ensemble != XEQ_MD_LANGEVIN || (md->c1 >= 0.0 && md->c1 <= 1.0 && md_finite(md->noise2) && md->noise2 >= 0.0),
+                "xeq_md_front: langevin needs 0 <= c1 <= 1 and a finite noise2 >= 0 (got %g, %g)", md->c1, md->noise2);
+  XEQ_CHECK_ARG(ensemble != XEQ_MD_BERENDSEN ||
+                    (md_finite(md->dt_over_tau) && md->dt_over_tau >= 0.0 && md_finite(md->t0) && md->t0 >= 0.0 && n_graphs >= 1),
+                "xeq_md_front: berendsen needs dt / tau >= 0, a target temperature >= 0 and a graph (got %g, %g, %lld)", md->dt_over_tau, md->t0,
                 (long long)n_graphs);
   MdBox box;
-  XEQ_CHECK_ARG(md_box(cell, pbc, &box), "xeq_md_front: the cell is singular or not finite");
-  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && inv_mass), "xeq_md_front: null state buffer");
-  XEQ_CHECK_ARG(n == 0 || !box.any || image, "xeq_md_front: a periodic system needs the image counts");
-  XEQ_CHECK_ARG(n == 0 || ensemble != XEQ_MD_LANGEVIN || (rng_id && book), "xeq_md_front: langevin needs rng_id and the step counter");
-  XEQ_CHECK_ARG(n == 0 || ensemble != XEQ_MD_BERENDSEN || (batch && ke && tfac), "xeq_md_front: berendsen needs batch, ke and tfac");
+  RES_TRY(res_box(who, sys, &box));
+  XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->vel && sys->frc && md->inv_mass), "xeq_md_front: null state buffer");
+  XEQ_CHECK_ARG(n == 0 || !box.any || sys->image, "xeq_md_front: a periodic system needs the image counts");
+  XEQ_CHECK_ARG(n == 0 || ensemble != XEQ_MD_LANGEVIN || (md->rng_id && sys->book), "xeq_md_front: langevin needs rng_id and the step counter");
+  XEQ_CHECK_ARG(n == 0 || ensemble != XEQ_MD_BERENDSEN || (sys->batch && md->ke && md->tfac), "xeq_md_front: berendsen needs batch, ke and tfac");
   if (n == 0) return XEQ_OK;
   if (dt == 0.0) ensemble = XEQ_MD_NVE;   // no time passes: no thermostat acts, the wrap alone is left
-  XEQ_DISPATCH_FLOAT(dtype, {
-    MdFrontArgs<T> a{n, n_graphs, ensemble, (T*)pos, (T*)vel, (const T*)frc, (const T*)inv_mass, batch, (const T*)ke, (const T*)tfac, rng_id, book, seed,
-                     dt, c1, noise2, dt_over_tau, t0, image, box};
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
+    MdFrontArgs<T> a{n, n_graphs, ensemble, (T*)sys->pos, (T*)sys->vel, (const T*)sys->frc, (const T*)md->inv_mass, sys->batch, (const T*)md->ke,
+                     (const T*)md->tfac, md->rng_id, sys->book, md->seed, dt, md->c1, md->noise2, md->dt_over_tau, md->t0, sys->image, box};
     hipLaunchKernelGGL(k_md_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   });
   XEQ_CHECK_LAUNCH("xeq_md_front");
   return XEQ_OK;
 }
 
-int xeq_md_back(int dtype, int advance, int64_t n, int64_t n_graphs, int64_t n_chunks, const void* pos, void* vel, void* frc, const void* frc_step,
-                const void* energy_step, const int32_t* n_edges_step, const void* inv_mass, const void* half_mass, const int32_t* chunk_atom0,
-                const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* ke, void* epot, int64_t* book,
-                double half_dt, const double* cell, const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start,
-                int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* stream) {
-  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_md_back: dtype %d (0 f32, 1 f64)", dtype);
-  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3 && n_graphs >= 0 && n_chunks >= 0 && n_chunks < ((int64_t)1 << 31),
-                "xeq_md_back: %lld atoms, %lld graphs, %lld chunks", (long long)n, (long long)n_graphs, (long long)n_chunks);
-  XEQ_CHECK_ARG(n_chunks <= n && n_chunks * XEQ_MD_CHUNK >= n, "xeq_md_back: %lld chunks of at most %d atoms cannot hold %lld atoms", (long long)n_chunks,
-                XEQ_MD_CHUNK, (long long)n);
-  XEQ_CHECK_ARG(md_finite(half_dt) && half_dt >= 0.0, "xeq_md_back: half time step %g", half_dt);
-  XEQ_CHECK_ARG(record_every >= 0 && record_rows >= 0 && record_start >= 0, "xeq_md_back: recorder (%lld, %lld, %lld)", (long long)record_every,
-                (long long)record_start, (long long)record_rows);
+int xeq_md_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
+                const xeq_res_recorder* rec, int advance, void* stream) {
+  const char* who = "xeq_md_back";
+  RES_TRY(res_dtype(who, sys, step && chunks && md));
+  if (!rec) rec = &RES_NO_RECORDER;
+  const int64_t n = sys->n, n_graphs = sys->n_graphs, n_chunks = sys->n_chunks;
+  RES_TRY(res_back_sizes(who, sys, (int64_t)1 << 31));
+  XEQ_CHECK_ARG(md_finite(md->half_dt) && md->half_dt >= 0.0, "xeq_md_back: half time step %g", md->half_dt);
+  RES_TRY(res_recorder(who, rec));
   MdBox box;
-  XEQ_CHECK_ARG(md_box(cell, pbc, &box), "xeq_md_back: the cell is singular or not finite");
-  XEQ_CHECK_ARG(book && n_edges_step, "xeq_md_back: null step counter or edge count");
-  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && frc_step && inv_mass && half_mass && chunk_atom0 && chunk_n && partial && partial_bad),
-                "xeq_md_back: null per-atom or per-chunk buffer");
-  XEQ_CHECK_ARG(n_graphs == 0 || (energy_step && graph_chunk_ptr && ke && epot), "xeq_md_back: null per-graph buffer");
-  const bool rec = advance && record_every > 0 && record_rows > 0;
-  XEQ_CHECK_ARG(!rec || ((n == 0 || traj_pos) && (n_graphs == 0 || (traj_epot && traj_ekin)) && traj_step), "xeq_md_back: null trajectory buffer");
-  XEQ_CHECK_ARG(!rec || n == 0 || !box.any || image, "xeq_md_back: a periodic system's recorder needs the image counts");
-  XEQ_DISPATCH_FLOAT(dtype, {
-    MdBackArgs<T> a{n, n_graphs, n_chunks, advance ? 1 : 0, (const T*)pos, (T*)vel, (T*)frc, (const T*)frc_step, (const T*)energy_step, n_edges_step,
-                    (const T*)inv_mass, (const T*)half_mass, chunk_atom0, chunk_n, graph_chunk_ptr, partial, partial_bad, (T*)ke, (T*)epot, book, half_dt,
-                    image, box, rec ? record_every : 0, record_start, record_rows, (T*)traj_pos, (T*)traj_epot, (T*)traj_ekin, traj_step};
+  RES_TRY(res_box(who, sys, &box));
+  XEQ_CHECK_ARG(sys->book && step->n_edges_step, "xeq_md_back: null step counter or edge count");
+  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks) && md->inv_mass && md->half_mass), "xeq_md_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(n_graphs == 0 || (step->energy_step && chunks->graph_chunk_ptr && md->ke && md->epot), "xeq_md_back: null per-graph buffer");
+  const bool on = advance && rec->every > 0 && rec->rows > 0;
+  if (on) RES_TRY(res_trajectory(who, sys, rec, box));
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
+    const MdBackArgs<T> a = md_back_args<T>(sys, step, chunks, md, rec, n_graphs, advance, box, on);
     if (n_chunks > 0) {
       hipLaunchKernelGGL(k_md_back<T>, dim3((unsigned)n_chunks), dim3(MD_CHUNK), 0, (hipStream_t)stream, a);
       XEQ_CHECK_LAUNCH("xeq_md_back");
@@ -943,58 +1020,55 @@ int xeq_pbc_tables_device(int dtype, const void* cell, const int32_t reps[3], co
   return XEQ_OK;
 }
 
-int xeq_npt_front(int dtype, int64_t n, void* pos, void* vel, const void* frc, const void* inv_mass, const int64_t* batch, const void* ke,
-                  const void* tfac, double dt, double dt_over_tau, double t0, double* box, void* step_cell, int32_t* image, void* stream) {
-  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_npt_front: dtype %d (0 f32, 1 f64)", dtype);
-  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3, "xeq_npt_front: %lld atoms", (long long)n);
+int xeq_npt_front(const xeq_res_system* sys, const xeq_md_params* md, const xeq_npt_params* npt, double dt, void* stream) {
+  const char* who = "xeq_npt_front";
+  RES_TRY(res_dtype(who, sys, md && npt));
+  const int64_t n = sys->n;
+  XEQ_CHECK_ARG(n >= 0 && n < RES_MAX_ATOMS, "xeq_npt_front: %lld atoms", (long long)n);
   XEQ_CHECK_ARG(md_finite(dt) && dt >= 0.0, "xeq_npt_front: time step %g", dt);
-  XEQ_CHECK_ARG(md_finite(dt_over_tau) && dt_over_tau >= 0.0 && md_finite(t0) && t0 >= 0.0,
-                "xeq_npt_front: berendsen needs dt / tau >= 0 and a target temperature >= 0 (got %g, %g)", dt_over_tau, t0);
-  XEQ_CHECK_ARG(box && step_cell, "xeq_npt_front: null box record or cell");
-  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && inv_mass && image), "xeq_npt_front: null state buffer");
-  XEQ_CHECK_ARG(n == 0 || (batch && ke && tfac), "xeq_npt_front: berendsen needs batch, ke and tfac");
+  XEQ_CHECK_ARG(md_finite(md->dt_over_tau) && md->dt_over_tau >= 0.0 && md_finite(md->t0) && md->t0 >= 0.0,
+                "xeq_npt_front: berendsen needs dt / tau >= 0 and a target temperature >= 0 (got %g, %g)", md->dt_over_tau, md->t0);
+  XEQ_CHECK_ARG(npt->box && npt->step_cell, "xeq_npt_front: null box record or cell");
+  XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->vel && sys->frc && md->inv_mass && sys->image), "xeq_npt_front: null state buffer");
+  XEQ_CHECK_ARG(n == 0 || (sys->batch && md->ke && md->tfac), "xeq_npt_front: berendsen needs batch, ke and tfac");
   if (n == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    MdFrontArgs<T> a{n, 1, dt == 0.0 ? XEQ_MD_NVE : XEQ_MD_BERENDSEN, (T*)pos, (T*)vel, (const T*)frc, (const T*)inv_mass, batch, (const T*)ke,
-                     (const T*)tfac, nullptr, nullptr, 0, dt, 1.0, 0.0, dt_over_tau, t0, image, MdBox{}};
-    hipLaunchKernelGGL(k_npt_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, box, (T*)step_cell);
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
+    MdFrontArgs<T> a{n, 1, dt == 0.0 ? XEQ_MD_NVE : XEQ_MD_BERENDSEN, (T*)sys->pos, (T*)sys->vel, (const T*)sys->frc, (const T*)md->inv_mass, sys->batch,
+                     (const T*)md->ke, (const T*)md->tfac, nullptr, nullptr, 0, dt, 1.0, 0.0, md->dt_over_tau, md->t0, sys->image, MdBox{}};
+    hipLaunchKernelGGL(k_npt_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, npt->box, (T*)npt->step_cell);
   });
   XEQ_CHECK_LAUNCH("xeq_npt_front");
   return XEQ_OK;
 }
 
-int xeq_npt_back(int dtype, int advance, int64_t n, int64_t n_chunks, const void* pos, void* vel, void* frc, const void* frc_step,
-                 const void* energy_step, const int32_t* n_edges_step, const void* virial_step, const int32_t* reps_needed, const int32_t* reps,
-                 const void* inv_mass, const void* half_mass, const int32_t* chunk_atom0, const int32_t* chunk_n, const int32_t* graph_chunk_ptr,
-                 double* partial, int32_t* partial_bad, void* ke, void* epot, void* virial, int32_t* reps_seen, int64_t* book, double* box,
-                 double half_dt, double kappa, double p0, double p_unit, const int32_t* image, int64_t record_every, int64_t record_start,
-                 int64_t record_rows, void* traj_pos, void* traj_epot, void* traj_ekin, int64_t* traj_step, void* traj_cell, double* traj_pressure,
-                 void* stream) {
-  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_npt_back: dtype %d (0 f32, 1 f64)", dtype);
-  XEQ_CHECK_ARG(n >= 1 && n < ((int64_t)1 << 31) / 3 && n_chunks >= 1 && n_chunks < ((int64_t)1 << 31), "xeq_npt_back: %lld atoms, %lld chunks",
-                (long long)n, (long long)n_chunks);
-  XEQ_CHECK_ARG(n_chunks <= n && n_chunks * XEQ_MD_CHUNK >= n, "xeq_npt_back: %lld chunks of at most %d atoms cannot hold %lld atoms", (long long)n_chunks,
-                XEQ_MD_CHUNK, (long long)n);
-  XEQ_CHECK_ARG(md_finite(half_dt) && half_dt >= 0.0, "xeq_npt_back: half time step %g", half_dt);
-  XEQ_CHECK_ARG(md_finite(kappa) && kappa >= 0.0 && md_finite(p0) && md_finite(p_unit),
-                "xeq_npt_back: barostat (dt / taup * beta / 3 = %g >= 0, target pressure %g, pressure unit %g)", kappa, p0, p_unit);
-  XEQ_CHECK_ARG(record_every >= 0 && record_rows >= 0 && record_start >= 0, "xeq_npt_back: recorder (%lld, %lld, %lld)", (long long)record_every,
-                (long long)record_start, (long long)record_rows);
-  XEQ_CHECK_ARG(book && n_edges_step && box && virial_step && virial, "xeq_npt_back: null step counter, edge count, box record or virial");
-  XEQ_CHECK_ARG(!reps_needed || (reps && reps_seen), "xeq_npt_back: image counts of the step without the captured counts or the running maximum");
-  XEQ_CHECK_ARG(pos && vel && frc && frc_step && inv_mass && half_mass && chunk_atom0 && chunk_n && partial && partial_bad,
-                "xeq_npt_back: null per-atom or per-chunk buffer");
-  XEQ_CHECK_ARG(energy_step && graph_chunk_ptr && ke && epot, "xeq_npt_back: null per-graph buffer");
-  const bool rec = advance && record_every > 0 && record_rows > 0;
-  XEQ_CHECK_ARG(!rec || (traj_pos && traj_epot && traj_ekin && traj_step && traj_cell && traj_pressure && image), "xeq_npt_back: null trajectory buffer");
-  XEQ_DISPATCH_FLOAT(dtype, {
+int xeq_npt_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
+                 const xeq_npt_params* npt, const xeq_res_recorder* rec, int advance, void* stream) {
+  const char* who = "xeq_npt_back";
+  RES_TRY(res_dtype(who, sys, step && chunks && md && npt));
+  if (!rec) rec = &RES_NO_RECORDER;
+  const int64_t n = sys->n, n_chunks = sys->n_chunks;
+  XEQ_CHECK_ARG(n >= 1 && n < RES_MAX_ATOMS && n_chunks >= 1 && n_chunks < ((int64_t)1 << 31), "xeq_npt_back: %lld atoms, %lld chunks", (long long)n,
+                (long long)n_chunks);
+  RES_TRY(res_chunks_hold(who, sys));
+  XEQ_CHECK_ARG(md_finite(md->half_dt) && md->half_dt >= 0.0, "xeq_npt_back: half time step %g", md->half_dt);
+  XEQ_CHECK_ARG(md_finite(npt->kappa) && npt->kappa >= 0.0 && md_finite(npt->p0) && md_finite(npt->p_unit),
+                "xeq_npt_back: barostat (dt / taup * beta / 3 = %g >= 0, target pressure %g, pressure unit %g)", npt->kappa, npt->p0, npt->p_unit);
+  RES_TRY(res_recorder(who, rec));
+  XEQ_CHECK_ARG(sys->book && step->n_edges_step && npt->box && step->virial_step && npt->virial,
+                "xeq_npt_back: null step counter, edge count, box record or virial");
+  XEQ_CHECK_ARG(!step->reps_needed || npt->reps_seen, "xeq_npt_back: image counts of the step without the captured counts or the running maximum");
+  XEQ_CHECK_ARG(res_back_buffers(sys, step, chunks) && md->inv_mass && md->half_mass, "xeq_npt_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(step->energy_step && chunks->graph_chunk_ptr && md->ke && md->epot, "xeq_npt_back: null per-graph buffer");
+  const bool on = advance && rec->every > 0 && rec->rows > 0;
+  XEQ_CHECK_ARG(!on || (rec->traj_pos && rec->traj_epot && rec->traj_second && rec->traj_step && rec->traj_cell && rec->traj_pressure && sys->image),
+                "xeq_npt_back: null trajectory buffer");
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
     MdBox any{};
     any.any = any.periodic[0] = any.periodic[1] = any.periodic[2] = 1;   // (the recorder's cell is the record's: NptBox::cell)
-    MdBackArgs<T> a{n, 1, n_chunks, advance ? 1 : 0, (const T*)pos, (T*)vel, (T*)frc, (const T*)frc_step, (const T*)energy_step, n_edges_step,
-                    (const T*)inv_mass, (const T*)half_mass, chunk_atom0, chunk_n, graph_chunk_ptr, partial, partial_bad, (T*)ke, (T*)epot, book, half_dt,
-                    image, any, rec ? record_every : 0, record_start, record_rows, (T*)traj_pos, (T*)traj_epot, (T*)traj_ekin, traj_step};
-    NptBox<T> bx{(const T*)virial_step, (T*)virial, box, reps_needed, reps_seen, {reps ? reps[0] : 0, reps ? reps[1] : 0, reps ? reps[2] : 0},
-                 kappa, p0, p_unit, (T*)traj_cell, traj_pressure};
+    const MdBackArgs<T> a = md_back_args<T>(sys, step, chunks, md, rec, 1, advance, any, on);
+    NptBox<T> bx{(const T*)step->virial_step, (T*)npt->virial, npt->box, step->reps_needed, npt->reps_seen,
+                 {(int32_t)step->reps[0], (int32_t)step->reps[1], (int32_t)step->reps[2]}, npt->kappa, npt->p0, npt->p_unit, (T*)rec->traj_cell,
+                 rec->traj_pressure};
     hipLaunchKernelGGL(k_npt_back<T>, dim3((unsigned)n_chunks), dim3(MD_CHUNK), 0, (hipStream_t)stream, a, bx);
     XEQ_CHECK_LAUNCH("xeq_npt_back");
     if (n_chunks != 1) hipLaunchKernelGGL(k_npt_join<T>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, bx);
@@ -1003,59 +1077,57 @@ int xeq_npt_back(int dtype, int advance, int64_t n, int64_t n_chunks, const void
   return XEQ_OK;
 }
 
-int xeq_fire_front(int dtype, int64_t n, int64_t n_graphs, void* pos, void* vel, const void* frc, const uint8_t* fixed, const int64_t* batch,
-                   const int32_t* status, const double* coef, const double* cell, const int32_t* pbc, int32_t* image, void* stream) {
-  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_fire_front: dtype %d (0 f32, 1 f64)", dtype);
-  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3 && n_graphs >= 0, "xeq_fire_front: %lld atoms, %lld graphs", (long long)n, (long long)n_graphs);
+int xeq_fire_front(const xeq_res_system* sys, const xeq_fire_params* fire, void* stream) {
+  const char* who = "xeq_fire_front";
+  RES_TRY(res_dtype(who, sys, fire));
+  const int64_t n = sys->n, n_graphs = sys->n_graphs;
+  RES_TRY(res_atoms_graphs(who, sys));
   XEQ_CHECK_ARG(n == 0 || n_graphs >= 1, "xeq_fire_front: %lld atoms in no graph", (long long)n);
   MdBox box;
-  XEQ_CHECK_ARG(md_box(cell, pbc, &box), "xeq_fire_front: the cell is singular or not finite");
-  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && batch && status && coef), "xeq_fire_front: null state buffer");
-  XEQ_CHECK_ARG(n == 0 || !box.any || image, "xeq_fire_front: a periodic system needs the image counts");
+  RES_TRY(res_box(who, sys, &box));
+  XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->vel && sys->frc && sys->batch && fire->status && fire->coef), "xeq_fire_front: null state buffer");
+  XEQ_CHECK_ARG(n == 0 || !box.any || sys->image, "xeq_fire_front: a periodic system needs the image counts");
   if (n == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    FireFrontArgs<T> a{n, n_graphs, (T*)pos, (T*)vel, (const T*)frc, fixed, batch, status, coef, image, box};
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
+    FireFrontArgs<T> a{n, n_graphs, (T*)sys->pos, (T*)sys->vel, (const T*)sys->frc, fire->fixed, sys->batch, fire->status, fire->coef, sys->image, box};
     hipLaunchKernelGGL(k_fire_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   });
   XEQ_CHECK_LAUNCH("xeq_fire_front");
   return XEQ_OK;
 }
 
-int xeq_fire_back(int dtype, int64_t n, int64_t n_graphs, int64_t n_chunks, const void* pos, const void* vel, void* frc, const void* frc_step,
-                  const void* energy_step, const int32_t* n_edges_step, const uint8_t* fixed, const int64_t* batch, const int32_t* chunk_atom0,
-                  const int32_t* chunk_n, const int32_t* graph_chunk_ptr, double* partial, int32_t* partial_bad, void* epot, void* fmax, double* dt,
-                  double* alpha, int32_t* n_pos, int32_t* status, int64_t* converged_at, double* coef, int64_t* book, double fmax_tol,
-                  double maxstep, double dtmax, int n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, const double* cell,
-                  const int32_t* pbc, const int32_t* image, int64_t record_every, int64_t record_start, int64_t record_rows, void* traj_pos,
-                  void* traj_epot, void* traj_fmax, int64_t* traj_step, void* stream) {
-  XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_fire_back: dtype %d (0 f32, 1 f64)", dtype);
-  XEQ_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31) / 3 && n_graphs >= 0 && n_chunks >= 0 && n_chunks < ((int64_t)1 << 29),
-                "xeq_fire_back: %lld atoms, %lld graphs, %lld chunks", (long long)n, (long long)n_graphs, (long long)n_chunks);
-  XEQ_CHECK_ARG(n_chunks <= n && n_chunks * XEQ_MD_CHUNK >= n, "xeq_fire_back: %lld chunks of at most %d atoms cannot hold %lld atoms", (long long)n_chunks,
-                XEQ_MD_CHUNK, (long long)n);
+int xeq_fire_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_fire_params* fire,
+                  const xeq_res_recorder* rec, void* stream) {
+  const char* who = "xeq_fire_back";
+  RES_TRY(res_dtype(who, sys, step && chunks && fire));
+  if (!rec) rec = &RES_NO_RECORDER;
+  const int64_t n = sys->n, n_graphs = sys->n_graphs, n_chunks = sys->n_chunks;
+  const xeq_fire_params& f = *fire;
+  RES_TRY(res_back_sizes(who, sys, (int64_t)1 << 29));
   XEQ_CHECK_ARG(n == 0 || n_graphs >= 1, "xeq_fire_back: %lld atoms in no graph", (long long)n);
-  XEQ_CHECK_ARG(fmax_tol > 0.0 && md_finite(fmax_tol), "xeq_fire_back: fmax %g", fmax_tol);
-  XEQ_CHECK_ARG(maxstep > 0.0 && dtmax > 0.0 && md_finite(maxstep) && md_finite(dtmax), "xeq_fire_back: maxstep %g, dtmax %g", maxstep, dtmax);
-  XEQ_CHECK_ARG(f_inc >= 1.0 && md_finite(f_inc) && f_dec > 0.0 && f_dec < 1.0 && alpha_start >= 0.0 && alpha_start <= 1.0 && f_alpha > 0.0 &&
-                    f_alpha <= 1.0 && n_min >= 0,
-                "xeq_fire_back: mixing parameters (f_inc %g, f_dec %g, alpha_start %g, f_alpha %g, n_min %d)", f_inc, f_dec, alpha_start, f_alpha, n_min);
-  XEQ_CHECK_ARG(record_every >= 0 && record_rows >= 0 && record_start >= 0, "xeq_fire_back: recorder (%lld, %lld, %lld)", (long long)record_every,
-                (long long)record_start, (long long)record_rows);
+  XEQ_CHECK_ARG(f.fmax_tol > 0.0 && md_finite(f.fmax_tol), "xeq_fire_back: fmax %g", f.fmax_tol);
+  XEQ_CHECK_ARG(f.maxstep > 0.0 && f.dtmax > 0.0 && md_finite(f.maxstep) && md_finite(f.dtmax), "xeq_fire_back: maxstep %g, dtmax %g", f.maxstep,
+                f.dtmax);
+  XEQ_CHECK_ARG(f.f_inc >= 1.0 && md_finite(f.f_inc) && f.f_dec > 0.0 && f.f_dec < 1.0 && f.alpha_start >= 0.0 && f.alpha_start <= 1.0 &&
+                    f.f_alpha > 0.0 && f.f_alpha <= 1.0 && f.n_min >= 0 && f.n_min < ((int64_t)1 << 31),
+                "xeq_fire_back: mixing parameters (f_inc %g, f_dec %g, alpha_start %g, f_alpha %g, n_min %lld)", f.f_inc, f.f_dec, f.alpha_start,
+                f.f_alpha, (long long)f.n_min);
+  RES_TRY(res_recorder(who, rec));
   MdBox box;
-  XEQ_CHECK_ARG(md_box(cell, pbc, &box), "xeq_fire_back: the cell is singular or not finite");
-  XEQ_CHECK_ARG(book && n_edges_step, "xeq_fire_back: null evaluation counter or edge count");
-  XEQ_CHECK_ARG(n == 0 || (pos && vel && frc && frc_step && batch && chunk_atom0 && chunk_n && partial && partial_bad),
-                "xeq_fire_back: null per-atom or per-chunk buffer");
-  XEQ_CHECK_ARG(n_graphs == 0 || (energy_step && graph_chunk_ptr && epot && fmax && dt && alpha && n_pos && status && converged_at && coef),
+  RES_TRY(res_box(who, sys, &box));
+  XEQ_CHECK_ARG(sys->book && step->n_edges_step, "xeq_fire_back: null evaluation counter or edge count");
+  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks) && sys->batch), "xeq_fire_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(n_graphs == 0 || (step->energy_step && chunks->graph_chunk_ptr && f.epot && f.fmax && f.dt && f.alpha && f.n_pos && f.status &&
+                                  f.converged_at && f.coef),
                 "xeq_fire_back: null per-graph buffer");
-  const bool rec = record_every > 0 && record_rows > 0;
-  XEQ_CHECK_ARG(!rec || ((n == 0 || traj_pos) && (n_graphs == 0 || (traj_epot && traj_fmax)) && traj_step), "xeq_fire_back: null trajectory buffer");
-  XEQ_CHECK_ARG(!rec || n == 0 || !box.any || image, "xeq_fire_back: a periodic system's recorder needs the image counts");
-  XEQ_DISPATCH_FLOAT(dtype, {
-    FireBackArgs<T> a{n, n_graphs, n_chunks, (const T*)pos, (const T*)vel, (T*)frc, (const T*)frc_step, (const T*)energy_step, n_edges_step, fixed, batch,
-                      chunk_atom0, chunk_n, graph_chunk_ptr, partial, partial_bad, (T*)epot, (T*)fmax, dt, alpha, n_pos, status, converged_at, coef, book,
-                      fmax_tol, maxstep, dtmax, f_inc, f_dec, alpha_start, f_alpha, n_min, image, box, rec ? record_every : 0, record_start, record_rows,
-                      (T*)traj_pos, (T*)traj_epot, (T*)traj_fmax, traj_step};
+  const bool on = rec->every > 0 && rec->rows > 0;
+  if (on) RES_TRY(res_trajectory(who, sys, rec, box));
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
+    FireBackArgs<T> a{n, n_graphs, n_chunks, (const T*)sys->pos, (const T*)sys->vel, (T*)sys->frc, (const T*)step->frc_step, (const T*)step->energy_step,
+                      step->n_edges_step, f.fixed, sys->batch, chunks->chunk_atom0, chunks->chunk_n, chunks->graph_chunk_ptr, chunks->partial,
+                      chunks->partial_bad, (T*)f.epot, (T*)f.fmax, f.dt, f.alpha, f.n_pos, f.status, f.converged_at, f.coef, sys->book, f.fmax_tol,
+                      f.maxstep, f.dtmax, f.f_inc, f.f_dec, f.alpha_start, f.f_alpha, (int)f.n_min, sys->image, box, on ? rec->every : 0, rec->start,
+                      rec->rows, (T*)rec->traj_pos, (T*)rec->traj_epot, (T*)rec->traj_second, rec->traj_step};
     if (n_chunks > 0) {
       hipLaunchKernelGGL(k_fire_back<T>, dim3((unsigned)n_chunks), dim3(MD_CHUNK), 0, (hipStream_t)stream, a);
       XEQ_CHECK_LAUNCH("xeq_fire_back");

@@ -17,7 +17,9 @@ LIB_PATH = os.environ.get("XEQ_LIB_PATH") or os.path.join(_HERE, "libxeq_hip.so"
 
 XEQ_F32, XEQ_F64 = 0, 1
 COPY_MANY_MAX = 16       # XEQ_COPY_MANY_MAX of include/xeq.h
+# (tests/test_resident_records_host.py holds the next four lines against the header)
 MD_CHUNK = 256          # XEQ_MD_CHUNK of include/xeq.h: atoms per kinetic-energy chunk (md.py, optimize.py)
+MD_NVE, MD_LANGEVIN, MD_BERENDSEN, MD_PURPOSE_LANGEVIN, MD_PURPOSE_MAXWELL = 0, 1, 2, 0, 1      # XEQ_MD_* of include/xeq.h (md.py)
 NPT_BOX, NPT_CELL, NPT_INV, NPT_CELL_NEXT, NPT_INV_NEXT, NPT_MU, NPT_P, NPT_V = 40, 0, 9, 18, 27, 36, 37, 38      # XEQ_NPT_* of include/xeq.h (md.py)
 FIRE_FRESH, FIRE_ACTIVE, FIRE_CONVERGED = 0, 1, 2      # XEQ_FIRE_* of include/xeq.h
 VIB_MAX_DIM, VIB_MAX_SWEEPS = 96, 30     # XEQ_VIB_MAX_DIM, XEQ_VIB_MAX_SWEEPS of include/xeq.h (vibrations.py)
@@ -35,6 +37,42 @@ CUTOFF_KINDS = {"cosine": 0, "polynomial": 1}
 
 _P = c_void_p
 _I3 = ctypes.POINTER(c_int32)
+
+
+def _record(c_name: str, *groups):
+    """The ctypes.Structure of one argument record of include/xeq.h: ``groups`` = (type, "member names") in the header's order."""
+    return type(c_name, (ctypes.Structure,), {"_fields_": [(name, kind) for kind, names in groups for name in names.split()]})
+
+
+# The argument records of the resident drivers' front / back entries (resident.py), member for member those of include/xeq.h; every
+# member is 8 bytes wide.  In the order of XEQ_REC_*: load() holds their sizes against xeq_record_bytes.
+ResSystem = _record("xeq_res_system", (c_int64, "dtype n n_graphs n_chunks"), (_P, "pos vel frc image batch book cell pbc"))
+ResStep = _record("xeq_res_step", (_P, "frc_step energy_step n_edges_step virial_step reps_needed"), (c_int64 * 3, "reps"))
+ResChunks = _record("xeq_res_chunks", (_P, "chunk_atom0 chunk_n graph_chunk_ptr partial partial_bad"))
+ResRecorder = _record("xeq_res_recorder", (c_int64, "every start rows"), (_P, "traj_pos traj_epot traj_second traj_step traj_cell traj_pressure"))
+MdParams = _record("xeq_md_params", (c_int64, "ensemble"), (_P, "inv_mass half_mass ke epot tfac rng_id"), (c_uint64, "seed"),
+                   (c_double, "c1 noise2 dt_over_tau t0 half_dt"))
+NptParams = _record("xeq_npt_params", (_P, "box step_cell virial reps_seen"), (c_double, "kappa p0 p_unit"))
+FireParams = _record("xeq_fire_params", (_P, "fixed epot fmax dt alpha n_pos status converged_at coef"), (c_double, "fmax_tol maxstep dtmax"),
+                     (c_int64, "n_min"), (c_double, "f_inc f_dec alpha_start f_alpha"))
+RECORDS = [ResSystem, ResStep, ResChunks, ResRecorder, MdParams, NptParams, FireParams]
+_R = ctypes.POINTER
+
+
+def fill(record, **members):
+    """Set the named members of an argument record and return it.  A tensor gives its address, a ctypes array (host data) its own, None
+    is NULL; the caller keeps both alive.  A name the record does not have is an error, not a new Python attribute."""
+    kinds = dict(record._fields_)
+    for name, value in members.items():
+        if name not in kinds:
+            raise AttributeError(f"{type(record).__name__} has no member {name!r}")
+        if isinstance(value, torch.Tensor):
+            value = value.data_ptr()
+        elif isinstance(value, ctypes.Array) and kinds[name] is _P:
+            value = ctypes.addressof(value)
+        setattr(record, name, value)
+    return record
+
 
 # name -> argtypes, exactly the prototypes of include/xeq.h
 _PROTOS = {
@@ -230,27 +268,23 @@ _PROTOS = {
     "xeq_ewald_layernorm_fwd": [_P, c_int64, c_int, _P, _P, c_double, _P, _P, _P],
     "xeq_ewald_layernorm_bwd": [_P, _P, _P, _P, c_int64, c_int, _P, _P],
     "xeq_ewald_combine": [_P, c_double, _P, c_double, _P, c_int64, _P, _P],
+    "xeq_record_bytes": [c_int],
     "xeq_md_inverse_cell": [ctypes.POINTER(c_double), ctypes.POINTER(c_double)],
     "xeq_md_normals": [c_int, c_uint64, c_int, c_uint64, _P, c_int64, _P, _P, _P],
-    "xeq_md_front": [c_int, c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint64, c_double, c_double, c_double, c_double, c_double,
-                     ctypes.POINTER(c_double), _I3, _P, _P],
-    "xeq_md_back": [c_int, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_double,
-                    ctypes.POINTER(c_double), _I3, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P],
+    "xeq_md_front": [_R(ResSystem), _R(MdParams), c_double, _P],
+    "xeq_md_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(MdParams), _R(ResRecorder), c_int, _P],
     "xeq_pbc_tables_device": [c_int, _P, _I3, _I3, c_double, _P, c_int64, _P, _P],
-    "xeq_npt_front": [c_int, c_int64, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_double, _P, _P, _P, _P],
-    "xeq_npt_back": [c_int, c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _I3, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                     c_double, c_double, c_double, c_double, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P],
-    "xeq_fire_front": [c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(c_double), _I3, _P, _P],
-    "xeq_fire_back": [c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                      c_double, c_double, c_double, c_int, c_double, c_double, c_double, c_double, ctypes.POINTER(c_double), _I3, _P, c_int64, c_int64,
-                      c_int64, _P, _P, _P, _P, _P],
+    "xeq_npt_front": [_R(ResSystem), _R(MdParams), _R(NptParams), c_double, _P],
+    "xeq_npt_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(MdParams), _R(NptParams), _R(ResRecorder), c_int, _P],
+    "xeq_fire_front": [_R(ResSystem), _R(FireParams), _P],
+    "xeq_fire_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(FireParams), _R(ResRecorder), _P],
     "xeq_vib_project": [c_int, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "xeq_vib_eigh": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],
     "xeq_vib_finish": [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P],
     "xeq_vib_thermo_sums": [_P, _P, _P, c_int64, c_double, _P, _P],
 }
 # entry points that return a size, not a status
-_RET_I64 = {"xeq_launch_count", "xeq_launch_names", "xeq_message_wq_packed_weight_floats", "xeq_rowptr_from_degrees_max", "xeq_csr_by_key_workspace", "xeq_message_wq_pcap", "xeq_message_wq_plan_workspace", "xeq_message_wq_win_ints",
+_RET_I64 = {"xeq_record_bytes", "xeq_launch_count", "xeq_launch_names", "xeq_message_wq_packed_weight_floats", "xeq_rowptr_from_degrees_max", "xeq_csr_by_key_workspace", "xeq_message_wq_pcap", "xeq_message_wq_plan_workspace", "xeq_message_wq_win_ints",
             "xeq_message_wq_parts_floats", "xeq_mlp_packed_floats", "xeq_exclusive_scan_i32_workspace", "xeq_node_block_fwd_tiles", "xeq_node_block_bwd_tiles", "xeq_node_block_rows", "xeq_pack_epoch", "xeq_tensor_product_wgrad_chunks", "xeq_small_rows_limit", "xeq_painn_few_rows_limit",
             "xeq_painn_filter_packed_floats", "xeq_painn_uv_packed_floats", "xeq_ewald_chunk", "xeq_ewald_parts_floats"}
 EXPORTS = ["xeq_version", "xeq_last_error", *_PROTOS]
@@ -275,6 +309,10 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_int64 if name in _RET_I64 else c_int
+    for which, record in enumerate(RECORDS):      # a binding whose layout is not the library's would hand kernels the wrong buffers
+        if ctypes.sizeof(record) != lib.xeq_record_bytes(which):
+            raise ImportError(f"{LIB_PATH}: {record.__name__} is {lib.xeq_record_bytes(which)} bytes in the library, {ctypes.sizeof(record)} in "
+                              "xequinet_amd/lib.py (a library of another version?)")
     _lib = lib
     return lib
 

@@ -36,10 +36,10 @@ from .lib import call, dtype_code, require_hip
 from .resident import ResidentDriver, chunk_tables  # noqa: F401  (chunk_tables: part of this module's interface)
 from .utils import units as _units
 
-ENSEMBLES = {"nve": 0, "langevin": 1, "berendsen": 2,        # XEQ_MD_NVE / _LANGEVIN / _BERENDSEN of include/xeq.h
-             "npt_berendsen": 2}                              # (its thermostat; the barostat has entries of its own: xeq_npt_front / _back)
+ENSEMBLES = {"nve": lib.MD_NVE, "langevin": lib.MD_LANGEVIN, "berendsen": lib.MD_BERENDSEN,
+             "npt_berendsen": lib.MD_BERENDSEN}               # (its thermostat; the barostat has entries of its own: xeq_npt_front / _back)
 NPT = "npt_berendsen"
-PURPOSE_LANGEVIN, PURPOSE_MAXWELL = 0, 1                     # XEQ_MD_PURPOSE_*
+PURPOSE_LANGEVIN, PURPOSE_MAXWELL = lib.MD_PURPOSE_LANGEVIN, lib.MD_PURPOSE_MAXWELL
 BOLTZMANN_J_PER_K = 1.380649e-23                             # exact (SI 2019)
 
 
@@ -164,15 +164,14 @@ class Dynamics(ResidentDriver):
         self._ck = None
         self._steps_host = 0
         self._fresh = False            # frc / ke / epot belong to the current positions and velocities
-        self._rec = (0, 0, 0)
-        self.trajectory: Dict[str, torch.Tensor] = {}
-        self._back_args = None
-        self._front_args = None
         self._ke_stale = False         # velocities were set since ke was formed
         self._no_edges = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._run_serial = 0           # (part of the cache key of xeq_md_back's arguments: every run has its own trajectory buffers)
 
         self._load_system(pos, atomic_numbers, cell, pbc)
+        self._md = lib.fill(lib.MdParams(), ensemble=ENSEMBLES[ensemble], inv_mass=self.inv_mass, half_mass=self.half_mass, ke=self.ke, epot=self.epot,
+                            tfac=self.tfac, rng_id=self.rng_id, seed=self.seed, c1=self._c1, noise2=self._noise2, dt_over_tau=self._dt_over_tau,
+                            t0=self.temperature_K or 0.0, half_dt=0.5 * self.dt)
+        self._own = (ctypes.byref(self._md),)          # the driver's own records, as both of its entries take them
         if self._npt:
             # the box record of include/xeq.h (XEQ_NPT_*): current = pending = the cell the step object holds, mu = 1
             c = (ctypes.c_double * 9)(*self._cell_c)
@@ -185,86 +184,27 @@ class Dynamics(ResidentDriver):
             self.box = on(rec, torch.float64)
             self.vir = torch.zeros(9, dtype=dt_, device=dev)
             self.reps_seen = torch.zeros(3, dtype=torch.int32, device=dev)
+            self._npt_rec = lib.fill(lib.NptParams(), box=self.box, step_cell=self.step.cell, virial=self.vir, reps_seen=self.reps_seen,
+                                     kappa=self._kappa, p0=self._p0, p_unit=self._p_unit)
+            self._own += (ctypes.byref(self._npt_rec),)
+        # the kinetic energies alone (_back_ke): the back on the forces and energies this object holds, which depend on the positions alone
+        self._own_step = lib.fill(lib.ResStep(), frc_step=self.frc, energy_step=self.epot, n_edges_step=self._no_edges,
+                                  virial_step=self.vir if self._npt else None)
         self._front_name, self._back_name = ("xeq_npt_front", "xeq_npt_back") if self._npt else ("xeq_md_front", "xeq_md_back")
-        call(self._front_name, *self._front_tuple(0.0), lib.stream())     # dt = 0: the wrap alone: the search sweeps +- reps images around the box, not around a stray atom
+        call(self._front_name, *self._front_args(0.0), lib.stream())      # dt = 0: the wrap alone: the search sweeps +- reps images around the box, not around a stray atom
 
     # ------------------------------------------------------------------------------------------------ launches
-    def _front_tuple(self, dt: float):
-        p = lib.ptr
-        if self._npt:
-            return (self._code, self.n_atoms, p(self._pos), p(self.vel), p(self.frc), p(self.inv_mass), p(self.step.batch), p(self.ke), p(self.tfac),
-                    dt, self._dt_over_tau, self.temperature_K or 0.0, p(self.box), p(self.step.cell), p(self.image))
-        return (self._code, ENSEMBLES[self.ensemble], self.n_atoms, self.n_graphs, p(self._pos), p(self.vel), p(self.frc), p(self.inv_mass),
-                p(self.step.batch), p(self.ke), p(self.tfac), p(self.rng_id), p(self.book), self.seed, dt, self._c1, self._noise2,
-                self._dt_over_tau, self.temperature_K or 0.0, self._cell_c, self._pbc_c, p(self.image))
+    def _front_args(self, dt: Optional[float] = None):
+        return (ctypes.byref(self._sys), *self._own, self.dt if dt is None else dt)
 
-    def _front(self, dt: float) -> None:
-        if dt == self.dt:
-            if self._front_args is None:
-                self._front_args = self._front_tuple(dt)          # (every buffer named here lives as long as this object)
-            call(self._front_name, *self._front_args, lib.stream())
-        else:
-            call(self._front_name, *self._front_tuple(dt), lib.stream())
-
-    def _back_tuple(self, outputs, frc=None, energy=None, n_edges=None, record=True):
-        """The arguments of the back entry behind (dtype, advance); ``outputs`` None: the driver's own copies (``_back_ke``)."""
-        p = lib.ptr
-        frc = outputs[keys.FORCES] if frc is None else frc
-        en = outputs[keys.TOTAL_ENERGY] if energy is None else energy
-        ne = outputs["n_edges"] if n_edges is None else n_edges
-        assert frc.is_contiguous() and frc.dtype == self.dtype and en.is_contiguous() and en.dtype == self.dtype and ne.dtype == torch.int32
-        t = self.trajectory if record else {}
-        every, start, rows = self._rec if record else (0, 0, 0)
-        if self._npt:
-            vir = self.vir if outputs is None else outputs[keys.VIRIAL]
-            needed = None if outputs is None else outputs["reps_needed"]
-            assert vir.is_contiguous() and vir.dtype == self.dtype and vir.numel() == 9
-            return (self.n_atoms, self.n_chunks, p(self._pos), p(self.vel), p(self.frc), p(frc), p(en), p(ne), p(vir), p(needed), lib.mul3(self.step.reps),
-                    p(self.inv_mass), p(self.half_mass), p(self._chunk_atom0), p(self._chunk_n), p(self._graph_chunk_ptr), p(self._partial),
-                    p(self._partial_bad), p(self.ke), p(self.epot), p(self.vir), p(self.reps_seen), p(self.book), p(self.box), 0.5 * self.dt, self._kappa,
-                    self._p0, self._p_unit, p(self.image), every, start, rows, p(t.get("pos")), p(t.get("epot")), p(t.get("ekin")), p(t.get("step")),
-                    p(t.get("cell")), p(t.get("pressure")))
-        return (self.n_atoms, self.n_graphs, self.n_chunks, p(self._pos), p(self.vel), p(self.frc), p(frc), p(en), p(ne), p(self.inv_mass),
-                p(self.half_mass), p(self._chunk_atom0), p(self._chunk_n), p(self._graph_chunk_ptr), p(self._partial), p(self._partial_bad),
-                p(self.ke), p(self.epot), p(self.book), 0.5 * self.dt, self._cell_c, self._pbc_c, p(self.image), every, start, rows,
-                p(t.get("pos")), p(t.get("epot")), p(t.get("ekin")), p(t.get("step")))
-
-    def _back(self, advance: bool) -> None:
-        key = (self.step.captures, self._rec, self._run_serial)
-        if self._back_args is None or self._back_args[0] != key:
-            self._back_args = (key, self._back_tuple(self.step.outputs))
-        call(self._back_name, self._code, int(advance), *self._back_args[1], lib.stream())
+    def _back_args(self, advance: bool):
+        return (ctypes.byref(self._sys), ctypes.byref(self._step_record()), ctypes.byref(self._chunks), *self._own, ctypes.byref(self._rec), int(advance))
 
     def _back_ke(self) -> None:
         """The kinetic energies of new velocities: the back kernel without a kick on the forces and energies this object holds (they
-        depend on the positions alone); no evaluation, no read-back."""
-        call(self._back_name, self._code, 0, *self._back_tuple(None, self.frc, self.epot, self._no_edges, record=False), lib.stream())
+        depend on the positions alone); no evaluation, no recorder, no read-back."""
+        call(self._back_name, ctypes.byref(self._sys), ctypes.byref(self._own_step), ctypes.byref(self._chunks), *self._own, None, 0, lib.stream())
         self._ke_stale = False
-
-    def _enqueue(self, n: int) -> None:
-        """``n`` steps on the current stream; nothing here waits for the device."""
-        if n <= 0:
-            return
-        # the step's own graph between two launches.  The first evaluation goes through the step object's logic; nothing can move the
-        # weights between that one and the window's check, so the others replay the graph it left.  Arguments are bound once.
-        L = lib.load()
-        front, back = getattr(L, self._front_name), getattr(L, self._back_name)
-        if self._front_args is None:
-            self._front_args = self._front_tuple(self.dt)
-        stream = lib.stream()
-        fa = (*self._front_args, stream)
-        if front(*fa):
-            raise RuntimeError(f"{self._front_name} failed: {L.xeq_last_error().decode()}")
-        self._eval()
-        self._back(True)
-        ba = (self._code, 1, *self._back_args[1], stream)
-        replay = self.step.graph.replay
-        for _ in range(n - 1):
-            if front(*fa):
-                raise RuntimeError(f"{self._front_name} failed: {L.xeq_last_error().decode()}")
-            replay()
-            if back(*ba):
-                raise RuntimeError(f"{self._back_name} failed: {L.xeq_last_error().decode()}")
 
     # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
     def _state(self):
@@ -284,9 +224,8 @@ class Dynamics(ResidentDriver):
             self._back_ke()
 
     def _first_evaluation(self) -> None:
-        self._eval()
-        self._back(False)
-        self._fresh, self._ke_stale = True, False
+        super()._first_evaluation()
+        self._ke_stale = False
 
     def _bad_message(self, first: int, n: int) -> str:
         return f"Dynamics: non-finite force or energy in steps {first} .. {first + n}; the state is that of step {first}"
@@ -302,19 +241,12 @@ class Dynamics(ResidentDriver):
         n_steps, check_every, record_every = int(n_steps), max(1, int(check_every)), max(0, int(record_every))
         if n_steps < 0:
             raise ValueError("Dynamics.run: n_steps < 0")
-        self._run_serial += 1
-        if record_every > 0:
+        self._record_run(n_steps, record_every, "ekin", self._steps_host)
+        if self._npt and record_every > 0:
             rows = n_steps // record_every
-            self.trajectory = {"pos": torch.zeros((rows, self.n_atoms, 3), dtype=self.dtype, device=self.device),
-                               "epot": torch.zeros((rows, self.n_graphs), dtype=self.dtype, device=self.device),
-                               "ekin": torch.zeros((rows, self.n_graphs), dtype=self.dtype, device=self.device),
-                               "step": torch.zeros(rows, dtype=torch.int64, device=self.device)}
-            if self._npt:
-                self.trajectory["cell"] = torch.zeros((rows, 3, 3), dtype=self.dtype, device=self.device)
-                self.trajectory["pressure"] = torch.zeros(rows, dtype=torch.float64, device=self.device)          # GPa
-            self._rec = (record_every, self._steps_host, rows)
-        else:
-            self.trajectory, self._rec = {}, (0, 0, 0)
+            self.trajectory["cell"] = torch.zeros((rows, 3, 3), dtype=self.dtype, device=self.device)
+            self.trajectory["pressure"] = torch.zeros(rows, dtype=torch.float64, device=self.device)          # GPa
+            lib.fill(self._rec, traj_cell=self.trajectory["cell"], traj_pressure=self.trajectory["pressure"])
         done = 0
         while done < n_steps:
             w = min(check_every, n_steps - done)

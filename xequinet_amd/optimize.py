@@ -14,6 +14,7 @@ reads four integers back and stops at the first check that finds no active graph
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, Optional
 
@@ -87,74 +88,22 @@ class FIRE(ResidentDriver):
         self._steps_host = 0           # evaluations done
         self._active_host = G
         self._fresh = False            # frc / epot / fmax / coef belong to the current positions
-        self._rec = (0, 0, 0)
-        self.trajectory: Dict[str, torch.Tensor] = {}
-        self._back_args = None
-        self._front_args = None
-        self._run_serial = 0           # (part of the cache key of xeq_fire_back's arguments: every run has its own trajectory buffers)
+        self._front_name, self._back_name = "xeq_fire_front", "xeq_fire_back"
 
         self._load_system(pos, atomic_numbers, cell, pbc)
+        self._fire = lib.fill(lib.FireParams(), fixed=self.fixed, epot=self.epot, fmax=self.fmax, dt=self.dt, alpha=self.alpha, n_pos=self.n_pos,
+                              status=self.status, converged_at=self._converged_at, coef=self.coef, fmax_tol=self.fmax_tol, maxstep=self.maxstep,
+                              dtmax=self.dtmax, n_min=self.n_min, f_inc=self.f_inc, f_dec=self.f_dec, alpha_start=self.alpha_start, f_alpha=self.f_alpha)
         if self._any_pbc:              # the wrap alone (c_v = c_f = d = 0 on zero velocities and forces): the search sweeps images around the box
-            p = lib.ptr
             every = torch.full((G,), lib.FIRE_ACTIVE, dtype=torch.int32, device=dev)
-            call("xeq_fire_front", self._code, N, G, p(self._pos), p(self.vel), p(self.frc), None, p(self.step.batch), p(every), p(self.coef),
-                 self._cell_c, self._pbc_c, p(self.image), lib.stream())
+            call("xeq_fire_front", ctypes.byref(self._sys), ctypes.byref(lib.fill(lib.FireParams(), status=every, coef=self.coef)), lib.stream())
 
     # ------------------------------------------------------------------------------------------------ launches
-    def _front_tuple(self):
-        p = lib.ptr
-        return (self._code, self.n_atoms, self.n_graphs, p(self._pos), p(self.vel), p(self.frc), p(self.fixed), p(self.step.batch), p(self.status),
-                p(self.coef), self._cell_c, self._pbc_c, p(self.image))
+    def _front_args(self):
+        return (ctypes.byref(self._sys), ctypes.byref(self._fire))
 
-    def _back_tuple(self, outputs):
-        p = lib.ptr
-        frc, en, ne = outputs[keys.FORCES], outputs[keys.TOTAL_ENERGY], outputs["n_edges"]
-        assert frc.is_contiguous() and frc.dtype == self.dtype and en.is_contiguous() and en.dtype == self.dtype and ne.dtype == torch.int32
-        t = self.trajectory
-        every, start, rows = self._rec
-        return (self._code, self.n_atoms, self.n_graphs, self.n_chunks, p(self._pos), p(self.vel), p(self.frc), p(frc), p(en), p(ne), p(self.fixed),
-                p(self.step.batch), p(self._chunk_atom0), p(self._chunk_n), p(self._graph_chunk_ptr), p(self._partial), p(self._partial_bad),
-                p(self.epot), p(self.fmax), p(self.dt), p(self.alpha), p(self.n_pos), p(self.status), p(self._converged_at), p(self.coef),
-                p(self.book), self.fmax_tol, self.maxstep, self.dtmax, self.n_min, self.f_inc, self.f_dec, self.alpha_start, self.f_alpha,
-                self._cell_c, self._pbc_c, p(self.image), every, start, rows, p(t.get("pos")), p(t.get("epot")), p(t.get("fmax")), p(t.get("step")))
-
-    def _args(self):
-        """The two argument tuples, bound once: every buffer named there lives as long as this object, except the step's outputs (a new
-        capture) and the trajectory (a new run)."""
-        if self._front_args is None:
-            self._front_args = self._front_tuple()
-        key = (self.step.captures, self._rec, self._run_serial)
-        if self._back_args is None or self._back_args[0] != key:
-            self._back_args = (key, self._back_tuple(self.step.outputs))
-        return self._front_args, self._back_args[1]
-
-    def _first_evaluation(self) -> None:
-        self._eval()
-        call("xeq_fire_back", *self._args()[1], lib.stream())
-        self._fresh = True
-
-    def _enqueue(self, n: int) -> None:
-        """``n`` iterations on the current stream; nothing here waits for the device.  The first evaluation goes through the step object's
-        logic; nothing can move the weights between that one and the window's check, so the others replay the graph it left."""
-        if n <= 0:
-            return
-        L = lib.load()
-        front, back = L.xeq_fire_front, L.xeq_fire_back
-        stream = lib.stream()
-        for k in range(n):
-            if k == 0:
-                fa = (*self._args()[0], stream)
-            if front(*fa):
-                raise RuntimeError(f"xeq_fire_front failed: {L.xeq_last_error().decode()}")
-            if k == 0:
-                self._eval()
-                ba = (*self._args()[1], stream)          # (behind the evaluation: a new capture has new output buffers)
-                replay = self.step.graph.replay
-            else:
-                replay()
-            if back(*ba):
-                raise RuntimeError(f"xeq_fire_back failed: {L.xeq_last_error().decode()}")
-
+    def _back_args(self, advance: bool):
+        return (ctypes.byref(self._sys), ctypes.byref(self._step_record()), ctypes.byref(self._chunks), ctypes.byref(self._fire), ctypes.byref(self._rec))
     # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
     def _state(self):
         return [self._pos, self.image, self.vel, self.frc, self.epot, self.fmax, self.dt, self.alpha, self.n_pos, self.status, self._converged_at,
@@ -176,15 +125,7 @@ class FIRE(ResidentDriver):
         max_steps, check_every, record_every = int(max_steps), max(1, int(check_every)), max(0, int(record_every))
         if max_steps < 0:
             raise ValueError("FIRE.run: max_steps < 0")
-        self._run_serial += 1
-        if record_every > 0:
-            rows = max_steps // record_every
-            mk = lambda *shape: torch.zeros(shape, dtype=self.dtype, device=self.device)
-            self.trajectory = {"pos": mk(rows, self.n_atoms, 3), "epot": mk(rows, self.n_graphs), "fmax": mk(rows, self.n_graphs),
-                               "step": torch.zeros(rows, dtype=torch.int64, device=self.device)}
-            self._rec = (record_every, self.step_count, rows)
-        else:
-            self.trajectory, self._rec = {}, (0, 0, 0)
+        self._record_run(max_steps, record_every, "fmax", self.step_count)
         if not self._fresh:
             self._window(0)            # evaluation 0: a start that is already relaxed moves nothing
         done = 0

@@ -1,18 +1,20 @@
 """What the drivers that live next to a whole-step graph share (md.Dynamics, optimize.FIRE; DESIGN.md sections 12 and 13): the step object
-and its static buffers, the chunk tables of the fixed-order per-graph sums, the one read-back per window, and the window / checkpoint /
-restore / grow protocol for a neighbour list that outgrows its capacity.  A driver supplies its own two launches and its own state.
+and its static buffers, the chunk tables of the fixed-order per-graph sums, the argument records of the front / back entries that every
+driver fills alike (include/xeq.h: system, step, chunks, recorder), the loop that enqueues front, step graph and back, the one read-back
+per window, and the window / checkpoint / restore / grow protocol for a neighbour list that outgrows its capacity.  A driver supplies the
+arguments of its own two launches and its own state.
 """
 from __future__ import annotations
 
 import ctypes
 import math
-from typing import Optional
+from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import lib, ops
-from .lib import dtype_code, require_hip
+from . import keys, lib, ops
+from .lib import call, dtype_code, require_hip
 from .runtime import GraphedStep, GraphedStepPBC, pair_capacity
 
 
@@ -30,10 +32,12 @@ def chunk_tables(ptr_host, chunk: int = lib.MD_CHUNK):
 
 
 class ResidentDriver:
-    """Base of the device-resident drivers.  A subclass sets, before the first window: ``book`` (int64 [4] on the device: entry 0 its
-    counter, 1 the largest n_edges seen, 2 the non-finite flag, 3 its own), ``_steps_host``, ``_fresh`` (forces and energies belong to
-    the current positions), ``_ck = None``; and defines ``_state()`` (the tensors of a checkpoint), ``_first_evaluation()``,
-    ``_enqueue(n)``, ``_bad_message(first, n)`` and, if it needs one, ``_before_window()``."""
+    """Base of the device-resident drivers.  A subclass sets, between ``_init_system`` and ``_load_system``: ``vel``, ``frc``, ``image``,
+    ``_partial``, ``_partial_bad`` and ``book`` (int64 [4] on the device: entry 0 its counter, 1 the largest n_edges seen, 2 the
+    non-finite flag, 3 its own); before the first window ``_steps_host``, ``_fresh`` (forces and energies belong to the current
+    positions), ``_ck = None``, ``_front_name`` / ``_back_name`` (its two entries); and defines ``_state()`` (the tensors of a
+    checkpoint), ``_front_args()`` / ``_back_args(advance)`` (the entries' arguments in front of the stream), ``_bad_message(first, n)``
+    and, if it needs one, ``_before_window()``."""
 
     def _init_system(self, model, N: int, ptr: Optional[torch.Tensor], cell: Optional[torch.Tensor], edge_capacity: Optional[int], tensors,
                      step_kwargs=None) -> None:
@@ -87,11 +91,72 @@ class ResidentDriver:
             self.step._load(pos, z, torch.from_numpy(self.ptr_host).to(dev), None)
             self._cell_dev, self._cell_c, self._pbc_c, self._any_pbc = None, None, None, False
         self._pos = self.step.pos[:N]        # THE positions: the step's static buffer (a periodic system's are wrapped into the box)
+        # the records every front / back entry takes (include/xeq.h); every buffer named here lives as long as this object
+        self._sys = lib.fill(lib.ResSystem(), dtype=self._code, n=N, n_graphs=self.n_graphs, n_chunks=self.n_chunks, pos=self._pos, vel=self.vel,
+                             frc=self.frc, image=self.image, batch=self.step.batch, book=self.book, cell=self._cell_c, pbc=self._pbc_c)
+        self._chunks = lib.fill(lib.ResChunks(), chunk_atom0=self._chunk_atom0, chunk_n=self._chunk_n, graph_chunk_ptr=self._graph_chunk_ptr,
+                                partial=self._partial, partial_bad=self._partial_bad)
+        self._step_rec, self._step_captures = lib.ResStep(), None
+        self._rec = lib.ResRecorder()        # (all zero: nothing is recorded)
+        self.trajectory: Dict[str, torch.Tensor] = {}
 
     def _eval(self) -> None:
         """The whole step on what the static buffers hold, through the step object's own logic (captured on first use, again when the
         weights moved or the edge arrays grew)."""
         self.step.replay()
+
+    # ------------------------------------------------------------------------------------------------ launches
+    def _step_record(self):
+        """The step graph's outputs as the back entries take them; refilled behind a new capture, which has new output buffers (and, for
+        a box on the device, may have other image counts)."""
+        if self._step_captures != self.step.captures:
+            out = self.step.outputs
+            frc, en, ne, vir = out[keys.FORCES], out[keys.TOTAL_ENERGY], out["n_edges"], out.get(keys.VIRIAL)
+            assert frc.is_contiguous() and frc.dtype == self.dtype and en.is_contiguous() and en.dtype == self.dtype and ne.dtype == torch.int32
+            assert vir is None or (vir.is_contiguous() and vir.dtype == self.dtype and vir.numel() == 9)
+            lib.fill(self._step_rec, frc_step=frc, energy_step=en, n_edges_step=ne, virial_step=vir, reps_needed=out.get("reps_needed"),
+                     reps=tuple(self.step.reps) if self.periodic else (0, 0, 0))
+            self._step_captures = self.step.captures
+        return self._step_rec
+
+    def _record_run(self, n_steps: int, record_every: int, second: str, start: int) -> None:
+        """A run's trajectory -- a row per ``record_every`` steps of pos, epot, ``second`` (a per-graph quantity) and step -- and the
+        recorder record that points at it; with ``record_every`` 0 neither."""
+        self.trajectory, self._rec = {}, lib.ResRecorder()
+        if record_every > 0:
+            rows = n_steps // record_every
+            mk = lambda *shape: torch.zeros(shape, dtype=self.dtype, device=self.device)
+            t = self.trajectory = {"pos": mk(rows, self.n_atoms, 3), "epot": mk(rows, self.n_graphs), second: mk(rows, self.n_graphs),
+                                   "step": torch.zeros(rows, dtype=torch.int64, device=self.device)}
+            lib.fill(self._rec, every=record_every, start=start, rows=rows, traj_pos=t["pos"], traj_epot=t["epot"], traj_second=t[second],
+                     traj_step=t["step"])
+
+    def _first_evaluation(self) -> None:
+        self._eval()
+        call(self._back_name, *self._back_args(False), lib.stream())
+        self._fresh = True
+
+    def _enqueue(self, n: int) -> None:
+        """``n`` steps on the current stream -- front, the step's own graph, back -- and nothing here waits for the device.  The first
+        evaluation goes through the step object's logic; nothing can move the weights between that one and the window's check, so the
+        others replay the graph it left.  Arguments are bound once."""
+        if n <= 0:
+            return
+        L = lib.load()
+        front, back = getattr(L, self._front_name), getattr(L, self._back_name)
+        stream = lib.stream()
+        fa = (*self._front_args(), stream)
+        for k in range(n):
+            if front(*fa):
+                raise RuntimeError(f"{self._front_name} failed: {L.xeq_last_error().decode()}")
+            if k == 0:
+                self._eval()
+                ba = (*self._back_args(True), stream)          # (behind the evaluation: a new capture has new output buffers)
+                replay = self.step.graph.replay
+            else:
+                replay()
+            if back(*ba):
+                raise RuntimeError(f"{self._back_name} failed: {L.xeq_last_error().decode()}")
 
     def _read_book(self):
         """THE read-back: (counter, largest n_edges since the last check, non-finite flag); the fourth entry is kept in ``_book_extra``.

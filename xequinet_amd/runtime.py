@@ -967,7 +967,8 @@ class GraphedStepPBC:
         self._run()
 
     def grow(self, n_edges_seen: int) -> None:
-        """More room for a list that reached ``n_edges_seen`` edges, by the rule of ``__call__``; the next replay captures again."""
+        """More room for a list that reached ``n_edges_seen`` edges: half as much again as the larger of that and the capacity, plus 64;
+        the next replay captures again."""
         self.n_edges = int(self.GROWTH * max(self.n_edges, int(n_edges_seen))) + 64
         self._alloc_edges()
         self.graph = None
@@ -982,9 +983,7 @@ class GraphedStepPBC:
         self._run()
         if check:
             while self.overflowed():
-                self.n_edges = int(self.GROWTH * max(self.n_edges, int(self.outputs["n_edges"].item()))) + 64
-                self._alloc_edges()
-                self.graph = None
+                self.grow(int(self.outputs["n_edges"].item()))
                 self._run()
         return dict(self.outputs)
 
