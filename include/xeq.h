@@ -1189,12 +1189,21 @@ int xeq_fire_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq
  *   sweeps [n]; status [n]: 0, or 1 when XEQ_VIB_MAX_SWEEPS sweeps did not reach off(A) <= dim 2^-53 |A|_F.  Two-sided cyclic Jacobi in
  *   round-robin ordering, A and V in LDS sized from max_dim (>= every dim[g]); max_dim > XEQ_VIB_MAX_DIM is refused with
  *   XEQ_ERR_INVALID_ARGUMENT before any launch.
+ * xeq_vib_eigh_large: the same arguments and the same output contract for dimensions up to XEQ_VIB_LARGE_MAX_DIM (any dim >= 1 is
+ *   accepted, so the two entries can be compared on one matrix).  One workgroup per matrix working in the matrix's own block of
+ *   `eigenvectors` in global memory (`mat` is only read; the two buffers must not overlap): Householder tridiagonalisation with
+ *   accumulated Q, then implicit-shift QL with the rotations applied to Q^T.  sweeps: the largest number of QL iterations any one
+ *   eigenvalue took; status 1 when one eigenvalue took more than XEQ_VIB_MAX_SWEEPS, or an eigenvalue is not finite.  max_dim >
+ *   XEQ_VIB_LARGE_MAX_DIM is refused with XEQ_ERR_INVALID_ARGUMENT before any launch: 768 is 256 atoms, and above it one workgroup per
+ *   matrix is the wrong shape for the work (a solver that spreads one matrix over the device is not built; vibrations.py keeps
+ *   torch.linalg.eigh there).
  * xeq_vib_finish: from the lowest m - n_tr eigenpairs of graph g (eigenvalues at 3 ptr[g]), at mode_ptr[g] (norm_mode [k, n, 3] at
  *   mode_off[g]): eigenvalue, norm_mode = m_i^-1/2 v_k, reduced_mass = 1 / sum norm_mode^2, freq_wavenumber = sign(l) sqrt(|l|)
  *   to_wavenumber, vib_temperature = sign(l) sqrt(|l|) to_kelvin, force_const = reduced_mass l; n_imaginary [n_graphs].
  * xeq_vib_thermo_sums: sums [n_graphs, 4] over the modes with eigenvalue > 0, x = vib_temperature / temperature:
  *   theta / 2, theta / (e^x - 1), x / (e^x - 1) - ln(1 - e^-x), x^2 e^x / (e^x - 1)^2. */
 #define XEQ_VIB_MAX_DIM 96
+#define XEQ_VIB_LARGE_MAX_DIM 768
 #define XEQ_VIB_MAX_SWEEPS 30
 enum { XEQ_VIB_ATOM = 0, XEQ_VIB_LINEAR = 1, XEQ_VIB_NONLINEAR = 2 };
 int xeq_vib_project(int dtype, const void* hess, const int64_t* hess_off, const double* pos, const double* mass, const int64_t* ptr,
@@ -1202,6 +1211,8 @@ int xeq_vib_project(int dtype, const void* hess, const int64_t* hess_off, const 
                     double* mass_tot, int32_t* n_tr, int32_t* rotor, double* sigma, void* stream);
 int xeq_vib_eigh(const double* mat, const int64_t* mat_off, const int64_t* val_off, const int32_t* dim, int64_t n, int max_dim,
                  double* eigenvalues, double* eigenvectors, int32_t* sweeps, int32_t* status, void* stream);
+int xeq_vib_eigh_large(const double* mat, const int64_t* mat_off, const int64_t* val_off, const int32_t* dim, int64_t n, int max_dim,
+                       double* eigenvalues, double* eigenvectors, int32_t* sweeps, int32_t* status, void* stream);
 int xeq_vib_finish(const double* eigenvalues, const double* eigenvectors, const int64_t* mat_off, const double* mass, const int64_t* ptr,
                    int64_t n_graphs, const int32_t* n_tr, const int64_t* mode_ptr, const int64_t* mode_off, double to_wavenumber, double to_kelvin,
                    double* eigenvalue, double* norm_mode, double* reduced_mass, double* freq_wavenumber, double* vib_temperature,

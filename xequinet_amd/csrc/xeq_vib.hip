@@ -1,5 +1,5 @@
 // Batched harmonic analysis behind the Hessian front (xequinet_amd/vibrations.py; the stage the reference hands to
-// pyscf at run/geometry.py:210-237).  Four kernels, all f64 whatever the Hessian's dtype, one workgroup per graph, no atomics: a graph's
+// pyscf at run/geometry.py:210-237).  Five kernels, all f64 whatever the Hessian's dtype, one workgroup per graph, no atomics: a graph's
 // result depends on no other graph of the launch and has the same bits alone and anywhere in a batch.
 //
 // k_vib_project (global memory, no size cap), per graph of n atoms, m = 3 n:
@@ -26,6 +26,10 @@
 //   cannot see below sqrt(u) |A|), before every sweep; stop at off <= m 2^-53 |A|_F, or after XEQ_VIB_MAX_SWEEPS sweeps with status 1.
 //   Output: eigenvalues ascending (equal ones by index), vector k contiguous, its largest-magnitude component (lowest index on a tie)
 //   positive.
+//
+// k_vib_eigh_large: the same contract for XEQ_VIB_MAX_DIM < m <= XEQ_VIB_LARGE_MAX_DIM (any m >= 1 is accepted), one workgroup per matrix
+//   working in the matrix's block of the output in global memory: Householder tridiagonalisation with accumulated Q, then implicit-shift
+//   QL with the rotations applied to Q^T (described at the kernel).  It reads `mat` and leaves it as it was.
 //
 // k_vib_finish: from the lowest m - n_tr eigenpairs: eigenvalue, norm_mode = m_i^-1/2 v, reduced mass 1 / sum norm_mode^2, wavenumber
 //   sign(lambda) sqrt(|lambda|) x factor (an imaginary mode negative: run/geometry.py:142), vibrational temperature, force constant,
@@ -507,6 +511,431 @@ __global__ void __launch_bounds__(VIB_THREADS) k_vib_eigh(VibEighArgs a) {
   }
 }
 
+// ---- the eigensolver above the LDS cap ---------------------------------------------------------------------------------------------
+// Smallest of one value per thread over the workgroup in a fixed tree; every thread gets it.  red: [VIB_THREADS] ints of LDS.
+__device__ __forceinline__ int vib_block_min(int v, int* red) {
+  const int t = threadIdx.x;
+  __syncthreads();   // the previous result may still be being read
+  red[t] = v;
+  __syncthreads();
+  for (int o = VIB_THREADS / 2; o > 0; o >>= 1) {
+    if (t < o) red[t] = min(red[t], red[t + o]);
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// One workgroup per matrix, working in the matrix's own [m, m] block Z of the output (global memory, L2-resident; the barriers of a
+// workgroup order its stores and loads as in k_vib_project); the tables d, e, u | c, p | s live in LDS.  Four phases:
+//  1. Z <- A, then Householder reduction to tridiagonal form from the last row up.  Step i (m - 1 .. 1) works on the leading i x i block,
+//     which is kept as a FULL symmetric matrix: x = row i (entries < i), sigma = sum_{k < i - 1} x_k^2 (the file's fixed pattern); sigma
+//     == 0 (or not > 0: a NaN): no reflector, e_{i-1} = x_{i-1} + sigma.  Else g = -sign(x_{i-1}) sqrt(sigma + x_{i-1}^2), u = x with
+//     u_{i-1} -= g, h = u.u / 2 = sigma + x_{i-1}^2 - x_{i-1} g, e_{i-1} = g; p = A u / h (thread r sums column r top to bottom:
+//     coalesced, no reduction), K = u.p / 2h, q = p - K u, A -= u q^T + q u^T, entry (j, k) as fma(u_lo, q_hi, q_lo u_hi) with lo = min(j, k),
+//     hi = max(j, k), so the block stays symmetric to the bit whatever the compiler contracts.  u stays in row i, h in Z[i][i] (d_i is in LDS).
+//  2. Q = H_{m-1} .. H_1 accumulated in place from the top-left corner (step i: the i x i block <- H_i x it, thread j owns column j:
+//     g_j = u.column / h, column -= g_j u; then row and column i of the block become those of the identity), then transposed in place:
+//     row i of Z is column i of Q.
+//  3. Implicit-shift QL on (d, e) with the running shift f (the EISPACK tql2 scheme): for l = 0 .. m - 1, tst1 = max(tst1, |d_l| + |e_l|);
+//     per iteration every thread looks for the first k >= l with |e_k| <= 2^-52 tst1 (k = m - 1 when none: e_{m-1} is never read), a
+//     fixed min tree; k == l: d_l + f is an eigenvalue.  Else lane 0 forms the shift and runs the (c, s) recurrence from k - 1 down to
+//     l into LDS, one barrier, and thread r applies all rotations of the iteration to entry r of the rows k .. l, carrying the moving
+//     row in a register.  (Every walk down the rows keeps several rows' loads in flight and a thread's up to three columns abreast:
+//     the arithmetic and its order are those written here.)  Iteration XEQ_VIB_MAX_SWEEPS + 1 of one eigenvalue sets status 1 and leaves the loops; every loop is a
+//     counted one, so a NaN (all comparisons false) ends there too; a non-finite eigenvalue gives status 1 as well.
+//  4. Ranks (ascending, equal ones by index), signs (largest-magnitude component positive, lowest index on a tie), and the rows are
+//     permuted in place along the permutation's cycles: thread r moves entry r of every row, lane 0 lists the cycles' first rows.
+// sweeps: the largest iteration count of any eigenvalue.
+constexpr int VIB_LARGE_DIM = XEQ_VIB_LARGE_MAX_DIM;
+constexpr int VIB_ROWS = 8;      // rows of a column walk a thread has in flight: one workgroup per matrix is bound by the latency of its loads
+static_assert(VIB_LARGE_DIM <= 3 * VIB_THREADS, "k_vib_eigh_large: a thread owns at most three columns");
+
+// Thread t owns the columns t, t + 256, ... of the n leading ones (t < n, NC >= ceil(n / 256)).  A column beyond n is walked as the
+// thread's first one and its result dropped, so that no load sits behind a branch.
+template <int NC>
+__device__ __forceinline__ void vib_columns(int n, int* col, bool* on) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int r = (int)threadIdx.x + c * VIB_THREADS;
+    on[c] = r < n;
+    col[c] = on[c] ? r : (int)threadIdx.x;
+  }
+}
+
+// acc[c] = sum_k Z[k][col_c] t[k] over the rows k = 0 .. n - 1, top to bottom
+template <int NC>
+__device__ __forceinline__ void vib_column_dots(const double* Z, int m, int n, const int* col, const double* t, double* acc) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+  int k = 0;
+  for (; k + VIB_ROWS <= n; k += VIB_ROWS) {
+    double z[VIB_ROWS][NC];
+#pragma unroll
+    for (int u = 0; u < VIB_ROWS; ++u)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) z[u][c] = Z[(k + u) * m + col[c]];
+#pragma unroll
+    for (int u = 0; u < VIB_ROWS; ++u) {
+      const double tk = t[k + u];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc[c] += z[u][c] * tk;
+    }
+  }
+  for (; k < n; ++k) {
+    const double tk = t[k];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] += Z[k * m + col[c]] * tk;
+  }
+}
+
+// Reduction step on the leading i x i block: p_r = (A u)_r / h into tp for the thread's columns; returns its part of u.p
+template <int NC>
+__device__ __forceinline__ double vib_reduce_products(const double* Z, int m, int i, double hh, const double* tu, double* tp) {
+  if ((int)threadIdx.x >= i) return 0.0;
+  int col[NC];
+  bool on[NC];
+  double acc[NC];
+  vib_columns<NC>(i, col, on);
+  vib_column_dots<NC>(Z, m, i, col, tu, acc);
+  double part = 0.0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (on[c]) {
+      const double pr = acc[c] / hh;
+      tp[col[c]] = pr;
+      part += tu[col[c]] * pr;
+    }
+  return part;
+}
+
+// Accumulation step: the leading i x i block <- (I - u u^T / h) x it, a thread on its own columns
+template <int NC>
+__device__ __forceinline__ void vib_reflect_columns(double* Z, int m, int i, double hh, const double* tu) {
+  if ((int)threadIdx.x >= i) return;
+  int col[NC];
+  bool on[NC];
+  double acc[NC];
+  vib_columns<NC>(i, col, on);
+  vib_column_dots<NC>(Z, m, i, col, tu, acc);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] /= hh;
+  int k = 0;
+  for (; k + VIB_ROWS <= i; k += VIB_ROWS) {
+    double z[VIB_ROWS][NC];
+#pragma unroll
+    for (int u = 0; u < VIB_ROWS; ++u)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) z[u][c] = Z[(k + u) * m + col[c]];
+#pragma unroll
+    for (int u = 0; u < VIB_ROWS; ++u) {
+      const double tk = tu[k + u];
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (on[c]) Z[(k + u) * m + col[c]] = z[u][c] - acc[c] * tk;
+    }
+  }
+  for (; k < i; ++k) {
+    const double tk = tu[k];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (on[c]) Z[k * m + col[c]] -= acc[c] * tk;
+  }
+}
+
+// One QL iteration's rotations (c_i, s_i), i = mm - 1 .. l, on the rows i, i + 1 of Q^T: a thread on its own columns, the moving row
+// in a register, the loads of four rows ahead of the stores
+template <int NC>
+__device__ __forceinline__ void vib_rotate_rows(double* Z, int m, int l, int mm, const double* tc, const double* ts) {
+  if ((int)threadIdx.x >= m) return;
+  int col[NC];
+  bool on[NC];
+  double carry[NC];
+  vib_columns<NC>(m, col, on);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) carry[c] = Z[mm * m + col[c]];
+  int i = mm - 1;
+  for (; i - 3 >= l; i -= 4) {
+    double z[4][NC];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) z[u][c] = Z[(i - u) * m + col[c]];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double cs = tc[i - u], sn = ts[i - u];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const double out = sn * z[u][c] + cs * carry[c];
+        carry[c] = cs * z[u][c] - sn * carry[c];
+        if (on[c]) Z[(i - u + 1) * m + col[c]] = out;
+      }
+    }
+  }
+  for (; i >= l; --i) {
+    const double cs = tc[i], sn = ts[i];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const double z0 = Z[i * m + col[c]];
+      const double out = sn * z0 + cs * carry[c];
+      carry[c] = cs * z0 - sn * carry[c];
+      if (on[c]) Z[(i + 1) * m + col[c]] = out;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (on[c]) Z[l * m + col[c]] = carry[c];
+}
+
+__global__ void __launch_bounds__(VIB_THREADS) k_vib_eigh_large(VibEighArgs a) {
+  __shared__ double td[VIB_LARGE_DIM], te[VIB_LARGE_DIM], tu[VIB_LARGE_DIM], tp[VIB_LARGE_DIM];
+  __shared__ double red[VIB_THREADS];
+  __shared__ int redi[VIB_THREADS], trank[VIB_LARGE_DIM], tlead[VIB_LARGE_DIM];
+  __shared__ double sh_h;
+  __shared__ int sh_n;
+  const int tid = threadIdx.x;
+  const int64_t g = blockIdx.x;
+  const int m = a.dim[g];
+  if (m <= 0 || m > a.max_dim || m > VIB_LARGE_DIM) {   // (the host checks the sizes before the launch: nothing is read or written beyond the tables)
+    if (tid == 0) {
+      a.sweeps[g] = 0;
+      a.status[g] = m == 0 ? 0 : 2;
+    }
+    return;
+  }
+  const double* src = a.mat + a.mat_off[g];
+  double* Z = a.v + a.mat_off[g];
+  for (int e = tid; e < m * m; e += VIB_THREADS) Z[e] = src[e];
+  __syncthreads();
+
+  // 1. reduction
+  for (int i = m - 1; i >= 1; --i) {
+    double* row = Z + i * m;
+    double part = 0.0;
+    for (int k = tid; k < i; k += VIB_THREADS) {
+      const double x = row[k];
+      tu[k] = x;
+      if (k < i - 1) part += x * x;
+    }
+    const double sigma = vib_block_sum(part, red);
+    const double f = tu[i - 1];
+    if (!(sigma > 0.0)) {
+      if (tid == 0) {
+        td[i] = row[i];
+        te[i - 1] = f + sigma;     // sigma is 0, or a NaN that must not be lost
+        row[i] = 0.0;
+      }
+      continue;     // (the next step writes tu below i - 1 only, and red behind a barrier)
+    }
+    const double nrm2 = sigma + f * f;
+    const double gg = -copysign(sqrt(nrm2), f);
+    const double hh = nrm2 - f * gg;
+    __syncthreads();     // every thread has read tu[i - 1]
+    if (tid == 0) {
+      td[i] = row[i];
+      te[i - 1] = gg;
+      tu[i - 1] = f - gg;
+      row[i - 1] = f - gg;
+      row[i] = hh;
+    }
+    __syncthreads();
+    part = i <= VIB_THREADS ? vib_reduce_products<1>(Z, m, i, hh, tu, tp)
+                            : (i <= 2 * VIB_THREADS ? vib_reduce_products<2>(Z, m, i, hh, tu, tp) : vib_reduce_products<3>(Z, m, i, hh, tu, tp));
+    const double kk = vib_block_sum(part, red) / (2.0 * hh);
+    for (int r = tid; r < i; r += VIB_THREADS) tp[r] -= kk * tu[r];
+    __syncthreads();
+    const uint32_t magic = (uint32_t)((1ull << 32) / (uint32_t)i) + 1u;   // e / i = umulhi(e, magic) for e i < 2^32; i >= 2 here
+    for (int e0 = tid; e0 < i * i; e0 += VIB_THREADS * VIB_BATCH) {
+      int at[VIB_BATCH];
+      double z[VIB_BATCH];
+#pragma unroll
+      for (int u = 0; u < VIB_BATCH; ++u) {
+        const int e = e0 + u * VIB_THREADS, ee = e < i * i ? e : 0;
+        const int j = (int)__umulhi((uint32_t)ee, magic), k = ee - j * i;
+        const int lo = min(j, k), hi = max(j, k);
+        at[u] = e < i * i ? j * m + k : -1;
+        z[u] = Z[j * m + k] - fma(tu[lo], tp[hi], tp[lo] * tu[hi]);
+      }
+#pragma unroll
+      for (int u = 0; u < VIB_BATCH; ++u)
+        if (at[u] >= 0) Z[at[u]] = z[u];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    td[0] = Z[0];
+    te[m - 1] = 0.0;
+    Z[0] = 1.0;
+  }
+  __syncthreads();
+
+  // 2. Q, then Q^T
+  for (int i = 1; i < m; ++i) {
+    double* row = Z + i * m;
+    const double hh = row[i];
+    if (hh > 0.0) {
+      for (int k = tid; k < i; k += VIB_THREADS) tu[k] = row[k];
+      __syncthreads();
+      if (i <= VIB_THREADS) vib_reflect_columns<1>(Z, m, i, hh, tu);
+      else if (i <= 2 * VIB_THREADS) vib_reflect_columns<2>(Z, m, i, hh, tu);
+      else vib_reflect_columns<3>(Z, m, i, hh, tu);
+    }
+    __syncthreads();     // h and u have been read, the columns are complete
+    for (int k = tid; k < i; k += VIB_THREADS) {
+      row[k] = 0.0;
+      Z[k * m + i] = 0.0;
+    }
+    if (tid == 0) row[i] = 1.0;
+    __syncthreads();
+  }
+  if (m > 1) {
+    const uint32_t magic = (uint32_t)((1ull << 32) / (uint32_t)m) + 1u;
+    for (int e = tid; e < m * m; e += VIB_THREADS) {
+      const int r = (int)__umulhi((uint32_t)e, magic), c = e - r * m;
+      if (r < c) {
+        const double x = Z[r * m + c], y = Z[c * m + r];
+        Z[r * m + c] = y;
+        Z[c * m + r] = x;
+      }
+    }
+  }
+  __syncthreads();
+
+  // 3. QL
+  int sweeps = 0, status = 0;
+  double fshift = 0.0, tst1 = 0.0;
+  for (int l = 0; l < m && status == 0; ++l) {
+    tst1 = fmax(tst1, fabs(td[l]) + fabs(te[l]));
+    int iter = 0;
+    while (true) {     // at most XEQ_VIB_MAX_SWEEPS + 1 passes: a pass ends the loop or counts one iteration
+      const double thr = 0x1p-52 * tst1;
+      int cand = m - 1;
+      for (int k = l + tid; k < m - 1; k += VIB_THREADS)
+        if (fabs(te[k]) <= thr) {
+          cand = k;
+          break;
+        }
+      const int mm = vib_block_min(cand, redi);
+      if (mm == l) break;
+      if (iter == XEQ_VIB_MAX_SWEEPS) {
+        status = 1;
+        break;
+      }
+      ++iter;
+      if (tid == 0) {
+        const double el = te[l], g0 = td[l], el1 = te[l + 1];
+        double p = (td[l + 1] - g0) / (2.0 * el);
+        double r = hypot(p, 1.0);
+        const double pr = p + copysign(r, p);
+        const double dl = el / pr, dl1 = el * pr, h = g0 - dl;
+        td[l] = dl;
+        td[l + 1] = dl1;
+        p = mm >= l + 2 ? td[mm] - h : td[mm];     // the entries l + 2 .. mm take the shift as they are read, those above mm below
+        double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
+        for (int i = mm - 1; i >= l; --i) {
+          c3 = c2;
+          c2 = c;
+          s2 = s;
+          const double ei = te[i], di = i >= l + 2 ? td[i] - h : td[i];
+          const double ce = c * ei, cp = c * p;
+          r = hypot(p, ei);
+          te[i + 1] = s * r;
+          s = ei / r;
+          c = p / r;
+          p = c * di - s * ce;
+          td[i + 1] = cp + s * (c * ce + s * di);
+          tu[i] = c;
+          tp[i] = s;
+        }
+        p = -s * s2 * c3 * el1 * el / dl1;
+        te[l] = s * p;
+        td[l] = c * p;
+        sh_h = h;
+      }
+      __syncthreads();
+      const double h = sh_h;
+      fshift += h;
+      for (int k = mm + 1 + tid; k < m; k += VIB_THREADS) td[k] -= h;
+      if (m <= VIB_THREADS) vib_rotate_rows<1>(Z, m, l, mm, tu, tp);
+      else if (m <= 2 * VIB_THREADS) vib_rotate_rows<2>(Z, m, l, mm, tu, tp);
+      else vib_rotate_rows<3>(Z, m, l, mm, tu, tp);
+      __syncthreads();
+    }
+    sweeps = max(sweeps, iter);
+    if (tid == 0) td[l] += fshift;
+  }
+
+  // 4. order, signs, output
+  __syncthreads();     // lane 0's last d_l + f
+  double bad = 0.0;
+  for (int k = tid; k < m; k += VIB_THREADS)
+    if (!isfinite(td[k])) bad = 1.0;
+  if (vib_block_sum(bad, red) > 0.0) status = 1;
+  double* sgn = tu;       // [m]
+  double* seen = tp;      // [m]
+  for (int k = tid; k < m; k += VIB_THREADS) {
+    const double d = td[k];
+    int r = 0;
+    for (int j = 0; j < m; ++j) {
+      const double dj = td[j];
+      r += (dj < d || (dj == d && j < k)) ? 1 : 0;
+    }
+    double best = -1.0, at = 0.0;
+    for (int j0 = 0; j0 < m; j0 += VIB_ROWS) {
+      double v[VIB_ROWS];
+#pragma unroll
+      for (int u = 0; u < VIB_ROWS; ++u) v[u] = Z[k * m + min(j0 + u, m - 1)];     // (the last entry again: never larger than itself)
+#pragma unroll
+      for (int u = 0; u < VIB_ROWS; ++u)
+        if (fabs(v[u]) > best) {
+          best = fabs(v[u]);
+          at = v[u];
+        }
+    }
+    if (status != 0) r = k;     // not a spectrum: the rows stay where they are
+    trank[k] = r;
+    sgn[k] = at < 0.0 ? -1.0 : 1.0;
+    seen[k] = 0.0;
+    a.w[a.val_off[g] + r] = d;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int k = 0; k < m; ++k) {
+      if (seen[k] != 0.0) continue;
+      tlead[n++] = k;
+      int j = k;
+      for (int c = 0; c < m && seen[j] == 0.0; ++c) {
+        seen[j] = 1.0;
+        j = trank[j];
+      }
+    }
+    sh_n = n;
+  }
+  __syncthreads();
+  const int n_cycles = sh_n;
+  for (int c = tid; c < m; c += VIB_THREADS)
+    for (int q = 0; q < n_cycles; ++q) {
+      const int k0 = tlead[q];
+      int j = k0;
+      double val = sgn[j] * Z[j * m + c];     // row j, on its way to row trank[j]
+      for (int n = 0; n < m; ++n) {
+        const int t = trank[j];
+        if (t == k0) {
+          Z[k0 * m + c] = val;
+          break;
+        }
+        const double next = sgn[t] * Z[t * m + c];
+        Z[t * m + c] = val;
+        val = next;
+        j = t;
+      }
+    }
+  if (tid == 0) {
+    a.sweeps[g] = sweeps;
+    a.status[g] = status;
+  }
+}
+
 // ---- modes, frequencies, thermochemistry sums --------------------------------------------------------------------------------------
 struct VibFinishArgs {
   const double* w;           // eigenvalues, graph g at 3 ptr[g]
@@ -619,6 +1048,21 @@ int xeq_vib_eigh(const double* mat, const int64_t* mat_off, const int64_t* val_o
   VibEighArgs a{mat, mat_off, val_off, dim, max_dim, eigenvalues, eigenvectors, sweeps, status};
   hipLaunchKernelGGL(k_vib_eigh, dim3((unsigned)n), dim3(VIB_THREADS), shmem, (hipStream_t)stream, a);
   XEQ_CHECK_LAUNCH("xeq_vib_eigh");
+  return XEQ_OK;
+}
+
+int xeq_vib_eigh_large(const double* mat, const int64_t* mat_off, const int64_t* val_off, const int32_t* dim, int64_t n, int max_dim,
+                       double* eigenvalues, double* eigenvectors, int32_t* sweeps, int32_t* status, void* stream) {
+  XEQ_CHECK_ARG(max_dim >= 0 && max_dim <= XEQ_VIB_LARGE_MAX_DIM,
+                "xeq_vib_eigh_large: dimension %d is beyond XEQ_VIB_LARGE_MAX_DIM = %d (one workgroup per matrix is the wrong shape above it)", max_dim,
+                XEQ_VIB_LARGE_MAX_DIM);
+  XEQ_CHECK_ARG(n >= 0 && n <= 0x7fffffff, "xeq_vib_eigh_large: n %lld", (long long)n);
+  XEQ_CHECK_ARG(n == 0 || (mat_off && val_off && dim && sweeps && status), "xeq_vib_eigh_large: null buffer");
+  XEQ_CHECK_ARG(n == 0 || max_dim == 0 || (mat && eigenvalues && eigenvectors), "xeq_vib_eigh_large: null matrix buffer");
+  if (n == 0) return XEQ_OK;
+  VibEighArgs a{mat, mat_off, val_off, dim, max_dim, eigenvalues, eigenvectors, sweeps, status};
+  hipLaunchKernelGGL(k_vib_eigh_large, dim3((unsigned)n), dim3(VIB_THREADS), 0, (hipStream_t)stream, a);
+  XEQ_CHECK_LAUNCH("xeq_vib_eigh_large");
   return XEQ_OK;
 }
 

@@ -23,6 +23,7 @@ MD_NVE, MD_LANGEVIN, MD_BERENDSEN, MD_PURPOSE_LANGEVIN, MD_PURPOSE_MAXWELL = 0, 
 NPT_BOX, NPT_CELL, NPT_INV, NPT_CELL_NEXT, NPT_INV_NEXT, NPT_MU, NPT_P, NPT_V = 40, 0, 9, 18, 27, 36, 37, 38      # XEQ_NPT_* of include/xeq.h (md.py)
 FIRE_FRESH, FIRE_ACTIVE, FIRE_CONVERGED = 0, 1, 2      # XEQ_FIRE_* of include/xeq.h
 VIB_MAX_DIM, VIB_MAX_SWEEPS = 96, 30     # XEQ_VIB_MAX_DIM, XEQ_VIB_MAX_SWEEPS of include/xeq.h (vibrations.py)
+VIB_LARGE_MAX_DIM = 768              # XEQ_VIB_LARGE_MAX_DIM: the cap of xeq_vib_eigh_large
 VIB_ROTORS = ("atom", "linear", "nonlinear")      # XEQ_VIB_ATOM, _LINEAR, _NONLINEAR
 SB_ACCUM_VEC = 16        # XEQ_SB_ACCUM_VEC of include/xeq.h: xeq_message_bwd_sb adds dL/dvec to the buffer it is handed
 XHAT_HIGHER_L_ZERO = 2   # XEQ_XHAT_HIGHER_L_ZERO of include/xeq.h: hint bit on the xhat_layout argument of the wq message kernels
@@ -280,6 +281,7 @@ _PROTOS = {
     "xeq_fire_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(FireParams), _R(ResRecorder), _P],
     "xeq_vib_project": [c_int, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "xeq_vib_eigh": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],
+    "xeq_vib_eigh_large": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],
     "xeq_vib_finish": [_P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P],
     "xeq_vib_thermo_sums": [_P, _P, _P, c_int64, c_double, _P, _P],
 }

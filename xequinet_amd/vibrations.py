@@ -6,11 +6,14 @@ The reference's ``--freq`` path (run/geometry.py:210-237) hands one Hessian at a
     xeq_vib_project   centre of mass, principal moments, rotor class, the orthonormal rigid-body basis Q [n_tr, 3 n] and
                       M = P Hmw P + sigma Q Q^T  (Hmw the mass-weighted symmetrised Hessian, P = I - Q Q^T, sigma = 2 |P Hmw P|_F)
     xeq_vib_eigh      all eigenpairs of every M with 3 n <= 96, one workgroup per graph, LDS-resident cyclic Jacobi in f64
+    xeq_vib_eigh_large  (``large="kernel"`` only) all eigenpairs of every M with 96 < 3 n <= 768 in one more launch, one workgroup per
+                      graph in the graph's block of global memory: Householder tridiagonalisation, then implicit-shift QL, in f64
     xeq_vib_finish    the lowest 3 n - n_tr eigenpairs as modes, wavenumbers, reduced masses, vibrational temperatures, force constants
 
 The shift sigma puts the n_tr rigid-body directions at the top of M's spectrum, so the vibrations are the lowest 3 n - n_tr eigenpairs
 and are never picked by overlap.  Graphs with 3 n > 96 take the same M through ``torch.linalg.eigh`` in f64 on the device (``solver``
-"tensor").  Every kernel runs one workgroup per graph in f64 with fixed summation orders: a graph's result has the same bits alone and
+"tensor"), one call per graph; with ``large="kernel"`` those up to 3 n = 768 (256 atoms) take xeq_vib_eigh_large instead (``solver``
+"large") and only the graphs above that stay with the tensor solver.  Every kernel runs one workgroup per graph in f64 with fixed summation orders: a graph's result has the same bits alone and
 anywhere in a batch.  ``thermo`` adds one launch (xeq_vib_thermo_sums) and elementwise tensor arithmetic.  There is no CPU fallback.
 
 Units.  ``masses`` are in amu, the Hessian in energy / length^2 of the model's units; an eigenvalue is in energy / (length^2 amu) and
@@ -48,7 +51,8 @@ def unit_factors(energy_unit: str, length_unit: str) -> Dict[str, float]:
 @dataclass
 class HarmonicResult:
     """Flat ragged f64 tensors on the device; graph g's modes are the rows ``mode_ptr[g] : mode_ptr[g + 1]``.  ``rotor``: 0 atom,
-    1 linear, 2 nonlinear (``lib.VIB_ROTORS``); ``solver[g]``: "kernel" or "tensor"; ``sigma``: the shift of M."""
+    1 linear, 2 nonlinear (``lib.VIB_ROTORS``); ``solver[g]``: "kernel", "large" or "tensor"; ``sigma``: the shift of M; ``sweeps``:
+    Jacobi sweeps ("kernel"), the most QL iterations any one eigenvalue took ("large"), 0 ("tensor")."""
     eigenvalue: torch.Tensor            # [K] energy / (length^2 amu)
     freq_wavenumber: torch.Tensor       # [K] cm^-1, an imaginary mode negative
     vib_temperature: torch.Tensor       # [K] kelvin
@@ -118,11 +122,16 @@ def _sizes_of(hessians: Sequence[torch.Tensor]) -> List[int]:
 
 
 def harmonic_analysis(hessians: Sequence[torch.Tensor], pos: torch.Tensor, masses: torch.Tensor, ptr=None, *, periodic: bool = False,
-                      energy_unit: Optional[str] = None, length_unit: Optional[str] = None) -> HarmonicResult:
+                      energy_unit: Optional[str] = None, length_unit: Optional[str] = None, large: str = "tensor") -> HarmonicResult:
     """Frequencies, normal modes and reduced masses of every graph of a batch.  ``hessians``: the list ``hessian()`` returns (f32 or
     f64, read as given and widened to f64); ``pos`` [N, 3]; ``masses`` [N] float64 in amu; ``ptr`` [G + 1] (None: from the blocks'
-    sizes; a ``ptr`` on the device is read back at the front to be checked against them); ``periodic``: translations only are removed.  Units default to ``utils.get_default_units()``.  One host read at the end
+    sizes; a ``ptr`` on the device is read back at the front to be checked against them); ``periodic``: translations only are removed.  Units default to ``utils.get_default_units()``.
+    ``large``: the solver of the graphs with ``lib.VIB_MAX_DIM < 3 n <= lib.VIB_LARGE_MAX_DIM``: "tensor" (one ``torch.linalg.eigh`` per
+    graph) or "kernel" (all of them in one xeq_vib_eigh_large launch, longest first; faster for a batch, slower for one big matrix:
+    profiles/vib_large_timing.txt); graphs above the larger cap take the tensor solver either way.  One host read at the end
     raises ``FloatingPointError`` naming the graphs whose eigensolver did not converge (and ``ValueError`` for a mass <= 0)."""
+    if large not in ("tensor", "kernel"):
+        raise ValueError(f"harmonic_analysis: large must be 'tensor' or 'kernel', got {large!r}")
     sizes = _sizes_of(hessians)
     G, N = len(sizes), sum(sizes)
     if not torch.is_tensor(pos) or pos.dim() != 2 or tuple(pos.shape) != (N, 3) or not pos.is_floating_point():
@@ -163,7 +172,7 @@ def harmonic_analysis(hessians: Sequence[torch.Tensor], pos: torch.Tensor, masse
     sweeps, status = torch.zeros(G, **i32), torch.zeros(G, **i32)
     moments, axes = torch.zeros((G, 3), **f64), torch.zeros((G, 9), **f64)
     mass_tot, sigma = torch.zeros(G, **f64), torch.zeros(G, **f64)
-    solver = ["kernel" if m <= lib.VIB_MAX_DIM else "tensor" for m in dims]
+    solver = ["kernel" if m <= lib.VIB_MAX_DIM else ("large" if large == "kernel" and m <= lib.VIB_LARGE_MAX_DIM else "tensor") for m in dims]
     empty = HarmonicResult(**out, mode_ptr=torch.zeros(G + 1, **i64), ptr=atom_ptr, n_tr=n_tr, rotor=rotor, moments=moments, mass_tot=mass_tot,
                            n_imaginary=n_imag, sweeps=sweeps, status=status, sigma=sigma, solver=solver, periodic=bool(periodic),
                            energy_unit=energy_unit, length_unit=length_unit, mode_ptr_host=[0] * (G + 1), mode_off_host=[0] * (G + 1))
@@ -198,8 +207,15 @@ def harmonic_analysis(hessians: Sequence[torch.Tensor], pos: torch.Tensor, masse
         call("xeq_vib_eigh", _p(mat), _p(sel_mat), _p(sel_val), _p(sel_dim), len(small), max(dims[g] for g in small), _p(val), _p(vec), _p(sw), _p(st), s)
         if len(small) != G:
             sweeps[idx], status[idx] = sw, st
+    big = sorted((g for g in range(G) if solver[g] == "large"), key=lambda g: -dims[g])      # longest first (equal ones in batch order)
+    if big:
+        idx = torch.tensor(big, **i64)
+        sel_mat, sel_val, sel_dim = mat_off_d[idx].contiguous(), (3 * host[2])[idx].contiguous(), dims_d[idx].to(torch.int32)
+        sw, st = torch.zeros(len(big), **i32), torch.zeros(len(big), **i32)
+        call("xeq_vib_eigh_large", _p(mat), _p(sel_mat), _p(sel_val), _p(sel_dim), len(big), dims[big[0]], _p(val), _p(vec), _p(sw), _p(st), s)
+        sweeps[idx], status[idx] = sw, st
     for g, m in enumerate(dims):
-        if m <= lib.VIB_MAX_DIM:
+        if solver[g] != "tensor":
             continue
         w, V = torch.linalg.eigh(mat[mat_off[g] : mat_off[g + 1]].view(m, m))      # the tensor solver: the same M, f64, on the device
         Vt = V.t().contiguous()
@@ -224,7 +240,7 @@ def harmonic_analysis(hessians: Sequence[torch.Tensor], pos: torch.Tensor, masse
     failed = [g for g in range(G) if back[g] != 0]
     if failed:
         raise FloatingPointError(f"harmonic_analysis: the eigensolver did not converge within {lib.VIB_MAX_SWEEPS} sweeps for the graphs {failed} "
-                                 "(a non-finite Hessian entry gives this too)")
+                                 "(Jacobi sweeps of a matrix, or QL iterations of one eigenvalue; a non-finite Hessian entry gives this too)")
     mp, mo = [0], [0]
     for g, m in enumerate(dims):
         kg = m - back[G + g]
