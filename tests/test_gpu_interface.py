@@ -482,7 +482,7 @@ def test_native_operator_never_reuses_the_weight_packs_of_a_dead_model():
 
 def test_replay_follows_a_weight_update():
     """A captured graph reads packed weight copies made at capture time; an in-place update of the parameters drops the graphs
-    (runtime.GraphedModel._parameter_state), so replay and the eager model keep agreeing."""
+    (runtime._Weights, which GraphedModel inherits), so replay and the eager model keep agreeing."""
     from xequinet_amd import runtime
     from xequinet_amd.data import NeighborTransform, XequiBatch, synthetic as syn
     from xequinet_amd.nn import resolve_model

@@ -15,7 +15,7 @@ import torch
 
 from . import keys, lib, ops
 from .lib import call, dtype_code, require_hip
-from .runtime import GraphedStep, GraphedStepPBC, pair_capacity
+from .runtime import GraphedStep, GraphedStepPBC, module_of, pair_capacity
 
 
 def chunk_tables(ptr_host, chunk: int = lib.MD_CHUNK):
@@ -52,7 +52,7 @@ class ResidentDriver:
             raise ValueError(f"{who}: a periodic system is ONE graph (GraphedStepPBC)")
         self.ptr_host = ptr_host
         self.n_atoms, self.n_graphs = N, len(ptr_host) - 1
-        cutoff = float((model if isinstance(model, torch.nn.Module) else model.model).cutoff_radius)
+        cutoff = float(module_of(model).cutoff_radius)
         if self.periodic:
             cell_h = np.asarray(cell.detach().double().cpu().numpy()).reshape(3, 3)
             if edge_capacity is None:       # from the density; a list that outgrows it is met by the restore protocol

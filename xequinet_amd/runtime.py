@@ -15,11 +15,67 @@ many frames only at small cutoffs; batches of recurring shapes always do).
 from __future__ import annotations
 
 from collections import OrderedDict
+from contextlib import contextmanager, nullcontext
 from typing import Dict, Optional
 
 import torch
 
 from . import keys, lib, ops
+
+
+def module_of(model):
+    """The ``torch.nn.Module`` behind ``model``: itself, or what a plain callable around a module (md_model._Core) holds in ``.model``."""
+    m = model
+    while not isinstance(m, torch.nn.Module) and hasattr(m, "model"):
+        m = m.model
+    return m
+
+
+def _capture(body, warmup: int, warm=None, keep=(), scope=None, pool=None):
+    """``warmup`` runs of ``warm`` (default: ``body``) on a side stream, off the capture -- lazy initialisation, the pack kernels, GEMM
+    selection under ``scope`` -- then ``body`` captured as a HIP graph (in the memory pool ``pool``, if given) -> (graph, what ``body``
+    returned).  The warm-up runs are not steps: the tensors in ``keep`` (the steps' edge counters) are put back behind them."""
+    if warmup:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with (nullcontext() if scope is None else scope), torch.cuda.stream(side):
+            kept = [t.clone() for t in keep]
+            for _ in range(warmup):
+                (body if warm is None else warm)()
+            for t, k in zip(keep, kept):
+                t.copy_(k)
+        torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    # thread-local capture mode: HIP calls of other host threads (RCCL's watchdog in a multi-rank job) do not
+    # invalidate the capture
+    with torch.cuda.graph(graph, pool=pool, capture_error_mode="thread_local"):
+        outputs = body()
+    return graph, outputs
+
+
+class _Weights:
+    """What every class that holds captured graphs knows about the model's weights.  A captured graph reads the matrix-core kernels'
+    PACKED weight copies of the moment it was captured (the pack kernels ran in the warm-up, outside the graph) next to the live tensors
+    the library GEMMs read: after an in-place update (optimizer step, load_state_dict, a replayed captured training step) a replay would
+    mix old and new weights, so the graphs are dropped and captured again."""
+
+    def _track_weights(self, model) -> None:
+        """In ``__init__``.  The tensor list is taken once (walking the module tree costs more than a small evaluation); replacing
+        parameter OBJECTS of a captured model needs a new object."""
+        m = module_of(model)
+        self._tracked = (list(m.parameters()) + list(m.buffers())) if isinstance(m, torch.nn.Module) else []
+        self._param_state = self._weights_key()
+
+    def _weights_key(self) -> tuple:
+        """Version counters of every parameter / buffer plus the pack epoch (include/xeq.h)."""
+        return tuple([t._version for t in self._tracked]) + (lib.pack_epoch(),)
+
+    def _weights_moved(self) -> bool:
+        """Whether the key moved since the last call (or the construction): the caller drops its graphs."""
+        state = self._weights_key()
+        moved = state != self._param_state
+        self._param_state = state
+        return moved
 
 
 class _Captured:
@@ -39,9 +95,7 @@ class _Captured:
 def refuse_electronic(model, who: str) -> None:
     """The whole-step and capacity-sized capture classes take no charge / spin input: a model with a charge or spin embedding
     (nn/electronic.py) would silently evaluate the neutral, spin-free molecule there, so it is refused."""
-    m = model
-    while not isinstance(m, torch.nn.Module) and hasattr(m, "model"):    # a plain callable around a module (md_model._Core)
-        m = m.model
+    m = module_of(model)
     if isinstance(m, torch.nn.Module):
         from .nn.electronic import ChargeEmbedding, SpinEmbedding
         from .nn.model import PaiNN
@@ -56,7 +110,7 @@ def refuse_electronic(model, who: str) -> None:
                              "(use GraphedModel, which captures data['charge'] / data['spin'], or the eager model)")
 
 
-class GraphedModel:
+class GraphedModel(_Weights):
     """``GraphedModel(model)(data) -> {energy, atomic_energies, forces[, virial]}`` with HIP-graph replay.
 
     ``data`` is the dict the model takes (``XequiBatch.to_dict()`` after ``NeighborTransform``); it must carry
@@ -90,23 +144,10 @@ class GraphedModel:
         self.warmup = warmup
         self._cache: "OrderedDict[tuple, _Captured]" = OrderedDict()
         self.captures = 0
-        self._tracked = None
-        self._param_state = self._parameter_state()
+        self.captures_same_list = 0      # captures of the graph without the walk-plan rebuild (reuse_unchanged_topology)
+        self._track_weights(model)
 
     # ------------------------------------------------------------------ helpers
-    def _parameter_state(self) -> tuple:
-        """Version counters of every parameter / buffer.  A captured graph reads the matrix-core kernels' PACKED weight copies
-        (made when the graph was captured) next to the live tensors the library GEMMs read: after an in-place update
-        (optimizer step, load_state_dict) a replay would mix old and new weights, so the graphs are dropped and re-captured.
-        The tensor list is taken once (walking the module tree costs more than a small evaluation); replacing parameter
-        OBJECTS of a captured model needs a new GraphedModel."""
-        if self._tracked is None:
-            m = self.model
-            while not isinstance(m, torch.nn.Module) and hasattr(m, "model"):    # a plain callable around a module (md_model._Core)
-                m = m.model
-            self._tracked = (list(m.parameters()) + list(m.buffers())) if isinstance(m, torch.nn.Module) else []
-        return tuple([t._version for t in self._tracked]) + (lib.pack_epoch(),)
-
     def _signature(self, data, eg: ops.EdgeGraph) -> tuple:
         pos = data[keys.POSITIONS]
         sig = (tuple(pos.shape), pos.dtype, pos.device.index, int(data[keys.EDGE_INDEX].shape[1]),
@@ -156,20 +197,14 @@ class GraphedModel:
         # library GEMM selection is timed during the warm-up only: TunableOp is a process-wide switch, so the state the
         # host application had is restored afterwards (selections made here stay cached inside the libraries' wrapper)
         from .tuning import gemm_autotune_scope
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with gemm_autotune_scope(self.tune_gemms), torch.cuda.stream(side):   # warm-up off the capture: GEMM selection, lazy init
-            for _ in range(self.warmup):
-                self._run(static)
-        torch.cuda.current_stream().wait_stream(side)
-        c.graph = torch.cuda.CUDAGraph()
-        # thread-local capture mode: HIP calls of other host threads (RCCL's watchdog in a multi-rank job) do not
-        # invalidate the capture
-        with torch.cuda.graph(c.graph, capture_error_mode="thread_local"):
+
+        def with_plans():
             # the walk plans / stream tables of the message kernels depend on the neighbour list only; rebuilding them is part of
             # the replayed graph (fixed sizes, in place over the static CSR arrays), not a dozen host launches in front of it
             c.edge_graph.refresh_plans()
-            c.outputs = self._run(static)
+            return self._run(static)
+
+        c.graph, c.outputs = _capture(with_plans, self.warmup, warm=lambda: self._run(static), scope=gemm_autotune_scope(self.tune_gemms))
         self.captures += 1
         return c
 
@@ -194,11 +229,9 @@ class GraphedModel:
 
     # --------------------------------------------------------------------- call
     def __call__(self, data: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        state = self._parameter_state()
-        if state != self._param_state:      # weights changed since the graphs were captured
+        if self._weights_moved():           # weights changed since the graphs were captured
             self._cache.clear()
             self._last = None
-            self._param_state = state
         c = self._last
         if (self.reuse_unchanged_topology and c is not None and keys.EDGE_GRAPH not in data
                 and self._same_topology(c, data)):
@@ -206,10 +239,8 @@ class GraphedModel:
             # graph replayed is the one WITHOUT the plan rebuild (eight launches at the sizes that take the wq kernels)
             ops.copy_many([(t, data[k]) for k, t in c.inputs.items() if k in data and k != keys.EDGE_INDEX])
             if c.graph_same is None:
-                c.graph_same = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(c.graph_same, pool=c.graph.pool(), capture_error_mode="thread_local"):
-                    c.outputs_same = self._run(c.static)
-                self.captures_same_list = getattr(self, "captures_same_list", 0) + 1
+                c.graph_same, c.outputs_same = _capture(lambda: self._run(c.static), 0, pool=c.graph.pool())   # (warmed up by the first graph)
+                self.captures_same_list += 1
             c.graph_same.replay()
             return c.outputs_same
         eg = self._edge_graph(data)
@@ -246,19 +277,6 @@ class GraphedModel:
 
 
 # ----------------------------------------------------------------------------------------------- whole step as one graph
-def _params_state(step) -> tuple:
-    """Version counters of the model's parameters and buffers plus the pack epoch (include/xeq.h): a captured graph holds the packed
-    weight copies of the moment it was captured (the pack kernels ran in the warm-up, outside the graph), so a step object
-    re-captures when any of them moved (optimizer step, load_state_dict, a replayed captured training step)."""
-    tracked = getattr(step, "_tracked_params", None)
-    if tracked is None:
-        m = step.model
-        while not isinstance(m, torch.nn.Module) and hasattr(m, "model"):
-            m = m.model
-        tracked = step._tracked_params = (list(m.parameters()) + list(m.buffers())) if isinstance(m, torch.nn.Module) else []
-    return tuple([t._version for t in tracked]) + (lib.pack_epoch(),)
-
-
 def pair_capacity(ptr_host) -> int:
     """Upper bound of an open-boundary neighbour list: every ordered pair inside a graph, sum_g n_g (n_g - 1)."""
     import numpy as np
@@ -267,23 +285,43 @@ def pair_capacity(ptr_host) -> int:
     return int((n * (n - 1)).sum())
 
 
-def _offer_zero_start(step, data) -> None:
-    """A static all-zero start buffer for the equivariant features (nn/xpainn.py, ZERO_EQUIVARIANT): the model's embedding takes it
-    instead of filling 36 MB of zeros per evaluation.  Only for models whose embedding says how wide it is."""
-    from .nn.xpainn import ZERO_EQUIVARIANT
+class _WholeStep(_Weights):
+    """What ``GraphedStep`` and ``GraphedStepPBC`` share: ONE captured graph of ``_step()`` over the object's static buffers, captured on
+    first use and again when the weights moved (or the subclass dropped ``graph``), and the static zero start buffer.  A subclass sets
+    ``model``, ``n_atoms``, ``pos``, ``warmup`` and ``_keep`` (the tensors a warm-up run must leave as they were) before ``_init_graph``."""
 
-    net = step.model if isinstance(step.model, torch.nn.Module) else getattr(step.model, "model", None)
-    mods = getattr(net, "mods", None)
-    emb = mods["embedding"] if (mods is not None and "embedding" in mods) else None
-    if emb is None or not hasattr(emb, "node_irreps"):
-        return
-    zero = getattr(step, "_zero_x", None)
-    if zero is None:
-        zero = step._zero_x = torch.zeros((step.n_atoms, emb.node_irreps.dim), dtype=step.pos.dtype, device=step.pos.device)
-    data[ZERO_EQUIVARIANT] = zero
+    _keep = ()
+
+    def _init_graph(self) -> None:
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.outputs: Dict[str, torch.Tensor] = {}
+        self.captures = 0
+        self._track_weights(self.model)
+        # a static all-zero start buffer for the equivariant features (nn/xpainn.py, ZERO_EQUIVARIANT): the model's embedding takes it
+        # instead of filling 36 MB of zeros per evaluation.  Only for models whose embedding says how wide it is.
+        mods = getattr(module_of(self.model), "mods", None)
+        emb = mods["embedding"] if (mods is not None and "embedding" in mods) else None
+        self._zero_x = (torch.zeros((self.n_atoms, emb.node_irreps.dim), dtype=self.pos.dtype, device=self.pos.device)
+                        if hasattr(emb, "node_irreps") else None)
+
+    def _offer_zero_start(self, data) -> None:
+        from .nn.xpainn import ZERO_EQUIVARIANT
+
+        if self._zero_x is not None:
+            data[ZERO_EQUIVARIANT] = self._zero_x
+
+    def replay(self) -> None:
+        """The step on whatever the static buffers hold (md.Dynamics writes positions there itself); results in ``outputs``.  Captured
+        on first use (and again when the weights moved: the capture's packed copies are stale), replayed after."""
+        if self._weights_moved():
+            self.graph = None
+        if self.graph is None:
+            self.graph, self.outputs = _capture(self._step, self.warmup, keep=self._keep)
+            self.captures += 1
+        self.graph.replay()
 
 
-class GraphedStep:
+class GraphedStep(_WholeStep):
     """Neighbour list + model as ONE captured HIP graph that does not depend on the edge count (open boundaries).
 
     ``GraphedModel`` replays the model per (atoms, edges) signature and leaves the neighbour list outside the graph, because the
@@ -317,15 +355,13 @@ class GraphedStep:
         self.ptr = torch.zeros(G + 1, dtype=torch.int64, device=dev)
         self.batch = torch.zeros(N, dtype=torch.int64, device=dev)
         self.edge_index = torch.zeros((2, max(E, 1)), dtype=torch.int64, device=dev)   # zero = a valid node id in every unused slot
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.outputs: Dict[str, torch.Tensor] = {}
         self.rowptr: Optional[torch.Tensor] = None
         self.warmup = warmup
-        self.captures = 0
-        self._param_state = None
         # edges of every step run so far (true counts), accumulated on the device inside the step's own launches: what a benchmark
         # reads once behind its timed region (zero it in front)
         self.edge_total = torch.zeros(1, dtype=torch.int64, device=self.pos.device)
+        self._keep = (self.edge_total,)                      # the warm-up runs are not steps: they leave the edge counter alone
+        self._init_graph()
 
     def overflowed(self) -> bool:
         """Whether the last step's neighbour list outgrew the edge capacity (reads the device-side count: a synchronisation).  Such a
@@ -339,7 +375,7 @@ class GraphedStep:
         eg = ops.EdgeGraph(self.edge_index, self.n_atoms, center_sorted=True, ptr=self.ptr, c_rowptr=rowptr, symmetric=True)
         data = {keys.POSITIONS: self.pos.detach(), keys.ATOMIC_NUMBERS: self.z, keys.EDGE_INDEX: self.edge_index, keys.BATCH: self.batch,
                 keys.BATCH_PTR: self.ptr, keys.EDGE_GRAPH: eg}
-        _offer_zero_start(self, data)
+        self._offer_zero_start(data)
         with torch.enable_grad():
             out = self.model(data, compute_forces=self.compute_forces, compute_virial=False)
         res = {k: v.detach() for k, v in out.items() if isinstance(v, torch.Tensor)}
@@ -378,31 +414,6 @@ class GraphedStep:
         call("xeq_load_padded_batch_z64" if z64 else "xeq_load_padded_batch", dtype_code(pos_c), p_(pos_c), p_(z_c), p_(ptr_c), p_(batch_c), n, g, self.n_atoms, self.n_graphs,
              1.0e4, self.PAD_SPACING, p_(self.pos), p_(self.z), p_(self.ptr), p_(self.batch), stream())
 
-    def _replay(self) -> None:
-        """The step on whatever the static buffers hold: captured on first use (and again when the weights moved), replayed after."""
-        state = _params_state(self)
-        if self.graph is not None and state != self._param_state:   # weights moved since the capture: its packed copies are stale
-            self.graph = None
-        self._param_state = state
-        if self.graph is None:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                counted = self.edge_total.clone()
-                for _ in range(self.warmup):
-                    self._step()
-                self.edge_total.copy_(counted)                  # the warm-up runs are not steps: they leave the edge counter alone
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.outputs = self._step()
-            self.captures += 1
-        self.graph.replay()
-
-    def replay(self) -> None:
-        """The step on whatever the static buffers hold (md.Dynamics writes positions there itself); results in ``outputs``."""
-        self._replay()
-
     def __call__(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, ptr: torch.Tensor, batch: Optional[torch.Tensor] = None,
                  ptr_host=None) -> Dict[str, torch.Tensor]:
         """-> {energy [G], atomic_energies [n], forces [n, 3], n_edges [1] (device)}: views of the graph's output buffers,
@@ -410,7 +421,7 @@ class GraphedStep:
         if ptr_host is not None and pair_capacity(ptr_host) > self.n_edges:
             raise ValueError(f"GraphedStep: the batch may hold {pair_capacity(ptr_host)} edges, the capacity is {self.n_edges}")
         self._load(pos, atomic_numbers, ptr, batch)
-        self._replay()
+        self.replay()
         n, g = int(pos.shape[0]), int(ptr.numel() - 1)
         out = {keys.TOTAL_ENERGY: self.outputs[keys.TOTAL_ENERGY][:g], "n_edges": self.outputs["n_edges"]}
         if keys.ATOMIC_ENERGIES in self.outputs:
@@ -431,7 +442,76 @@ def auto_lanes(n_atoms: int) -> int:
     return max(1, int(env)) if env else 1
 
 
-class GraphedLanes:
+class _Steps:
+    """The counters of a class that runs its work on several ``GraphedStep`` objects, ``self.steps``."""
+
+    @property
+    def edge_total(self) -> torch.Tensor:
+        """Edges of every step run so far, all of ``steps`` (a device scalar; a synchronisation-free sum of their counters)."""
+        return torch.stack([st.edge_total for st in self.steps]).sum(0)
+
+    def zero_edge_total(self) -> None:
+        for st in self.steps:
+            st.edge_total.zero_()
+
+    def overflowed(self) -> bool:
+        """Whether the last list of one of ``steps`` outgrew its edge capacity (GraphedStep.overflowed: a synchronisation)."""
+        return any(st.overflowed() for st in self.steps)
+
+
+class _Ranges:
+    """ONE batch of independent molecules as contiguous molecule ranges -- the lanes of ``GraphedLanes``, the chunks of ``GraphedChunks``:
+    ``who`` and ``what`` in the messages -- each evaluated by a ``GraphedStep``, and the arrays (as ``like``) their results are gathered
+    into, in the batch's own order."""
+
+    def __init__(self, who: str, what: str, like: torch.Tensor, n_atoms: int, n_graphs: int, compute_forces: bool) -> None:
+        self.who, self.what = who, what
+        self.energy = torch.zeros(n_graphs, dtype=like.dtype, device=like.device)
+        self.atomic = torch.zeros(n_atoms, dtype=like.dtype, device=like.device)
+        self.forces = torch.zeros((n_atoms, 3), dtype=like.dtype, device=like.device) if compute_forces else None
+        self.ptr_host, self.ranges, self.needs = None, [], []
+
+    def cut(self, ptr_host, cuts, fit: Optional["GraphedStep"] = None) -> None:
+        """``ranges``: (a, b, g0, g1) -- atoms a .. b - 1, molecules g0 .. g1 - 1 -- per ``(g0, g1)`` of ``cuts`` over the host ``ptr``;
+        ``needs``: the (atoms, graphs, possible edges) a step must hold for each.  Refused: a range beyond the capacity of the step
+        ``fit``, and ranges on both sides of the node-block threshold."""
+        import numpy as np
+
+        ph = np.asarray(ptr_host, dtype=np.int64)
+        ranges = [(int(ph[g0]), int(ph[g1]), int(g0), int(g1)) for g0, g1 in cuts]
+        needs = [(b - a, g1 - g0, pair_capacity(ph[g0 : g1 + 1] - ph[g0])) for a, b, g0, g1 in ranges]
+        for n, g, e in needs:
+            if fit is not None and (n > fit.n_atoms or g > fit.n_graphs - 1 or e > fit.n_edges):
+                raise ValueError(f"{self.who}: {self.what} of {n} atoms / {g} graphs / {e} possible edges "
+                                 f"exceeds the {self.what} capacity {fit.n_atoms} / {fit.n_graphs - 1} / {fit.n_edges}")
+        if len({bool(ops.lib.load().xeq_node_block_auto(n)) for n, _, _ in needs}) > 1:
+            raise ValueError(f"{self.who}: the {self.what}s fall on both sides of the node-block threshold (their bits would differ from the unsplit batch's)")
+        self.ptr_host, self.ranges, self.needs = ptr_host, ranges, needs
+
+    @staticmethod
+    def inputs(pos: torch.Tensor, atomic_numbers: torch.Tensor, ptr: torch.Tensor, batch: torch.Tensor):
+        """(pos, z, ptr, batch) as ``GraphedStep._load_shard`` reads them."""
+        z_c = atomic_numbers.contiguous() if atomic_numbers.dtype in (torch.int32, torch.int64) else atomic_numbers.to(torch.int32).contiguous()
+        return pos.detach().contiguous(), z_c, ptr.to(torch.int64).contiguous(), batch.to(torch.int64).contiguous()
+
+    def scatter(self, k: int, o: Dict[str, torch.Tensor]) -> list:
+        """The (destination, source) pairs of ``ops.copy_many`` that put a step's outputs ``o`` at range ``k``'s place in the batch."""
+        a, b, g0, g1 = self.ranges[k]
+        pairs = [(self.energy[g0:g1], o[keys.TOTAL_ENERGY][: g1 - g0])]
+        if keys.ATOMIC_ENERGIES in o:
+            pairs.append((self.atomic[a:b], o[keys.ATOMIC_ENERGIES][: b - a]))
+        if self.forces is not None and keys.FORCES in o:
+            pairs.append((self.forces[a:b], o[keys.FORCES][: b - a]))
+        return pairs
+
+    def results(self, n: int, g: int) -> Dict[str, torch.Tensor]:
+        out = {keys.TOTAL_ENERGY: self.energy[:g], keys.ATOMIC_ENERGIES: self.atomic[:n]}
+        if self.forces is not None:
+            out[keys.FORCES] = self.forces[:n]
+        return out
+
+
+class GraphedLanes(_Weights, _Steps):
     """One batch of independent molecules as ``lanes`` contiguous molecule ranges whose whole steps (``GraphedStep``: neighbour list +
     model + forces) run CONCURRENTLY as parallel branches of ONE captured HIP graph.
 
@@ -449,8 +529,6 @@ class GraphedLanes:
     def __init__(self, model: torch.nn.Module, capacity, lanes: int = 2, cutoff: Optional[float] = None, compute_forces: bool = True,
                  warmup: int = 2, slack: float = 0.15) -> None:
         refuse_electronic(model, "GraphedLanes")
-        from . import lib
-
         assert 2 <= lanes <= lib.COPY_MANY_MAX // 3
         n_atoms, n_graphs, n_edges = (int(c) for c in capacity)
         self.model, self.lanes, self.compute_forces, self.warmup = model, lanes, compute_forces, warmup
@@ -459,107 +537,94 @@ class GraphedLanes:
         self.steps = [GraphedStep(model, (grow(n_atoms), grow(n_graphs), grow(n_edges)), cutoff=cutoff, compute_forces=compute_forces, warmup=0)
                       for _ in range(lanes)]
         p = self.steps[0].pos
-        self.energy = torch.zeros(n_graphs, dtype=p.dtype, device=p.device)
-        self.atomic = torch.zeros(n_atoms, dtype=p.dtype, device=p.device)
-        self.forces = torch.zeros((n_atoms, 3), dtype=p.dtype, device=p.device) if compute_forces else None
+        self._ranges = _Ranges("GraphedLanes", "lane", p, n_atoms, n_graphs, compute_forces)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.lane_outputs = None
         self.captures = 0
-        self._param_state = None
-        self._cuts = (None, None)
+        self._track_weights(model)
         self._streams = [torch.cuda.Stream(device=p.device) for _ in range(lanes - 1)]
 
-    @property
-    def edge_total(self) -> torch.Tensor:
-        """Edges of every step run so far, all lanes (a device scalar; a synchronisation-free sum of the lanes' counters)."""
-        return torch.stack([st.edge_total for st in self.steps]).sum(0)
-
-    def zero_edge_total(self) -> None:
-        for st in self.steps:
-            st.edge_total.zero_()
-
-    def overflowed(self) -> bool:
-        return any(st.outputs and int(st.outputs["n_edges"].item()) > st.n_edges for st in self.steps)
-
-    def _plan(self, ptr_host):
-        import numpy as np
-        from .dist import shard_by_edges
-
-        if self._cuts[0] is not ptr_host:
-            ph = np.asarray(ptr_host, dtype=np.int64)
-            cuts = shard_by_edges(ph, self.lanes)
-            plan = [(int(ph[g0]), int(ph[g1]), int(g0), int(g1)) for g0, g1 in cuts]
-            for (a, b, g0, g1), st in zip(plan, self.steps):
-                if b - a > st.n_atoms or g1 - g0 > st.n_graphs - 1 or pair_capacity(ph[g0 : g1 + 1] - ph[g0]) > st.n_edges:
-                    raise ValueError(f"GraphedLanes: lane of {b - a} atoms / {g1 - g0} graphs / {pair_capacity(ph[g0:g1 + 1] - ph[g0])} possible edges "
-                                     f"exceeds the lane capacity {st.n_atoms} / {st.n_graphs - 1} / {st.n_edges}")
-            self._cuts = (ptr_host, plan)
-        return self._cuts[1]
-
-    def _capture(self) -> None:
-        main = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            counted = [st.edge_total.clone() for st in self.steps]
-            for _ in range(self.warmup):
-                for st in self.steps:
-                    st._step()
-            for st, c in zip(self.steps, counted):
-                st.edge_total.copy_(c)                          # the warm-up runs are not steps
-        main.wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
+    def _lanes(self) -> list:
+        """Every lane's step, as parallel branches of whatever is capturing."""
         outs = [None] * self.lanes
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            cur = torch.cuda.current_stream()
-            for i in range(1, self.lanes):                      # fork: every lane but the first on its own stream
-                self._streams[i - 1].wait_stream(cur)
-                with torch.cuda.stream(self._streams[i - 1]):
-                    outs[i] = self.steps[i]._step()
-            outs[0] = self.steps[0]._step()
-            for i in range(1, self.lanes):                      # join
-                cur.wait_stream(self._streams[i - 1])
-        for st, o in zip(self.steps, outs):
-            st.outputs = o
-        self.lane_outputs = outs
-        self.captures += 1
+        cur = torch.cuda.current_stream()
+        for i in range(1, self.lanes):                      # fork: every lane but the first on its own stream
+            self._streams[i - 1].wait_stream(cur)
+            with torch.cuda.stream(self._streams[i - 1]):
+                outs[i] = self.steps[i]._step()
+        outs[0] = self.steps[0]._step()
+        for i in range(1, self.lanes):                      # join
+            cur.wait_stream(self._streams[i - 1])
+        return outs
 
     def __call__(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, ptr: torch.Tensor, batch: torch.Tensor, ptr_host) -> Dict[str, torch.Tensor]:
         """-> {energy [G], atomic_energies [n], forces [n, 3]}: this object's output buffers, overwritten by the next call."""
+        from .dist import shard_by_edges
+
         n, g = int(pos.shape[0]), int(ptr.numel() - 1)
         if n > self.n_atoms or g > self.n_graphs:
             raise ValueError(f"GraphedLanes: batch of {n} atoms / {g} graphs exceeds the capacity {self.n_atoms} / {self.n_graphs}")
-        plan = self._plan(ptr_host)
-        sides = {bool(ops.lib.load().xeq_node_block_auto(b - a)) for a, b, _, _ in plan}
-        if len(sides) > 1:
-            raise ValueError("GraphedLanes: the lanes fall on both sides of the node-block threshold (their bits would differ from the unsplit step's)")
-        pos_c = pos.detach().contiguous()
-        ptr_c, batch_c = ptr.to(torch.int64).contiguous(), batch.to(torch.int64).contiguous()
-        z_c = atomic_numbers.contiguous() if atomic_numbers.dtype in (torch.int32, torch.int64) else atomic_numbers.to(torch.int32).contiguous()
-        for (a, b, g0, g1), st in zip(plan, self.steps):
-            st._load_shard(pos_c, z_c, ptr_c, batch_c, a, b, g0, g1)
-        state = _params_state(self)
-        if self.graph is not None and state != self._param_state:
+        plan = self._ranges
+        if plan.ptr_host is not ptr_host:
+            plan.cut(ptr_host, shard_by_edges(ptr_host, self.lanes), fit=self.steps[0])
+        inputs = plan.inputs(pos, atomic_numbers, ptr, batch)
+        for r, st in zip(plan.ranges, self.steps):
+            st._load_shard(*inputs, *r)
+        if self._weights_moved():
             self.graph = None
-        self._param_state = state
         if self.graph is None:
-            self._capture()
+            self.graph, self.lane_outputs = _capture(self._lanes, self.warmup, warm=lambda: [st._step() for st in self.steps],
+                                                     keep=[st.edge_total for st in self.steps])
+            for st, o in zip(self.steps, self.lane_outputs):
+                st.outputs = o
+            self.captures += 1
         self.graph.replay()
-        pairs = []
-        for (a, b, g0, g1), o in zip(plan, self.lane_outputs):
-            pairs.append((self.energy[g0:g1], o[keys.TOTAL_ENERGY][: g1 - g0]))
-            if keys.ATOMIC_ENERGIES in o:
-                pairs.append((self.atomic[a:b], o[keys.ATOMIC_ENERGIES][: b - a]))
-            if self.forces is not None and keys.FORCES in o:
-                pairs.append((self.forces[a:b], o[keys.FORCES][: b - a]))
-        ops.copy_many(pairs)                                     # ONE launch: the lanes' results into the batch's own order
-        out = {keys.TOTAL_ENERGY: self.energy[:g], keys.ATOMIC_ENERGIES: self.atomic[:n]}
-        if self.forces is not None:
-            out[keys.FORCES] = self.forces[:n]
-        return out
+        ops.copy_many([p for k, o in enumerate(self.lane_outputs) for p in plan.scatter(k, o)])   # ONE launch: the lanes' results into the batch's own order
+        return plan.results(n, g)
 
 
-class GraphedStepsInFlight:
+class _StepsOnStreams(_Steps):
+    """``depth`` ``GraphedStep`` contexts in ``steps``, each run on a HIP stream of its own (``_streams``) with an event behind its last
+    work (``_done``)."""
+
+    NODE_BLOCK_WAVES = 4
+
+    def _open_streams(self, depth: int, device) -> None:
+        self.depth = depth
+        self._streams = [torch.cuda.Stream(device=device) for _ in range(depth)]
+        self._done = [torch.cuda.Event() for _ in range(depth)]
+
+    @contextmanager
+    def _side_by_side(self):
+        """Workgroups of four waves for the node-block launches captured inside (the setting is read at launch, i.e. at capture): next to
+        another step's kernels a CU that finishes early is not idle (profiles/r05_in_flight.txt: 2.00 -> 1.89 ms)."""
+        L = ops.lib.load()
+        former = L.xeq_node_block_set_waves(self.NODE_BLOCK_WAVES) if self.depth > 1 else None
+        try:
+            yield
+        finally:
+            if former is not None:
+                L.xeq_node_block_set_waves(former)
+
+    @staticmethod
+    def _hold(tensors, streams) -> None:
+        """The caching allocator must not hand the inputs out while the side streams read them."""
+        for t in tensors:
+            if t is not None and t.is_cuda:
+                for s in streams:
+                    t.record_stream(s)
+
+    def __del__(self):
+        # the contexts' buffers were allocated on the creator's stream and are used on the side streams: nothing of theirs may still be
+        # running when the allocator takes the memory back
+        try:
+            for s in self._streams:
+                s.synchronize()
+        except Exception:
+            pass
+
+
+class GraphedStepsInFlight(_StepsOnStreams):
     """A STREAM of batches with ``depth`` of them in flight: ``depth`` independent ``GraphedStep`` contexts (their own static buffers
     and captured graphs), each replayed on its own HIP stream, taken in turn.
 
@@ -577,16 +642,11 @@ class GraphedStepsInFlight:
         out = steps.result(t)                      # the CALLER's stream waits for that step; views valid until ``depth`` submits later
     """
 
-    NODE_BLOCK_WAVES = 4
-
     def __init__(self, model: torch.nn.Module, capacity, depth: int = 2, **kw) -> None:
         refuse_electronic(model, "GraphedStepsInFlight")
         assert depth >= 1
-        self.depth = int(depth)
-        self.steps = [GraphedStep(model, capacity, **kw) for _ in range(self.depth)]
-        dev = self.steps[0].pos.device
-        self._streams = [torch.cuda.Stream(device=dev) for _ in range(self.depth)]
-        self._done = [torch.cuda.Event() for _ in range(self.depth)]
+        self.steps = [GraphedStep(model, capacity, **kw) for _ in range(int(depth))]
+        self._open_streams(int(depth), self.steps[0].pos.device)
         self._out = [None] * self.depth
         self._serial = [-1] * self.depth
         self.submitted = 0
@@ -595,14 +655,17 @@ class GraphedStepsInFlight:
     def edge_total(self) -> torch.Tensor:
         """Edges of every step submitted so far (a device scalar on the caller's stream; waits for the steps in flight)."""
         self.drain()
-        return torch.stack([st.edge_total for st in self.steps]).sum(0)
+        return super().edge_total
 
     def zero_edge_total(self) -> None:
         self.drain()
-        cur = torch.cuda.current_stream()
-        for st, s in zip(self.steps, self._streams):
-            st.edge_total.zero_()
-            s.wait_stream(cur)
+        super().zero_edge_total()
+        for s in self._streams:                              # (the contexts' next steps run behind the zeroing)
+            s.wait_stream(torch.cuda.current_stream())
+
+    def overflowed(self) -> bool:
+        self.drain()
+        return super().overflowed()
 
     def submit(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, ptr: torch.Tensor, batch: Optional[torch.Tensor] = None,
                ptr_host=None) -> int:
@@ -612,20 +675,10 @@ class GraphedStepsInFlight:
         i = self.submitted % self.depth
         s = self._streams[i]
         s.wait_stream(torch.cuda.current_stream())
-        L = ops.lib.load()
-        # workgroups of four waves for the node-block launches captured here (the setting is read at launch, i.e. at capture): next to
-        # another step's kernels a CU that finishes early is not idle (profiles/r05_in_flight.txt: 2.00 -> 1.89 ms)
-        former = L.xeq_node_block_set_waves(self.NODE_BLOCK_WAVES) if self.depth > 1 else None
-        try:
-            with torch.cuda.stream(s):
-                self._out[i] = self.steps[i](pos, atomic_numbers, ptr, batch, ptr_host)
-                self._done[i].record(s)
-        finally:
-            if former is not None:
-                L.xeq_node_block_set_waves(former)
-        for t in (pos, atomic_numbers, ptr, batch):
-            if t is not None and t.is_cuda:
-                t.record_stream(s)                           # the caching allocator must not hand the inputs out while the side stream reads them
+        with self._side_by_side(), torch.cuda.stream(s):
+            self._out[i] = self.steps[i](pos, atomic_numbers, ptr, batch, ptr_host)
+            self._done[i].record(s)
+        self._hold((pos, atomic_numbers, ptr, batch), [s])
         self._serial[i] = self.submitted
         self.submitted += 1
         return self._serial[i]
@@ -649,21 +702,8 @@ class GraphedStepsInFlight:
         """One step, waited for (the GraphedStep call form; nothing overlaps this way)."""
         return self.result(self.submit(pos, atomic_numbers, ptr, batch, ptr_host))
 
-    def __del__(self):
-        # the contexts' buffers were allocated on the creator's stream and are used on the side streams: nothing of theirs may still be
-        # running when the allocator takes the memory back
-        try:
-            for s in self._streams:
-                s.synchronize()
-        except Exception:
-            pass
 
-    def overflowed(self) -> bool:
-        self.drain()
-        return any(st.overflowed() for st in self.steps)
-
-
-class GraphedChunks:
+class GraphedChunks(_StepsOnStreams):
     """ONE batch of independent open-boundary molecules of any size as contiguous molecule ranges ("chunks": at most ``max_edges``
     possible edges each, dist.plan_chunks -- the message kernels address with 32-bit offsets), every chunk a whole captured step
     (``GraphedStep``: neighbour list, walk plan, model, forces over capacity-sized arrays, edge count on the device) and ``depth`` of
@@ -686,85 +726,39 @@ class GraphedChunks:
 
         ph = np.asarray(ptr_host, dtype=np.int64)
         self.ptr_host = ph
-        cuts = plan_chunks(ph, int(WM_MAX_EDGES_PER_CHUNK if max_edges is None else max_edges))
-        self.plan = [(int(ph[g0]), int(ph[g1]), int(g0), int(g1)) for g0, g1 in cuts]
-        cap = (max(b - a for a, b, _, _ in self.plan) + 64, max(g1 - g0 for _, _, g0, g1 in self.plan),
-               max(pair_capacity(ph[g0 : g1 + 1] - ph[g0]) for _, _, g0, g1 in self.plan))
-        sides = {bool(ops.lib.load().xeq_node_block_auto(b - a)) for a, b, _, _ in self.plan}
-        if len(sides) > 1:
-            raise ValueError("GraphedChunks: the chunks fall on both sides of the node-block threshold (their bits would differ from one evaluation's)")
-        self.depth = max(1, min(int(depth), len(self.plan)))
-        self.steps = [GraphedStep(model, cap, compute_forces=compute_forces) for _ in range(self.depth)]
-        p = self.steps[0].pos
-        n, g = int(ph[-1]), len(ph) - 1
-        self.energy = torch.zeros(g, dtype=p.dtype, device=p.device)
-        self.atomic = torch.zeros(n, dtype=p.dtype, device=p.device)
-        self.forces = torch.zeros((n, 3), dtype=p.dtype, device=p.device) if compute_forces else None
-        self._streams = [torch.cuda.Stream(device=p.device) for _ in range(self.depth)]
-        self._done = [torch.cuda.Event() for _ in range(self.depth)]
+        self._ranges = plan = _Ranges("GraphedChunks", "chunk", next(model.parameters()), int(ph[-1]), len(ph) - 1, compute_forces)
+        plan.cut(ph, plan_chunks(ph, int(WM_MAX_EDGES_PER_CHUNK if max_edges is None else max_edges)))
+        cap = (max(n for n, _, _ in plan.needs) + 64, max(g for _, g, _ in plan.needs), max(e for _, _, e in plan.needs))
+        depth = max(1, min(int(depth), self.n_chunks))
+        self.steps = [GraphedStep(model, cap, compute_forces=compute_forces) for _ in range(depth)]
+        self._open_streams(depth, self.steps[0].pos.device)
 
     @property
     def n_chunks(self) -> int:
-        return len(self.plan)
-
-    @property
-    def edge_total(self) -> torch.Tensor:
-        """Edges of every chunk evaluated so far (a device scalar)."""
-        return torch.stack([st.edge_total for st in self.steps]).sum(0)
-
-    def zero_edge_total(self) -> None:
-        for st in self.steps:
-            st.edge_total.zero_()
-
-    def overflowed(self) -> bool:
-        return any(st.overflowed() for st in self.steps)
+        return len(self._ranges.ranges)
 
     def __call__(self, pos: torch.Tensor, atomic_numbers: torch.Tensor, ptr: torch.Tensor, batch: torch.Tensor) -> Dict[str, torch.Tensor]:
         """-> {energy [G], atomic_energies [N], forces [N, 3]}: this object's result arrays (overwritten by the next call), ordered into the
         caller's stream.  ``batch``: the per-atom graph index (int64)."""
         assert int(pos.shape[0]) == int(self.ptr_host[-1]) and int(ptr.numel()) == len(self.ptr_host), "GraphedChunks: another batch than the planned one"
-        pos_c = pos.detach().contiguous()
-        ptr_c, batch_c = ptr.to(torch.int64).contiguous(), batch.to(torch.int64).contiguous()
-        z_c = atomic_numbers.contiguous() if atomic_numbers.dtype in (torch.int32, torch.int64) else atomic_numbers.to(torch.int32).contiguous()
+        plan = self._ranges
+        inputs = plan.inputs(pos, atomic_numbers, ptr, batch)
         cur = torch.cuda.current_stream()
-        L = ops.lib.load()
-        former = L.xeq_node_block_set_waves(GraphedStepsInFlight.NODE_BLOCK_WAVES) if self.depth > 1 else None
-        try:
-            for k, (a, b, g0, g1) in enumerate(self.plan):
+        with self._side_by_side():
+            for k, r in enumerate(plan.ranges):
                 i = k % self.depth
                 st, s = self.steps[i], self._streams[i]
                 if k < self.depth:
                     s.wait_stream(cur)                               # the inputs (and the result arrays' last readers) are on the caller's stream
                 with torch.cuda.stream(s):
-                    st._load_shard(pos_c, z_c, ptr_c, batch_c, a, b, g0, g1)
-                    st._replay()
-                    o = st.outputs
-                    pairs = [(self.energy[g0:g1], o[keys.TOTAL_ENERGY][: g1 - g0])]
-                    if keys.ATOMIC_ENERGIES in o:
-                        pairs.append((self.atomic[a:b], o[keys.ATOMIC_ENERGIES][: b - a]))
-                    if self.forces is not None and keys.FORCES in o:
-                        pairs.append((self.forces[a:b], o[keys.FORCES][: b - a]))
-                    ops.copy_many(pairs)                             # the chunk's results to their place, behind its replay on its stream
+                    st._load_shard(*inputs, *r)
+                    st.replay()
+                    ops.copy_many(plan.scatter(k, st.outputs))       # the chunk's results to their place, behind its replay on its stream
                     self._done[i].record(s)
-        finally:
-            if former is not None:
-                L.xeq_node_block_set_waves(former)
-        for t in (pos_c, z_c, ptr_c, batch_c):
-            for s in self._streams:
-                t.record_stream(s)
+        self._hold(inputs, self._streams)
         for i in range(self.depth):
             cur.wait_event(self._done[i])
-        out = {keys.TOTAL_ENERGY: self.energy, keys.ATOMIC_ENERGIES: self.atomic}
-        if self.forces is not None:
-            out[keys.FORCES] = self.forces
-        return out
-
-    def __del__(self):
-        try:    # (as GraphedStepsInFlight: the side streams are idle before the buffers go back to the allocator)
-            for s in self._streams:
-                s.synchronize()
-        except Exception:
-            pass
+        return plan.results(int(pos.shape[0]), int(ptr.numel() - 1))
 
 
 def evaluate_batches(model: torch.nn.Module, batches, capacity, depth: int = 2, compute_forces: bool = True):
@@ -789,7 +783,7 @@ def evaluate_batches(model: torch.nn.Module, batches, capacity, depth: int = 2, 
         yield fetch()
 
 
-class GraphedStepPBC:
+class GraphedStepPBC(_WholeStep):
     """Neighbour search + model of ONE periodic (or open) system as one captured HIP graph: what an MD engine that hands over
     positions and a box per step runs (the GROMACS-style model, interface/jit_model.py:183-216: ``single_radius_graph`` inside
     ``forward``, then the evaluation).
@@ -823,7 +817,7 @@ class GraphedStepPBC:
         (the MD front ends' unit-free core)."""
         refuse_electronic(model, "GraphedStepPBC")
         self.model = model
-        net = model if isinstance(model, torch.nn.Module) else model.model
+        net = module_of(model)
         self.n_atoms, self.n_edges = int(n_atoms), int(edge_capacity)
         self.cutoff = float(net.cutoff_radius if cutoff is None else cutoff)
         self.compute_forces = compute_forces
@@ -843,11 +837,10 @@ class GraphedStepPBC:
         self.ptr = torch.tensor([0, N], dtype=torch.int64, device=self.device)
         self.batch = torch.zeros(N, dtype=torch.int64, device=self.device)
         self.warmup = warmup
-        self.captures = 0
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.outputs: Dict[str, torch.Tensor] = {}
+        self._init_graph()
         self._cell_host = None
         self._pbc = None
+        self._pbc_seen = None            # (the periodicity TENSOR of the last call, its version): _load_cell
         self._reps = None
         self._tab_flat: Optional[torch.Tensor] = None
         self._alloc_edges()
@@ -871,7 +864,7 @@ class GraphedStepPBC:
                            cell_offsets=self.cell_offsets)
         data = {keys.POSITIONS: self.pos.detach(), keys.ATOMIC_NUMBERS: self.z, keys.CELL: self.cell, keys.EDGE_INDEX: self.edge_index,
                 keys.CELL_OFFSETS: self.cell_offsets, keys.BATCH: self.batch, keys.BATCH_PTR: self.ptr, keys.EDGE_GRAPH: eg}
-        _offer_zero_start(self, data)
+        self._offer_zero_start(data)
         with torch.enable_grad():
             out = self.model(data, compute_forces=self.compute_forces, compute_virial=self.compute_virial)
         res = {k: v.detach() for k, v in out.items() if isinstance(v, torch.Tensor)}
@@ -889,7 +882,7 @@ class GraphedStepPBC:
         # the usual step: the box the tables were built for (NVT, or NPT between barostat moves) and the very periodicity tensor of the
         # last call -- asked on the device with one launch and one read-back (ops.any_differs) instead of two read-backs of the values
         if (self._cell_host is not None and isinstance(pbc, torch.Tensor) and cell.is_cuda and cell.dtype == self.dtype
-                and getattr(self, "_pbc_seen", None) is not None and self._pbc_seen[0] is pbc and self._pbc_seen[1] == pbc._version
+                and self._pbc_seen is not None and self._pbc_seen[0] is pbc and self._pbc_seen[1] == pbc._version
                 and not ops.any_differs([(cell.detach().reshape(self.cell.shape), self.cell)])):
             return
         c = np.ascontiguousarray(cell.detach().to(self.dtype).reshape(1, 3, 3).cpu().numpy())     # the step's one small round trip
@@ -944,28 +937,6 @@ class GraphedStepPBC:
         """Images per axis of the captured table."""
         return None if self._reps is None else list(self._reps)
 
-    def _run(self) -> None:
-        state = _params_state(self)
-        if self.graph is not None and state != getattr(self, "_param_state", None):   # weights moved: the captured packed copies are stale
-            self.graph = None
-        self._param_state = state
-        if self.graph is None:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(self.warmup):
-                    self._step()
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.outputs = self._step()
-            self.captures += 1
-        self.graph.replay()
-
-    def replay(self) -> None:
-        """The step on whatever the static buffers hold (md.Dynamics writes positions there itself); results in ``outputs``."""
-        self._run()
-
     def grow(self, n_edges_seen: int) -> None:
         """More room for a list that reached ``n_edges_seen`` edges: half as much again as the larger of that and the capacity, plus 64;
         the next replay captures again."""
@@ -980,11 +951,11 @@ class GraphedStepPBC:
             raise ValueError(f"GraphedStepPBC: {pos.shape[0]} atoms, captured for {self.n_atoms}")
         self._load_cell(cell, pbc)
         ops.copy_many([(self.pos, pos.detach().to(self.dtype)), (self.z, atomic_numbers.to(torch.int32))])
-        self._run()
+        self.replay()
         if check:
             while self.overflowed():
                 self.grow(int(self.outputs["n_edges"].item()))
-                self._run()
+                self.replay()
         return dict(self.outputs)
 
     def overflowed(self) -> bool:
