@@ -83,36 +83,6 @@ int64_t xeq_exclusive_scan_i32_workspace(int64_t n);
 int xeq_exclusive_scan_i32_ws(const int32_t* counts, int64_t n, int32_t* out, void* workspace, int64_t workspace_bytes,
                               void* stream);
 
-/* Replaces torch_cluster.radius_graph at data/transform.py:58-64 (non-PBC):
- * same-graph pairs with d^2 < r^2 (strict), no self loops, unlimited neighbours.
- * Phase 1 writes deg[N]; the caller scans it (xeq_exclusive_scan_i32), reads
- * E = rowptr[N] back, allocates edge_index[2,E]; phase 2 fills it in canonical
- * order: sorted by center (row 0), then neighbor (row 1). */
-/* Capacity form (round 3): the edge count need not reach the host.  Pass a CAPACITY as n_edges (edge_index [2, capacity], never
- * written past) and hand the same capacity to xeq_reverse_edge_map, xeq_edge_vectors_fwd and the wq message entry points: every
- * walk over the list is bounded by rowptr[n_nodes] on the device, slots behind it keep whatever valid node ids they held (zero-
- * initialise the buffer once).  This is what lets neighbour list + model run as ONE captured HIP graph for batches of changing
- * edge counts (xequinet_amd/runtime.py::GraphedStep); an open-boundary list never exceeds sum_g n_g (n_g - 1). */
-int xeq_radius_graph_count(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                           double cutoff, int32_t* deg, void* stream);
-int xeq_radius_graph_fill(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                          double cutoff, const int32_t* rowptr, int64_t n_edges, int64_t* edge_index, void* stream);
-
-/* Cell-list form of the open-boundary search for graphs of many atoms (the sweep above is O(n_g^2) per graph): per
- * graph an axis-aligned bin grid over its bounding box, lo[G,3] / inv_w[G,3] (inverse bin width, width >= cutoff) /
- * nbins[G,3], bin_base[G+1] = running bin count.  xeq_radius_graph_bin_ids gives each atom's global bin id, the caller
- * sorts atoms by it (xeq_csr_by_key: bin_start, bin_atom); count/fill visit the 3x3x3 bin block of each center with the
- * same d^2 < r^2 arithmetic and rank the hits per center: the same canonical edge_index, bit for bit. */
-int xeq_radius_graph_bin_ids(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes, const void* lo,
-                             const void* inv_w, const int32_t* nbins, const int32_t* bin_base, int64_t* keys, void* stream);
-int xeq_radius_graph_count_cl(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes, double cutoff,
-                              const void* lo, const void* inv_w, const int32_t* nbins, const int32_t* bin_base,
-                              const int32_t* bin_start, const int32_t* bin_atom, int32_t* deg, void* stream);
-int xeq_radius_graph_fill_cl(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes, double cutoff,
-                             const void* lo, const void* inv_w, const int32_t* nbins, const int32_t* bin_base,
-                             const int32_t* bin_start, const int32_t* bin_atom, const int32_t* rowptr, int64_t n_edges,
-                             int64_t* tmp_keys, int64_t* edge_index, void* stream);
-
 /* Everything the periodic search derives from the cells alone (HOST function: host pointers in and out, no device work).
  * Replaces the host-side preparation of data/radius_graph.py: images per axis reps[a] = max_g ceil(cutoff |a_j x a_k| / V)
  * on the periodic axes, 0 on the open ones (:61-89); the image table grid[n_cells, 3] in cartesian_prod order, first axis
@@ -138,56 +108,81 @@ int xeq_pbc_tables_device(int dtype, const void* cell, const int32_t reps[3], co
  * axes (pbc[a] != 0), pos_wrap = (fractional - shift) cell[g].  cell / cell_inv [G, 3, 3] row-major (rows = lattice vectors). */
 int xeq_pbc_wrap(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes, const void* cell,
                  const void* cell_inv, const int32_t pbc[3], void* pos_wrap, void* shift, void* stream);
-/* Replaces the cdist/nonzero search of radius_graph_pbc (data/radius_graph.py:118-126,
- * 162-181).  The caller supplies what the reference computes on the host side:
- * wrapped positions pos_wrap[N,3] (:111), per-graph image translation vectors
- * img[G, n_cells, 3] (:104) and the integer image table cells[n_cells,3] (:97),
- * per-atom wrap shift[N,3] (:113).  Pairs with 0.01 < D < cutoff are emitted
- * center-major, then by (neighbor * n_cells + cell) ascending, bit-identical to the
- * reference ordering; cell_offsets = cells[cell] + shift[center] - shift[neighbor]
- * (:186-190). */
-int xeq_radius_graph_pbc_count(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                               int64_t n_nodes, const void* img, int64_t n_cells, double cutoff, int32_t* deg,
-                               void* stream);
-int xeq_radius_graph_pbc_fill(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                              int64_t n_nodes, const void* img, const void* cells, const void* shift,
-                              int64_t n_cells, double cutoff, const int32_t* rowptr, int64_t n_edges,
-                              int64_t* edge_index, void* cell_offsets, void* stream);
+/* ------------------------------------------------------------ neighbour search */
 
-/* The same search with image pruning (default of the Python front): per (center, neighbor) pair only the image
- * offsets n with |f_a - n_a| <= thr_a on every periodic axis are evaluated, f = (pos_wrap[c] - pos_wrap[n]) . recip^T --
- * a necessary condition for the pair to be within the cutoff, so the edge set and its order are bit-identical to the
- * exhaustive form above (the survivors are evaluated with the same arithmetic).  recip[G,3,3]: rows a_j x a_k / V of
- * each cell (what data/radius_graph.py:61-82 builds for its image counts); thr[G,3] = cutoff |recip_a| + margin;
- * reps[3] = images per axis of the enumeration (n_cells = prod (2 reps + 1), cartesian_prod order). */
-int xeq_radius_graph_pbc_count_pruned(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                                      int64_t n_nodes, const void* img, int64_t n_cells, double cutoff, const void* recip,
-                                      const void* thr, const int32_t reps[3], int32_t* deg, void* stream);
-int xeq_radius_graph_pbc_fill_pruned(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                                     int64_t n_nodes, const void* img, const void* cells, const void* shift, int64_t n_cells,
-                                     double cutoff, const void* recip, const void* thr, const int32_t reps[3],
-                                     const int32_t* rowptr, int64_t n_edges, int64_t* edge_index, void* cell_offsets,
-                                     void* stream);
+/* ONE neighbour search in five forms, described by one argument record (the rules of the records further down: every member 8 bytes
+ * wide, no padding, XEQ_REC_NEIGHBORS of xeq_record_bytes; read during the call, not retained).  `kind` names the form -- it is
+ * stated, never inferred from which pointers are set -- and the form names the members it reads; a member a form needs and finds
+ * NULL is refused with XEQ_ERR_INVALID_ARGUMENT and the member's name in xeq_last_error, before anything is launched.  All forms
+ * emit the same canonical list: sorted by center (row 0 of edge_index), then by neighbor -- the periodic forms by
+ * (neighbor * n_cells + cell) ascending -- bit for bit whichever form ran.
+ *
+ * XEQ_NEIGHBORS_OPEN_SWEEP   Replaces torch_cluster.radius_graph at data/transform.py:58-64 (non-PBC): same-graph pairs with
+ *     d^2 < r^2 (strict), no self loops, unlimited neighbours.  One wave per center sweeps its graph.  Reads pos, ptr.
+ * XEQ_NEIGHBORS_OPEN_BINS    The same list for graphs of many atoms (the sweep is O(n_g^2) per graph): per graph an axis-aligned
+ *     bin grid over its bounding box, lo[G,3] / inv_w[G,3] (inverse bin width, width >= cutoff) / nbins[G,3], bin_base[G+1] =
+ *     running bin count.  Count and fill visit the 3x3x3 bin block of each center with the same d^2 < r^2 arithmetic and rank
+ *     the hits per center.  Reads pos, ptr, lo, inv_w, nbins, bin_base, bin_start, bin_atom.
+ * XEQ_NEIGHBORS_PBC_ALL      Replaces the cdist/nonzero search of radius_graph_pbc (data/radius_graph.py:118-126, 162-181).  The
+ *     caller supplies what the reference computes on the host side: wrapped positions pos[N,3] (:111), per-graph image
+ *     translation vectors img[G, n_cells, 3] (:104), the integer image table cells[n_cells,3] (:97) and the per-atom wrap
+ *     shift[N,3] (:113).  Pairs with 0.01 < D < cutoff, every image of every pair tested; cell_offsets = cells[cell] +
+ *     shift[center] - shift[neighbor] (:186-190).  Reads pos, ptr, img, n_cells; the fill also cells, shift.
+ * XEQ_NEIGHBORS_PBC_PRUNED   The same search with image pruning (default of the Python front): per (center, neighbor) pair only
+ *     the image offsets n with |f_a - n_a| <= thr_a on every periodic axis are evaluated, f = (pos[c] - pos[n]) . recip^T -- a
+ *     necessary condition for the pair to be within the cutoff, so the edge set and its order are those of the exhaustive form
+ *     (the survivors are evaluated with the same arithmetic).  recip[G,3,3]: rows a_j x a_k / V of each cell (what
+ *     data/radius_graph.py:61-82 builds for its image counts); thr[G,3] = cutoff |recip_a| + margin; reps[3] = images per axis of
+ *     the enumeration (n_cells = prod (2 reps + 1), cartesian_prod order; anything else is refused).  Reads what PBC_ALL reads and
+ *     recip, thr, reps.
+ * XEQ_NEIGHBORS_PBC_BINS     The pruned search for graphs of many atoms.  Bins live in fractional coordinates: nbins[G,3] per axis
+ *     (1 on open axes; bin width >= the cutoff across lattice planes, i.e. nbins_a <= 1 / thr_a), bin_base[G+1] = running sum of
+ *     bins per graph.  Count and fill visit the 3x3x3 bin block around each center (same per-pair arithmetic and image pruning);
+ *     the fill writes unordered keys and ranks them per center, which restores the reference's order.  Reads what PBC_PRUNED reads
+ *     and nbins, bin_base, bin_start, bin_atom.
+ *
+ * The sequence: for the two bin-grid kinds first xeq_neighbors_bin_ids (keys[N] = each atom's global bin id; reads pos, ptr,
+ * nbins, bin_base and lo, inv_w or recip), then the caller sorts atoms by it (xeq_csr_by_key: bin_start[n_bins + 1], bin_atom[N])
+ * and sets the two members.  xeq_neighbors_count writes deg[N]; the caller scans it (xeq_exclusive_scan_i32), reads E =
+ * rowptr[N] back and allocates edge_index[2, E] (periodic kinds: cell_offsets[E, 3] of `dtype`; bin-grid kinds: tmp_keys[E], NULL
+ * for the others); xeq_neighbors_fill writes them.  n_nodes = 0 and (for the fill) n_edges = 0 return XEQ_OK at once.
+ *
+ * Capacity form (round 3): the edge count need not reach the host.  Pass a CAPACITY as n_edges of the open sweep or the pruned
+ * periodic kind (edge_index [2, capacity], never written past) and hand the same capacity to the reverse-edge maps,
+ * xeq_edge_vectors_fwd and the wq message entry points: every walk over the list is bounded by rowptr[n_nodes] on the device,
+ * slots behind it keep whatever valid node ids they held (zero-initialise the buffer once).  This is what lets neighbour list +
+ * model run as ONE captured HIP graph for batches of changing edge counts (xequinet_amd/runtime.py::GraphedStep); an
+ * open-boundary list never exceeds sum_g n_g (n_g - 1). */
+enum { XEQ_NEIGHBORS_OPEN_SWEEP = 0, XEQ_NEIGHBORS_OPEN_BINS = 1, XEQ_NEIGHBORS_PBC_ALL = 2, XEQ_NEIGHBORS_PBC_PRUNED = 3,
+       XEQ_NEIGHBORS_PBC_BINS = 4 };
 
-/* Cell-list form of the same search for graphs of many atoms (the pair sweep above is O(n_g^2)).  Bins live in
- * fractional coordinates: nbins[G,3] per axis (1 on open axes; bin width >= the cutoff across lattice planes, i.e.
- * nbins_a <= 1 / thr_a), bin_base[G+1] = running sum of bins per graph.  xeq_radius_graph_pbc_bin_ids writes each atom's
- * global bin id; the caller sorts atoms by it (xeq_csr_by_key: bin_start[n_bins+1], bin_atom[N]).  count/fill then
- * visit the 3x3x3 bin block around each center (same per-pair arithmetic and image pruning as the _pruned form); fill
- * writes unordered keys into tmp_keys[E] and ranks them per center, so edge_index / cell_offsets come out in the
- * reference's order, bit-identical to the exhaustive form. */
-int xeq_radius_graph_pbc_bin_ids(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                                 const void* recip, const int32_t* nbins, const int32_t* bin_base, int64_t* keys, void* stream);
-int xeq_radius_graph_pbc_count_cl(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                                  const void* img, int64_t n_cells, double cutoff, const void* recip, const void* thr,
-                                  const int32_t reps[3], const int32_t* nbins, const int32_t* bin_base,
-                                  const int32_t* bin_start, const int32_t* bin_atom, int32_t* deg, void* stream);
-int xeq_radius_graph_pbc_fill_cl(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                                 const void* img, const void* cells, const void* shift, int64_t n_cells, double cutoff,
-                                 const void* recip, const void* thr, const int32_t reps[3], const int32_t* nbins,
-                                 const int32_t* bin_base, const int32_t* bin_start, const int32_t* bin_atom,
-                                 const int32_t* rowptr, int64_t n_edges, int64_t* tmp_keys, int64_t* edge_index,
-                                 void* cell_offsets, void* stream);
+typedef struct xeq_neighbor_search {
+  int64_t dtype;            /* XEQ_F32 / XEQ_F64: the type of pos, img, cells, shift, recip, thr, lo, inv_w and cell_offsets */
+  int64_t kind;             /* XEQ_NEIGHBORS_* */
+  int64_t n_graphs;
+  int64_t n_nodes;
+  int64_t n_cells;          /* periodic kinds: images in the table, > 0 */
+  double cutoff;
+  int64_t reps[3];          /* pruned and periodic bin-grid kinds: images per axis */
+  const void* pos;          /* [N, 3]; the periodic kinds: wrapped positions */
+  const int64_t* ptr;       /* [G + 1]: first atom of every graph */
+  const void* img;          /* [G, n_cells, 3] */
+  const void* cells;        /* [n_cells, 3] (fill) */
+  const void* shift;        /* [N, 3] (fill) */
+  const void* recip;        /* [G, 3, 3] */
+  const void* thr;          /* [G, 3] */
+  const void* lo;           /* [G, 3] */
+  const void* inv_w;        /* [G, 3] */
+  const int32_t* nbins;     /* [G, 3] */
+  const int32_t* bin_base;  /* [G + 1] */
+  const int32_t* bin_start; /* [n_bins + 1] (count, fill) */
+  const int32_t* bin_atom;  /* [N] (count, fill) */
+} xeq_neighbor_search;
+
+int xeq_neighbors_bin_ids(const xeq_neighbor_search* search, int64_t* keys, void* stream);
+int xeq_neighbors_count(const xeq_neighbor_search* search, int32_t* deg, void* stream);
+int xeq_neighbors_fill(const xeq_neighbor_search* search, const int32_t* rowptr, int64_t n_edges, int64_t* tmp_keys, int64_t* edge_index,
+                       void* cell_offsets, void* stream);
 
 /* ------------------------------------------------------------ edge geometry */
 
@@ -198,7 +193,7 @@ int xeq_radius_graph_pbc_fill_cl(int dtype, const void* pos_wrap, const int64_t*
  * rev[e] = -1 where the reverse edge is missing (the list was not symmetric). */
 int xeq_reverse_edge_map(const int64_t* edge_index, int64_t n_edges, int64_t n_nodes, const int32_t* c_rowptr,
                          int32_t* rev, void* stream);
-/* The same for a PERIODIC list of the builders below (xeq_radius_graph_pbc_*: center-sorted, a center's edges ascending in (neighbor,
+/* The same for a PERIODIC list of the builders above (the XEQ_NEIGHBORS_PBC_* kinds: center-sorted, a center's edges ascending in (neighbor,
  * image)): rev[e] = position of (j <- i, -offset) for e = (i <- j, offset), -1 where the list holds no such edge.  Such a list is
  * symmetric up to a rounding at the cutoff -- the reference forms |pos_i - (pos_j + image)| (data/radius_graph.py:117-121), and the two
  * directions round differently -- so a -1 can occur for an edge within an ulp of the cutoff, where the envelope is ~1e-14 (and its
@@ -991,7 +986,8 @@ int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const 
  * -- so a record's layout is its field order, without padding, on any ABI; xeq_record_bytes(which) gives the library's sizeof for a
  * binding to compare with its own (-1: no such record).  A record is read during the call and not retained.  Pointers are device
  * pointers unless marked HOST; `dtype` below: a buffer of the system record's floating type. */
-enum { XEQ_REC_SYSTEM = 0, XEQ_REC_STEP = 1, XEQ_REC_CHUNKS = 2, XEQ_REC_RECORDER = 3, XEQ_REC_MD = 4, XEQ_REC_NPT = 5, XEQ_REC_FIRE = 6 };
+enum { XEQ_REC_SYSTEM = 0, XEQ_REC_STEP = 1, XEQ_REC_CHUNKS = 2, XEQ_REC_RECORDER = 3, XEQ_REC_MD = 4, XEQ_REC_NPT = 5, XEQ_REC_FIRE = 6,
+       XEQ_REC_NEIGHBORS = 7 /* xeq_neighbor_search, with the neighbour search above */ };
 int64_t xeq_record_bytes(int which);
 
 typedef struct xeq_res_system {

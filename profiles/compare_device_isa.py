@@ -25,7 +25,7 @@ def kernels(obj):
         m = SYMBOL.match(line.strip())
         if m:
             cur = out.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":      # "...": objdump's mark for the zero padding behind a symbol
             cur.append(line.split("//")[0].strip())
     return out
 

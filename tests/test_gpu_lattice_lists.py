@@ -168,6 +168,63 @@ def test_registered_operators_equal_the_exact_list(dtype, npdt):
         assert int(rowptr[-1].item()) == ei.shape[1]
 
 
+# ------------------------------------------------------------------------------------------- the C entries on hand-filled records
+SMALLEST_OPEN = min(lc.names(periodic=False), key=lambda n: lc.case(n).n_atoms)
+
+
+@pytest.mark.parametrize("dtype,npdt", DTYPES, ids=IDS)
+@pytest.mark.parametrize("kind", ["OPEN_SWEEP", "OPEN_BINS", "PBC_ALL", "PBC_PRUNED", "PBC_BINS"])
+def test_entries_on_hand_filled_records_equal_the_exact_list(kind, dtype, npdt):
+    """xeq_neighbors_bin_ids / _count / _fill through lib.call on a record filled HERE, member by member, with the scan by torch: a
+    front of ops.py that fills the record wrongly cannot be masked by an entry that reads it equally wrongly.  Every kind, on the
+    smallest cases (8 and 70 atoms), bit for bit the exact list."""
+    from xequinet_amd import lib, ops
+    from xequinet_amd.data.radius_graph import _with_bins
+
+    periodic, bins = kind.startswith("PBC"), kind.endswith("BINS")
+    name = "small444" if periodic else SMALLEST_OPEN
+    c = lc.case(name)
+    ei, off, _ = lc.exact(name)
+    N, G, st = c.n_atoms, len(c.ptr) - 1, lib.stream()
+    rec = lib.fill(lib.NeighborSearch(), dtype=lib.XEQ_F32 if dtype == torch.float32 else lib.XEQ_F64, kind=getattr(lib, "NEIGHBORS_" + kind),
+                   n_graphs=G, n_nodes=N, cutoff=c.rc)
+    if periodic:
+        s = _setup_case(name, dtype, npdt)[1]
+        pos, ptr_t, img, cells, shift = (s[k].contiguous() for k in ("pw", "ptr", "img", "grid", "shift"))
+        recip, thr = s["prune"][0].to(dtype).contiguous(), s["prune"][1].to(dtype).contiguous()
+        lib.fill(rec, pos=pos, ptr=ptr_t, img=img, cells=cells, shift=shift, n_cells=cells.shape[0])
+        if kind != "PBC_ALL":
+            lib.fill(rec, recip=recip, thr=thr, reps=tuple(s["prune"][2]))
+        if bins:
+            nbins = _with_bins(s["prune"], c.pbc)[3].contiguous()
+    else:
+        pos, ptr_t = _t(lc.positions(c, npdt)), _t(c.ptr, torch.int64)
+        lib.fill(rec, pos=pos, ptr=ptr_t)
+        if bins:
+            lo, nbins, inv_w = ops._box_grid(pos, ptr_t, c.rc)
+            lib.fill(rec, lo=lo, inv_w=inv_w)
+    if bins:
+        assert nbins.dtype == torch.int32 and nbins.shape == (G, 3)
+        bin_base = torch.zeros(G + 1, dtype=torch.int32, device=DEV)
+        bin_base[1:] = torch.cumsum(nbins.prod(dim=1), 0)
+        keys = torch.empty(N, dtype=torch.int64, device=DEV)
+        lib.fill(rec, nbins=nbins, bin_base=bin_base)
+        lib.call("xeq_neighbors_bin_ids", rec, lib.ptr(keys), st)
+        bin_start, bin_atom = ops.csr_by_key(keys, int(bin_base[-1]))
+        lib.fill(rec, bin_start=bin_start, bin_atom=bin_atom)
+    deg = torch.empty(N, dtype=torch.int32, device=DEV)
+    lib.call("xeq_neighbors_count", rec, lib.ptr(deg), st)
+    rowptr = torch.zeros(N + 1, dtype=torch.int32, device=DEV)
+    rowptr[1:] = torch.cumsum(deg, 0)
+    np.testing.assert_array_equal(_np(rowptr), np.searchsorted(ei[0], np.arange(N + 1)), err_msg=f"{name} {kind} rowptr")
+    E = int(rowptr[-1])
+    got_ei = torch.full((2, E), -1, dtype=torch.int64, device=DEV)
+    got_off = torch.full((E, 3), float("nan"), dtype=dtype, device=DEV) if periodic else None
+    tmp_keys = torch.empty(E, dtype=torch.int64, device=DEV) if bins else None
+    lib.call("xeq_neighbors_fill", rec, lib.ptr(rowptr), E, lib.ptr(tmp_keys), lib.ptr(got_ei), lib.ptr(got_off), st)
+    _same(got_ei, got_off, ei, off, f"{name} {kind}")
+
+
 # ------------------------------------------------------------------------------------------------------------------ guard bands
 GUARDED_CASE = "sc32_faces"
 

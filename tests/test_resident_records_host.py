@@ -1,4 +1,5 @@
-"""The argument records of the resident drivers' entries (include/xeq.h: xeq_res_*, xeq_*_params) against their ctypes mirrors in
+"""The argument records of the resident drivers' entries and of the neighbour search (include/xeq.h: xeq_res_*, xeq_*_params,
+xeq_neighbor_search) against their ctypes mirrors in
 xequinet_amd/lib.py, and the constants lib.py restates against the header's #define / enum values.  Host only: the header is parsed as
 text, the library is asked for its sizes."""
 import ctypes
@@ -47,7 +48,7 @@ def test_records_match_the_header_member_for_member():
     L = lib.load()
     assert sorted(records) == sorted(r.__name__ for r in lib.RECORDS)              # every record of the header has its mirror, and no other
     which = {"xeq_res_system": "SYSTEM", "xeq_res_step": "STEP", "xeq_res_chunks": "CHUNKS", "xeq_res_recorder": "RECORDER", "xeq_md_params": "MD",
-             "xeq_npt_params": "NPT", "xeq_fire_params": "FIRE"}
+             "xeq_npt_params": "NPT", "xeq_fire_params": "FIRE", "xeq_neighbor_search": "NEIGHBORS"}
     for index, rec in enumerate(lib.RECORDS):
         members = records[rec.__name__]
         assert const["XEQ_REC_" + which[rec.__name__]] == index, rec.__name__      # lib.RECORDS is in the order of XEQ_REC_*

@@ -169,6 +169,15 @@ template <typename T> __device__ __forceinline__ T sub_rn(T a, T b);
 template <> __device__ __forceinline__ float sub_rn<float>(float a, float b) { return __fsub_rn(a, b); }
 template <> __device__ __forceinline__ double sub_rn<double>(double a, double b) { return __dsub_rn(a, b); }
 
+// The edge decision of the two open-boundary kernels (pair sweep, bin grid), written once: d^2 = (dx dx + dy dy) + dz dz < r^2, no
+// self loop.  Both kernels compile to the instructions they had with the text in place (profiles/neighbor_search_refactor.txt).
+template <typename T>
+__device__ __forceinline__ bool open_hit(const T* __restrict__ pos, T xi, T yi, T zi, int64_t i, int64_t j, T r2) {
+  T dx = sub_rn<T>(xi, pos[3 * j]), dy = sub_rn<T>(yi, pos[3 * j + 1]), dz = sub_rn<T>(zi, pos[3 * j + 2]);
+  T d2 = add_rn<T>(add_rn<T>(mul_rn<T>(dx, dx), mul_rn<T>(dy, dy)), mul_rn<T>(dz, dz));
+  return d2 < r2 && j != i;
+}
+
 // One wave per center, lane = candidate neighbour (64 at a time in ascending index: a ballot + prefix popcount keeps the
 // (center, neighbor) order).  A thread per center walking its molecule in a dependent loop took 13 + 7 us (count + fill) for
 // the 335 k distance checks of QM9-1024 on a third of the CUs.
@@ -189,9 +198,7 @@ __global__ void k_radius_graph(const T* __restrict__ pos, const int64_t* __restr
     const int64_t j = j0 + lane;
     bool hit = false;
     if (j < b) {
-      T dx = sub_rn<T>(xi, pos[3 * j]), dy = sub_rn<T>(yi, pos[3 * j + 1]), dz = sub_rn<T>(zi, pos[3 * j + 2]);
-      T d2 = add_rn<T>(add_rn<T>(mul_rn<T>(dx, dx), mul_rn<T>(dy, dy)), mul_rn<T>(dz, dz));
-      hit = d2 < r2 && j != i;
+      hit = open_hit<T>(pos, xi, yi, zi, i, j, r2);
     }
     const unsigned long long m = __ballot(hit);
     if (FILL && hit) {
@@ -605,9 +612,7 @@ __global__ void k_radius_graph_cl(const T* __restrict__ pos, const int64_t* __re
           int64_t j = 0;
           if (sl < s1) {
             j = bin_atom[sl];
-            T dx = sub_rn<T>(xi, pos[3 * j]), dy = sub_rn<T>(yi, pos[3 * j + 1]), dz = sub_rn<T>(zi, pos[3 * j + 2]);
-            T d2 = add_rn<T>(add_rn<T>(mul_rn<T>(dx, dx), mul_rn<T>(dy, dy)), mul_rn<T>(dz, dz));
-            hit = d2 < r2 && j != i;
+            hit = open_hit<T>(pos, xi, yi, zi, i, j, r2);
           }
           const unsigned long long m = __ballot(hit);
           if (FILL && hit) tmp_keys[w + __popcll(m & ((1ull << lane) - 1ull))] = j;
@@ -694,6 +699,99 @@ static void tables_host(const T* cell, int64_t G, const int32_t reps[3], double 
     CellGeom<T> cg;
     cell_geom<T>(a, cg);
     cell_table_prune<T>(cg, cutoff, recip + 9 * g, thr + 3 * g);
+  }
+}
+
+// ---- the neighbour search's host side (include/xeq.h: xeq_neighbor_search; the three entries are at the end of this file) ----
+enum { NB_BIN_IDS, NB_COUNT, NB_FILL };
+struct NbMember {
+  const char* name;
+  const void* p;
+  bool needed;
+};
+
+// Every check of the three entries, made before anything is launched.  XEQ_OK with *run == false: nothing to launch (no nodes, or
+// a fill of no edges).  `outputs`: the entry's own pointer arguments, checked like the record's members.
+static int neighbors_check(const char* who, const xeq_neighbor_search* s, int pass, int64_t n_edges, std::initializer_list<NbMember> outputs,
+                           bool* run) {
+  *run = false;
+  XEQ_CHECK_ARG(s, "%s: null argument record", who);
+  XEQ_CHECK_ARG(s->dtype == XEQ_F32 || s->dtype == XEQ_F64, "%s: dtype %lld (0 f32, 1 f64)", who, (long long)s->dtype);
+  const int64_t kind = s->kind;
+  XEQ_CHECK_ARG(kind >= XEQ_NEIGHBORS_OPEN_SWEEP && kind <= XEQ_NEIGHBORS_PBC_BINS,
+                "%s: kind %lld (0 open sweep, 1 open bins, 2 periodic all images, 3 periodic pruned, 4 periodic bins)", who, (long long)kind);
+  const bool search = pass != NB_BIN_IDS, fill = pass == NB_FILL;
+  const bool bins = kind == XEQ_NEIGHBORS_OPEN_BINS || kind == XEQ_NEIGHBORS_PBC_BINS, open_bins = kind == XEQ_NEIGHBORS_OPEN_BINS;
+  const bool periodic = kind >= XEQ_NEIGHBORS_PBC_ALL, pruned = kind >= XEQ_NEIGHBORS_PBC_PRUNED;
+  XEQ_CHECK_ARG(search || bins, "%s: kind %lld has no bin grid", who, (long long)kind);
+  XEQ_CHECK_ARG(s->n_graphs >= 0 && s->n_nodes >= 0 && n_edges >= 0, "%s: negative size (n_graphs %lld, n_nodes %lld, n_edges %lld)", who,
+                (long long)s->n_graphs, (long long)s->n_nodes, (long long)n_edges);
+  if (periodic && search) {
+    XEQ_CHECK_ARG(s->n_cells > 0, "%s: n_cells %lld", who, (long long)s->n_cells);
+    if (pruned) {
+      const int64_t* r = s->reps;
+      XEQ_CHECK_ARG(r[0] >= 0 && r[1] >= 0 && r[2] >= 0 && r[0] < 65536 && r[1] < 65536 && r[2] < 65536 &&
+                        (2 * r[0] + 1) * (2 * r[1] + 1) * (2 * r[2] + 1) == s->n_cells,
+                    "%s: reps (%lld, %lld, %lld) do not match n_cells %lld", who, (long long)r[0], (long long)r[1], (long long)r[2],
+                    (long long)s->n_cells);
+    }
+  }
+  if (s->n_nodes == 0 || (fill && n_edges == 0)) return XEQ_OK;
+  XEQ_CHECK_ARG(s->n_graphs > 0, "%s: n_nodes %lld with n_graphs 0", who, (long long)s->n_nodes);
+  const NbMember members[] = {{"pos", s->pos, true},
+                              {"ptr", s->ptr, true},
+                              {"img", s->img, periodic && search},
+                              {"cells", s->cells, periodic && fill},
+                              {"shift", s->shift, periodic && fill},
+                              {"recip", s->recip, pruned},
+                              {"thr", s->thr, pruned && search},
+                              {"lo", s->lo, open_bins},
+                              {"inv_w", s->inv_w, open_bins},
+                              {"nbins", s->nbins, bins},
+                              {"bin_base", s->bin_base, bins},
+                              {"bin_start", s->bin_start, bins && search},
+                              {"bin_atom", s->bin_atom, bins && search}};
+  for (const NbMember& m : members) XEQ_CHECK_ARG(!m.needed || m.p, "%s: member %s is NULL (kind %lld reads it)", who, m.name, (long long)kind);
+  for (const NbMember& m : outputs) XEQ_CHECK_ARG(!m.needed || m.p, "%s: %s is NULL (kind %lld needs it)", who, m.name, (long long)kind);
+  *run = true;
+  return XEQ_OK;
+}
+
+// The counting (FILL = false) or writing pass of the record's kind: one wave per center, four centers per workgroup; the bin-grid
+// kinds' writing pass is followed by the ranking of every center's segment.
+template <typename T, bool FILL>
+static void neighbors_launch(const xeq_neighbor_search* s, int32_t* deg, const int32_t* rowptr, int64_t n_edges, int64_t* tmp_keys,
+                             int64_t* edge_index, void* cell_offsets, hipStream_t st) {
+  const int64_t G = s->n_graphs, N = s->n_nodes, nc = s->n_cells;
+  const dim3 grid((unsigned)((N + 3) / 4)), block(256);
+  const T *pos = (const T*)s->pos, *img = (const T*)s->img, *cells = (const T*)s->cells, *shift = (const T*)s->shift;
+  const T *recip = (const T*)s->recip, *thr = (const T*)s->thr, *lo = (const T*)s->lo, *inv_w = (const T*)s->inv_w;
+  const T rc = (T)s->cutoff;
+  const PbcPrune pr{{(int)s->reps[0], (int)s->reps[1], (int)s->reps[2]}};
+  switch (s->kind) {
+    case XEQ_NEIGHBORS_OPEN_SWEEP:
+      hipLaunchKernelGGL((k_radius_graph<T, FILL>), grid, block, 0, st, pos, s->ptr, G, N, rc * rc, deg, rowptr, n_edges, edge_index);
+      break;
+    case XEQ_NEIGHBORS_OPEN_BINS:
+      hipLaunchKernelGGL((k_radius_graph_cl<T, FILL>), grid, block, 0, st, pos, s->ptr, G, N, rc * rc, lo, inv_w, s->nbins, s->bin_base,
+                         s->bin_start, s->bin_atom, deg, rowptr, tmp_keys);
+      if (FILL) hipLaunchKernelGGL(k_sort_segment_plain, grid, block, 0, st, (const int64_t*)tmp_keys, rowptr, N, n_edges, edge_index);
+      break;
+    case XEQ_NEIGHBORS_PBC_ALL:
+      hipLaunchKernelGGL((k_radius_graph_pbc<T, FILL>), grid, block, 0, st, pos, s->ptr, G, N, img, cells, shift, nc, rc, deg, rowptr, n_edges,
+                         edge_index, (T*)cell_offsets);
+      break;
+    case XEQ_NEIGHBORS_PBC_PRUNED:
+      hipLaunchKernelGGL((k_radius_graph_pbc_img<T, FILL>), grid, block, 0, st, pos, s->ptr, G, N, img, cells, shift, nc, rc, recip, thr, pr, deg,
+                         rowptr, n_edges, edge_index, (T*)cell_offsets);
+      break;
+    case XEQ_NEIGHBORS_PBC_BINS:
+      hipLaunchKernelGGL((k_radius_graph_pbc_cl<T, FILL>), grid, block, 0, st, pos, s->ptr, G, N, img, nc, rc, recip, thr, pr, s->nbins,
+                         s->bin_base, s->bin_start, s->bin_atom, deg, rowptr, tmp_keys);
+      if (FILL)
+        hipLaunchKernelGGL((k_pbc_sort_segment<T>), grid, block, 0, st, (const int64_t*)tmp_keys, rowptr, s->ptr, G, N, nc, cells, shift, n_edges,
+                           edge_index, (T*)cell_offsets);
+      break;
   }
 }
 }  // namespace xeq
@@ -866,36 +964,6 @@ int xeq_reverse_edge_map_pbc(int dtype, const int64_t* edge_index, const void* c
   return XEQ_OK;
 }
 
-int xeq_radius_graph_count(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                           double cutoff, int32_t* deg, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0, "xeq_radius_graph_count: negative size");
-  if (n_nodes == 0) return XEQ_OK;
-  XEQ_CHECK_ARG(n_graphs > 0, "xeq_radius_graph_count: nodes without graphs");
-  XEQ_DISPATCH_FLOAT(dtype, {
-    T rc = (T)cutoff;
-    hipLaunchKernelGGL((k_radius_graph<T, false>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos, ptr, n_graphs, n_nodes, rc * rc, deg,
-                       (const int32_t*)nullptr, (int64_t)0, (int64_t*)nullptr);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_count");
-  return XEQ_OK;
-}
-
-int xeq_radius_graph_fill(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                          double cutoff, const int32_t* rowptr, int64_t n_edges, int64_t* edge_index,
-                          void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_edges >= 0, "xeq_radius_graph_fill: negative size");
-  if (n_nodes == 0 || n_edges == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    T rc = (T)cutoff;
-    hipLaunchKernelGGL((k_radius_graph<T, true>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos, ptr, n_graphs, n_nodes, rc * rc, (int32_t*)nullptr,
-                       rowptr, n_edges, edge_index);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_fill");
-  return XEQ_OK;
-}
-
 /* Capacity form of the open-boundary list (runtime.GraphedStep): count[0] = raw[n_nodes], the true edge count, and rowptr = raw when the
  * list fits the capacity, ALL ZEROS (an empty list) when it does not.  A list cut at the capacity would no longer be symmetric, and the
  * symmetric shortcuts downstream (reverse-edge map, mirror walk) index by the reverse edge; an empty list is safe for every kernel.
@@ -966,176 +1034,46 @@ int xeq_pbc_wrap(int dtype, const void* pos, const int64_t* ptr, int64_t n_graph
   return XEQ_OK;
 }
 
-int xeq_radius_graph_pbc_count(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                               int64_t n_nodes, const void* img, int64_t n_cells, double cutoff, int32_t* deg,
-                               void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_cells > 0, "xeq_radius_graph_pbc_count: bad sizes");
-  if (n_nodes == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_radius_graph_pbc<T, false>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos_wrap, ptr, n_graphs, n_nodes, (const T*)img,
-                       (const T*)nullptr, (const T*)nullptr, n_cells, (T)cutoff, deg, (const int32_t*)nullptr,
-                       (int64_t)0, (int64_t*)nullptr, (T*)nullptr);
+/* ---- the neighbour search: one argument record, five kinds (include/xeq.h: xeq_neighbor_search; checks and launches above) */
+int xeq_neighbors_bin_ids(const xeq_neighbor_search* s, int64_t* keys, void* stream) {
+  bool run;
+  const int status = neighbors_check("xeq_neighbors_bin_ids", s, NB_BIN_IDS, 0, {{"keys", keys, true}}, &run);
+  if (status != XEQ_OK || !run) return status;
+  const int64_t G = s->n_graphs, N = s->n_nodes;
+  const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+  XEQ_DISPATCH_FLOAT(s->dtype, {
+    if (s->kind == XEQ_NEIGHBORS_OPEN_BINS)
+      hipLaunchKernelGGL((k_box_bin_ids<T>), grid, block, 0, (hipStream_t)stream, (const T*)s->pos, s->ptr, G, N, (const T*)s->lo,
+                         (const T*)s->inv_w, s->nbins, s->bin_base, keys);
+    else
+      hipLaunchKernelGGL((k_pbc_bin_ids<T>), grid, block, 0, (hipStream_t)stream, (const T*)s->pos, s->ptr, G, N, (const T*)s->recip, s->nbins,
+                         s->bin_base, keys);
   });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_pbc_count");
+  XEQ_CHECK_LAUNCH("xeq_neighbors_bin_ids");
   return XEQ_OK;
 }
 
-int xeq_radius_graph_pbc_fill(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                              int64_t n_nodes, const void* img, const void* cells, const void* shift,
-                              int64_t n_cells, double cutoff, const int32_t* rowptr, int64_t n_edges,
-                              int64_t* edge_index, void* cell_offsets, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_cells > 0 && n_edges >= 0, "xeq_radius_graph_pbc_fill: bad sizes");
-  if (n_nodes == 0 || n_edges == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_radius_graph_pbc<T, true>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos_wrap, ptr, n_graphs, n_nodes, (const T*)img,
-                       (const T*)cells, (const T*)shift, n_cells, (T)cutoff, (int32_t*)nullptr, rowptr, n_edges,
-                       edge_index, (T*)cell_offsets);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_pbc_fill");
+int xeq_neighbors_count(const xeq_neighbor_search* s, int32_t* deg, void* stream) {
+  bool run;
+  const int status = neighbors_check("xeq_neighbors_count", s, NB_COUNT, 0, {{"deg", deg, true}}, &run);
+  if (status != XEQ_OK || !run) return status;
+  XEQ_DISPATCH_FLOAT(s->dtype, { neighbors_launch<T, false>(s, deg, nullptr, 0, nullptr, nullptr, nullptr, (hipStream_t)stream); });
+  XEQ_CHECK_LAUNCH("xeq_neighbors_count");
   return XEQ_OK;
 }
 
-int xeq_radius_graph_pbc_count_pruned(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                                      int64_t n_nodes, const void* img, int64_t n_cells, double cutoff, const void* recip,
-                                      const void* thr, const int32_t reps[3], int32_t* deg, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_cells > 0, "xeq_radius_graph_pbc_count_pruned: bad sizes");
-  XEQ_CHECK_ARG(reps[0] >= 0 && reps[1] >= 0 && reps[2] >= 0 &&
-                    (int64_t)(2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1) == n_cells,
-                "xeq_radius_graph_pbc_count_pruned: image counts (%d,%d,%d) do not match n_cells %lld", reps[0], reps[1],
-                reps[2], (long long)n_cells);
-  if (n_nodes == 0) return XEQ_OK;
-  PbcPrune pr{{reps[0], reps[1], reps[2]}};
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_radius_graph_pbc_img<T, false>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos_wrap, ptr, n_graphs, n_nodes, (const T*)img, (const T*)nullptr,
-                       (const T*)nullptr, n_cells, (T)cutoff, (const T*)recip, (const T*)thr, pr, deg,
-                       (const int32_t*)nullptr, (int64_t)0, (int64_t*)nullptr, (T*)nullptr);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_pbc_count_pruned");
-  return XEQ_OK;
-}
-
-int xeq_radius_graph_pbc_fill_pruned(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs,
-                                     int64_t n_nodes, const void* img, const void* cells, const void* shift, int64_t n_cells,
-                                     double cutoff, const void* recip, const void* thr, const int32_t reps[3],
-                                     const int32_t* rowptr, int64_t n_edges, int64_t* edge_index, void* cell_offsets,
-                                     void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_cells > 0 && n_edges >= 0, "xeq_radius_graph_pbc_fill_pruned: bad sizes");
-  XEQ_CHECK_ARG((int64_t)(2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1) == n_cells,
-                "xeq_radius_graph_pbc_fill_pruned: image counts do not match n_cells");
-  if (n_nodes == 0 || n_edges == 0) return XEQ_OK;
-  PbcPrune pr{{reps[0], reps[1], reps[2]}};
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_radius_graph_pbc_img<T, true>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos_wrap, ptr, n_graphs, n_nodes, (const T*)img, (const T*)cells,
-                       (const T*)shift, n_cells, (T)cutoff, (const T*)recip, (const T*)thr, pr, (int32_t*)nullptr, rowptr,
-                       n_edges, edge_index, (T*)cell_offsets);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_pbc_fill_pruned");
-  return XEQ_OK;
-}
-
-/* ---- cell-list form (graphs of many atoms): see k_radius_graph_pbc_cl */
-int xeq_radius_graph_pbc_bin_ids(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                                 const void* recip, const int32_t* nbins, const int32_t* bin_base, int64_t* keys, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0, "xeq_radius_graph_pbc_bin_ids: bad sizes");
-  if (n_nodes == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_pbc_bin_ids<T>), dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const T*)pos_wrap, ptr, n_graphs, n_nodes, (const T*)recip, nbins, bin_base, keys);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_pbc_bin_ids");
-  return XEQ_OK;
-}
-
-int xeq_radius_graph_pbc_count_cl(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                                  const void* img, int64_t n_cells, double cutoff, const void* recip, const void* thr,
-                                  const int32_t reps[3], const int32_t* nbins, const int32_t* bin_base,
-                                  const int32_t* bin_start, const int32_t* bin_atom, int32_t* deg, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_cells > 0, "xeq_radius_graph_pbc_count_cl: bad sizes");
-  XEQ_CHECK_ARG((int64_t)(2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1) == n_cells,
-                "xeq_radius_graph_pbc_count_cl: image counts do not match n_cells");
-  if (n_nodes == 0) return XEQ_OK;
-  PbcPrune pr{{reps[0], reps[1], reps[2]}};
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_radius_graph_pbc_cl<T, false>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos_wrap, ptr, n_graphs, n_nodes, (const T*)img, n_cells, (T)cutoff,
-                       (const T*)recip, (const T*)thr, pr, nbins, bin_base, bin_start, bin_atom, deg,
-                       (const int32_t*)nullptr, (int64_t*)nullptr);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_pbc_count_cl");
-  return XEQ_OK;
-}
-
-int xeq_radius_graph_pbc_fill_cl(int dtype, const void* pos_wrap, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes,
-                                 const void* img, const void* cells, const void* shift, int64_t n_cells, double cutoff,
-                                 const void* recip, const void* thr, const int32_t reps[3], const int32_t* nbins,
-                                 const int32_t* bin_base, const int32_t* bin_start, const int32_t* bin_atom,
-                                 const int32_t* rowptr, int64_t n_edges, int64_t* tmp_keys, int64_t* edge_index,
-                                 void* cell_offsets, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_cells > 0 && n_edges >= 0, "xeq_radius_graph_pbc_fill_cl: bad sizes");
-  XEQ_CHECK_ARG((int64_t)(2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1) == n_cells,
-                "xeq_radius_graph_pbc_fill_cl: image counts do not match n_cells");
-  if (n_nodes == 0 || n_edges == 0) return XEQ_OK;
-  PbcPrune pr{{reps[0], reps[1], reps[2]}};
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_radius_graph_pbc_cl<T, true>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0,
-                       (hipStream_t)stream, (const T*)pos_wrap, ptr, n_graphs, n_nodes, (const T*)img, n_cells, (T)cutoff,
-                       (const T*)recip, (const T*)thr, pr, nbins, bin_base, bin_start, bin_atom, (int32_t*)nullptr, rowptr,
-                       tmp_keys);
-    hipLaunchKernelGGL((k_pbc_sort_segment<T>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const int64_t*)tmp_keys, rowptr, ptr, n_graphs, n_nodes, n_cells, (const T*)cells, (const T*)shift,
-                       n_edges, edge_index, (T*)cell_offsets);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_pbc_fill_cl");
-  return XEQ_OK;
-}
-
-/* ---- open-boundary cell list: see k_radius_graph_cl */
-int xeq_radius_graph_bin_ids(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes, const void* lo,
-                             const void* inv_w, const int32_t* nbins, const int32_t* bin_base, int64_t* keys, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0, "xeq_radius_graph_bin_ids: bad sizes");
-  if (n_nodes == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    hipLaunchKernelGGL((k_box_bin_ids<T>), dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const T*)pos, ptr, n_graphs, n_nodes, (const T*)lo, (const T*)inv_w, nbins, bin_base, keys);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_bin_ids");
-  return XEQ_OK;
-}
-
-int xeq_radius_graph_count_cl(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes, double cutoff,
-                              const void* lo, const void* inv_w, const int32_t* nbins, const int32_t* bin_base,
-                              const int32_t* bin_start, const int32_t* bin_atom, int32_t* deg, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0, "xeq_radius_graph_count_cl: bad sizes");
-  if (n_nodes == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    T rc = (T)cutoff;
-    hipLaunchKernelGGL((k_radius_graph_cl<T, false>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const T*)pos, ptr, n_graphs, n_nodes, rc * rc, (const T*)lo, (const T*)inv_w, nbins, bin_base, bin_start,
-                       bin_atom, deg, (const int32_t*)nullptr, (int64_t*)nullptr);
-  });
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_count_cl");
-  return XEQ_OK;
-}
-
-int xeq_radius_graph_fill_cl(int dtype, const void* pos, const int64_t* ptr, int64_t n_graphs, int64_t n_nodes, double cutoff,
-                             const void* lo, const void* inv_w, const int32_t* nbins, const int32_t* bin_base,
-                             const int32_t* bin_start, const int32_t* bin_atom, const int32_t* rowptr, int64_t n_edges,
-                             int64_t* tmp_keys, int64_t* edge_index, void* stream) {
-  XEQ_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_edges >= 0, "xeq_radius_graph_fill_cl: bad sizes");
-  if (n_nodes == 0 || n_edges == 0) return XEQ_OK;
-  XEQ_DISPATCH_FLOAT(dtype, {
-    T rc = (T)cutoff;
-    hipLaunchKernelGGL((k_radius_graph_cl<T, true>), dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const T*)pos, ptr, n_graphs, n_nodes, rc * rc, (const T*)lo, (const T*)inv_w, nbins, bin_base, bin_start,
-                       bin_atom, (int32_t*)nullptr, rowptr, tmp_keys);
-  });
-  hipLaunchKernelGGL(k_sort_segment_plain, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     (const int64_t*)tmp_keys, rowptr, n_nodes, n_edges, edge_index);
-  XEQ_CHECK_LAUNCH("xeq_radius_graph_fill_cl");
+int xeq_neighbors_fill(const xeq_neighbor_search* s, const int32_t* rowptr, int64_t n_edges, int64_t* tmp_keys, int64_t* edge_index,
+                       void* cell_offsets, void* stream) {
+  bool run;
+  const bool bins = s && (s->kind == XEQ_NEIGHBORS_OPEN_BINS || s->kind == XEQ_NEIGHBORS_PBC_BINS);
+  const bool periodic = s && s->kind >= XEQ_NEIGHBORS_PBC_ALL;
+  const int status = neighbors_check("xeq_neighbors_fill", s, NB_FILL, n_edges,
+                                     {{"rowptr", rowptr, true}, {"tmp_keys", tmp_keys, bins}, {"edge_index", edge_index, true},
+                                      {"cell_offsets", cell_offsets, periodic}},
+                                     &run);
+  if (status != XEQ_OK || !run) return status;
+  XEQ_DISPATCH_FLOAT(s->dtype, { neighbors_launch<T, true>(s, nullptr, rowptr, n_edges, tmp_keys, edge_index, cell_offsets, (hipStream_t)stream); });
+  XEQ_CHECK_LAUNCH("xeq_neighbors_fill");
   return XEQ_OK;
 }
 

@@ -934,6 +934,7 @@ int64_t xeq_record_bytes(int which) {
     case XEQ_REC_MD: return sizeof(xeq_md_params);
     case XEQ_REC_NPT: return sizeof(xeq_npt_params);
     case XEQ_REC_FIRE: return sizeof(xeq_fire_params);
+    case XEQ_REC_NEIGHBORS: return sizeof(xeq_neighbor_search);
   }
   return -1;
 }

@@ -1169,25 +1169,36 @@ std::vector<Tensor> xpainn_eval(const Tensor& pos, const Tensor& atomic_numbers,
                              compute_forces, compute_virial, charge, spin);
 }
 
-// open-boundary neighbour list; one device-to-host read of the edge count, as the reference's nonzero()
+// count -> scan -> size -> fill on a filled search record (include/xeq.h: xeq_neighbor_search), the host path of both registered
+// list operators: one device-to-host read of the edge count, as the reference's nonzero().  -> (edge_index [2, E], cell_offsets
+// [E, 3] for the periodic kinds, else undefined, rowptr [N + 1])
+static std::tuple<Tensor, Tensor, Tensor> neighbor_list(const xeq_neighbor_search& s, const Tensor& pos, const Tensor& ptr64, const char* who) {
+  const int64_t N = s.n_nodes;
+  Tensor deg = i32(N, ptr64), rowptr = i32(N + 1, ptr64);
+  void* st = cur_stream();
+  XCALL(xeq_neighbors_count(&s, (int32_t*)deg.data_ptr(), st));
+  const int64_t scan_bytes = xeq_exclusive_scan_i32_workspace(N);
+  TORCH_CHECK(scan_bytes >= 0, who, ": too many nodes");
+  Tensor scan_work = at::empty({std::max<int64_t>(scan_bytes, 1)}, pos.options().dtype(at::kByte));
+  XCALL(xeq_exclusive_scan_i32_ws((const int32_t*)deg.data_ptr(), N, (int32_t*)rowptr.data_ptr(), scan_work.data_ptr(), scan_bytes, st));
+  const int64_t E = N > 0 ? (int64_t)rowptr[N].item<int32_t>() : 0;
+  Tensor ei = at::empty({2, E}, ptr64.options()), cell_offsets;
+  if (s.kind >= XEQ_NEIGHBORS_PBC_ALL) cell_offsets = at::empty({E, 3}, pos.options());
+  XCALL(xeq_neighbors_fill(&s, (const int32_t*)rowptr.data_ptr(), E, nullptr, (int64_t*)ei.data_ptr(),
+                           cell_offsets.defined() ? cell_offsets.data_ptr() : nullptr, st));
+  return {ei, cell_offsets, rowptr};
+}
+
+// open-boundary neighbour list (the pair sweep)
 std::tuple<Tensor, Tensor> radius_graph(const Tensor& pos_in, const Tensor& ptr, double cutoff) {
   need_hip(pos_in, "pos");
   const Tensor pos = pos_in.detach().contiguous();
   const Tensor ptr64 = ptr.to(at::kLong).contiguous();
-  const int64_t N = pos.size(0), G = ptr64.numel() - 1;
-  const int dt = dcode(pos);
-  Tensor deg = i32(N, ptr64), rowptr = i32(N + 1, ptr64);
-  void* st = cur_stream();
-  XCALL(xeq_radius_graph_count(dt, pos.data_ptr(), (const int64_t*)ptr64.data_ptr(), G, N, cutoff, (int32_t*)deg.data_ptr(), st));
-  const int64_t scan_bytes = xeq_exclusive_scan_i32_workspace(N);
-  TORCH_CHECK(scan_bytes >= 0, "xeq::radius_graph: too many nodes");
-  Tensor scan_work = at::empty({std::max<int64_t>(scan_bytes, 1)}, pos.options().dtype(at::kByte));
-  XCALL(xeq_exclusive_scan_i32_ws((const int32_t*)deg.data_ptr(), N, (int32_t*)rowptr.data_ptr(), scan_work.data_ptr(), scan_bytes, st));
-  const int64_t E = N > 0 ? (int64_t)rowptr[N].item<int32_t>() : 0;
-  Tensor ei = at::empty({2, E}, ptr64.options());
-  XCALL(xeq_radius_graph_fill(dt, pos.data_ptr(), (const int64_t*)ptr64.data_ptr(), G, N, cutoff, (const int32_t*)rowptr.data_ptr(), E,
-                              (int64_t*)ei.data_ptr(), st));
-  return {ei, rowptr.narrow(0, 0, N + 1)};
+  xeq_neighbor_search s = {};
+  s.dtype = dcode(pos), s.kind = XEQ_NEIGHBORS_OPEN_SWEEP, s.n_graphs = ptr64.numel() - 1, s.n_nodes = pos.size(0), s.cutoff = cutoff;
+  s.pos = pos.data_ptr(), s.ptr = (const int64_t*)ptr64.data_ptr();
+  const auto out = neighbor_list(s, pos, ptr64, "xeq::radius_graph");
+  return {std::get<0>(out), std::get<2>(out)};
 }
 
 // periodic neighbour list of ONE system (data/radius_graph.py:195-275): positions are not wrapped, cell [3, 3], pbc [3].
@@ -1214,21 +1225,12 @@ std::tuple<Tensor, Tensor, Tensor> radius_graph_pbc(const Tensor& pos_in, const 
                thr = tab.narrow(0, 6 * nc + 9, 3);
   const Tensor ptr64 = at::tensor({(int64_t)0, N}, at::TensorOptions().dtype(at::kLong)).to(pos.device());
   const Tensor shift = at::zeros_like(pos);
-  Tensor deg = i32(N, ptr64), rowptr = i32(N + 1, ptr64);
-  void* st = cur_stream();
-  XCALL(xeq_radius_graph_pbc_count_pruned(dt, pos.data_ptr(), (const int64_t*)ptr64.data_ptr(), 1, N, offs.data_ptr(), nc, cutoff,
-                                          recip.data_ptr(), thr.data_ptr(), reps, (int32_t*)deg.data_ptr(), st));
-  const int64_t scan_bytes = xeq_exclusive_scan_i32_workspace(N);
-  TORCH_CHECK(scan_bytes >= 0, "xeq::radius_graph_pbc: too many nodes");
-  Tensor scan_work = at::empty({std::max<int64_t>(scan_bytes, 1)}, pos.options().dtype(at::kByte));
-  XCALL(xeq_exclusive_scan_i32_ws((const int32_t*)deg.data_ptr(), N, (int32_t*)rowptr.data_ptr(), scan_work.data_ptr(), scan_bytes, st));
-  const int64_t E = N > 0 ? (int64_t)rowptr[N].item<int32_t>() : 0;                          // round trip 2
-  Tensor ei = at::empty({2, E}, ptr64.options());
-  Tensor cell_offsets = at::empty({E, 3}, pos.options());
-  XCALL(xeq_radius_graph_pbc_fill_pruned(dt, pos.data_ptr(), (const int64_t*)ptr64.data_ptr(), 1, N, offs.data_ptr(), grid.data_ptr(),
-                                         shift.data_ptr(), nc, cutoff, recip.data_ptr(), thr.data_ptr(), reps,
-                                         (const int32_t*)rowptr.data_ptr(), E, (int64_t*)ei.data_ptr(), cell_offsets.data_ptr(), st));
-  return {ei, cell_offsets, rowptr};
+  xeq_neighbor_search s = {};
+  s.dtype = dt, s.kind = XEQ_NEIGHBORS_PBC_PRUNED, s.n_graphs = 1, s.n_nodes = N, s.n_cells = nc, s.cutoff = cutoff;
+  s.reps[0] = reps[0], s.reps[1] = reps[1], s.reps[2] = reps[2];
+  s.pos = pos.data_ptr(), s.ptr = (const int64_t*)ptr64.data_ptr(), s.img = offs.data_ptr(), s.cells = grid.data_ptr();
+  s.shift = shift.data_ptr(), s.recip = recip.data_ptr(), s.thr = thr.data_ptr();
+  return neighbor_list(s, pos, ptr64, "xeq::radius_graph_pbc");                              // round trip 2: the edge count
 }
 
 // ---------------------------------------------------------------------------------------------- linear layers of the training pass

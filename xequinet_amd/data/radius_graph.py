@@ -4,7 +4,7 @@ Host-side preparation follows the reference line by line in meaning (image count
 :61-89, image table :93-104, wrapping :6-32/:111-116) using torch ops on the
 device, so that the per-pair arithmetic the HIP search kernel sees is the
 reference's; the O(n^2 n_cells) cdist/nonzero search and the Python loop over
-graphs (:118-181) are replaced by ``xeq_radius_graph_pbc_{count,fill}``."""
+graphs (:118-181) are replaced by ``xeq_neighbors_count`` / ``xeq_neighbors_fill`` on a periodic ``xeq_neighbor_search``."""
 from __future__ import annotations
 
 from typing import List, Tuple

@@ -45,8 +45,8 @@ def _record(c_name: str, *groups):
     return type(c_name, (ctypes.Structure,), {"_fields_": [(name, kind) for kind, names in groups for name in names.split()]})
 
 
-# The argument records of the resident drivers' front / back entries (resident.py), member for member those of include/xeq.h; every
-# member is 8 bytes wide.  In the order of XEQ_REC_*: load() holds their sizes against xeq_record_bytes.
+# The argument records of the resident drivers' front / back entries (resident.py) and of the neighbour search, member for member those
+# of include/xeq.h; every member is 8 bytes wide.  In the order of XEQ_REC_*: load() holds their sizes against xeq_record_bytes.
 ResSystem = _record("xeq_res_system", (c_int64, "dtype n n_graphs n_chunks"), (_P, "pos vel frc image batch book cell pbc"))
 ResStep = _record("xeq_res_step", (_P, "frc_step energy_step n_edges_step virial_step reps_needed"), (c_int64 * 3, "reps"))
 ResChunks = _record("xeq_res_chunks", (_P, "chunk_atom0 chunk_n graph_chunk_ptr partial partial_bad"))
@@ -56,7 +56,11 @@ MdParams = _record("xeq_md_params", (c_int64, "ensemble"), (_P, "inv_mass half_m
 NptParams = _record("xeq_npt_params", (_P, "box step_cell virial reps_seen"), (c_double, "kappa p0 p_unit"))
 FireParams = _record("xeq_fire_params", (_P, "fixed epot fmax dt alpha n_pos status converged_at coef"), (c_double, "fmax_tol maxstep dtmax"),
                      (c_int64, "n_min"), (c_double, "f_inc f_dec alpha_start f_alpha"))
-RECORDS = [ResSystem, ResStep, ResChunks, ResRecorder, MdParams, NptParams, FireParams]
+# The neighbour search's record (ops._neighbor_list); kinds: XEQ_NEIGHBORS_* of include/xeq.h
+NeighborSearch = _record("xeq_neighbor_search", (c_int64, "dtype kind n_graphs n_nodes n_cells"), (c_double, "cutoff"), (c_int64 * 3, "reps"),
+                         (_P, "pos ptr img cells shift recip thr lo inv_w nbins bin_base bin_start bin_atom"))
+NEIGHBORS_OPEN_SWEEP, NEIGHBORS_OPEN_BINS, NEIGHBORS_PBC_ALL, NEIGHBORS_PBC_PRUNED, NEIGHBORS_PBC_BINS = range(5)
+RECORDS = [ResSystem, ResStep, ResChunks, ResRecorder, MdParams, NptParams, FireParams, NeighborSearch]
 _R = ctypes.POINTER
 
 
@@ -88,23 +92,12 @@ _PROTOS = {
     "xeq_exclusive_scan_i32_ws": [_P, c_int64, _P, _P, c_int64, _P],
     "xeq_reverse_edge_map": [_P, c_int64, c_int64, _P, _P, _P],
     "xeq_reverse_edge_map_pbc": [c_int, _P, _P, c_int64, c_int64, _P, _P, _P],
-    "xeq_radius_graph_count": [c_int, _P, _P, c_int64, c_int64, c_double, _P, _P],
-    "xeq_radius_graph_fill": [c_int, _P, _P, c_int64, c_int64, c_double, _P, c_int64, _P, _P],
-    "xeq_radius_graph_bin_ids": [c_int, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P],
-    "xeq_radius_graph_count_cl": [c_int, _P, _P, c_int64, c_int64, c_double, _P, _P, _P, _P, _P, _P, _P, _P],
-    "xeq_radius_graph_fill_cl": [c_int, _P, _P, c_int64, c_int64, c_double, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P],
+    "xeq_neighbors_bin_ids": [_R(NeighborSearch), _P, _P],
+    "xeq_neighbors_count": [_R(NeighborSearch), _P, _P],
+    "xeq_neighbors_fill": [_R(NeighborSearch), _P, c_int64, _P, _P, _P, _P],
     "xeq_pbc_image_counts": [c_int, _P, c_int64, _I3, c_double, _I3],
     "xeq_pbc_tables_host": [c_int, _P, c_int64, _I3, c_double, _P, c_int64],
     "xeq_pbc_wrap": [c_int, _P, _P, c_int64, c_int64, _P, _P, _I3, _P, _P, _P],
-    "xeq_radius_graph_pbc_count": [c_int, _P, _P, c_int64, c_int64, _P, c_int64, c_double, _P, _P],
-    "xeq_radius_graph_pbc_fill": [c_int, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_double, _P, c_int64, _P, _P, _P],
-    "xeq_radius_graph_pbc_count_pruned": [c_int, _P, _P, c_int64, c_int64, _P, c_int64, c_double, _P, _P, _I3, _P, _P],
-    "xeq_radius_graph_pbc_fill_pruned": [c_int, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_double, _P, _P, _I3, _P, c_int64,
-                                         _P, _P, _P],
-    "xeq_radius_graph_pbc_bin_ids": [c_int, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P],
-    "xeq_radius_graph_pbc_count_cl": [c_int, _P, _P, c_int64, c_int64, _P, c_int64, c_double, _P, _P, _I3, _P, _P, _P, _P, _P, _P],
-    "xeq_radius_graph_pbc_fill_cl": [c_int, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_double, _P, _P, _I3, _P, _P, _P, _P,
-                                     _P, c_int64, _P, _P, _P, _P],
     "xeq_edge_vectors_fwd": [c_int, _P, _P, c_int64, _P, _P, _P, _P, _P, _P],
     "xeq_edge_vectors_bwd": [c_int, _P, c_int64, _P, _P, _P, _P, _P, _P],
     "xeq_sph_harm_fwd": [c_int, _P, c_int64, _I3, c_int, _P, _P],

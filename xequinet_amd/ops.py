@@ -284,27 +284,80 @@ def _box_grid(pos, ptr_, cutoff):
     return lo.contiguous(), nb.contiguous(), inv_w
 
 
-def _radius_graph_cell_list(pos, ptr_, cutoff):
-    """Open-boundary neighbour list through a per-graph bin grid (xeq_radius_graph_*_cl): O(N) instead of O(n_g^2)."""
-    N, G = pos.shape[0], ptr_.numel() - 1
-    dev, dt = pos.device, dtype_code(pos)
-    lo, nb, inv_w = _box_grid(pos, ptr_, cutoff)
-    bin_base = torch.zeros(G + 1, dtype=torch.int32, device=dev)
-    bin_base[1:] = torch.cumsum(nb.prod(dim=1), 0)
-    n_bins = int(bin_base[-1].item())
-    keys_ = torch.empty(N, dtype=torch.int64, device=dev)
-    call("xeq_radius_graph_bin_ids", dt, ptr(pos), ptr(ptr_), G, N, ptr(lo), ptr(inv_w), ptr(nb), ptr(bin_base), ptr(keys_), stream())
-    bin_start, bin_atom = csr_by_key(keys_, n_bins)
+def _search_record(kind: int, pos, ptr_, cutoff, **members):
+    """A filled xeq_neighbor_search (include/xeq.h).  The record holds addresses only: the caller keeps the tensors alive."""
+    return lib.fill(lib.NeighborSearch(), dtype=dtype_code(pos), kind=kind, n_graphs=ptr_.numel() - 1, n_nodes=pos.shape[0],
+                    cutoff=float(cutoff), pos=pos, ptr=ptr_, **members)
+
+
+def _bin_base(nbins):
+    """(bin_base [G + 1] int32: the running bin count of the graphs, its total).  The total is a host value: one read-back."""
+    bin_base = torch.zeros(nbins.shape[0] + 1, dtype=torch.int32, device=nbins.device)
+    bin_base[1:] = torch.cumsum(nbins.prod(dim=1), 0)
+    return bin_base, int(bin_base[-1].item())
+
+
+def _guard_empty(deg, N, cap, rowptr, running_total):
+    """Capacity guard of the open form -> count [1]: a list that outgrew the capacity is replaced by an EMPTY one."""
+    count = torch.empty(1, dtype=torch.int32, device=deg.device)
+    if N <= _scan_one_launch_max():     # scan, total and capacity guard by one workgroup in one launch (three before)
+        call("xeq_rowptr_from_degrees", ptr(deg), N, cap, ptr(rowptr), ptr(count), ptr(running_total), stream())
+    else:
+        raw = torch.empty(N + 1, dtype=torch.int32, device=deg.device)
+        _exclusive_scan(deg, N, raw)
+        call("xeq_rowptr_guard", ptr(raw), N, cap, ptr(rowptr), ptr(count), stream())
+        if running_total is not None:
+            running_total.add_(count)
+    return count
+
+
+def _guard_cut(deg, N, cap, rowptr, running_total):
+    """Capacity guard of the periodic form -> count [1].  Every kernel downstream walks by this row pointer: a list that outgrew the
+    capacity must not lead them past the buffers.  The true count is kept aside for the caller's check, the row pointer is cut at the
+    capacity (rows behind it become empty; the fill writes nothing at or past `cap`): the step's results are then wrong but every
+    access stays in bounds."""
+    _exclusive_scan(deg, N, rowptr)
+    count = rowptr[N:].clone()
+    rowptr.clamp_(max=cap)
+    return count
+
+
+def _neighbor_list(rec, pos, n_bins: int = 0, out=None, guard=None, running_total=None):
+    """THE host sequence of every neighbour search: (bin ids -> sort by bin ->) count -> scan -> size -> fill, on a filled record.
+    ``pos``: the positions the record points at (their device, dtype and count size the outputs).
+    ``out`` None: the edge count is read back (one host sync, as in the reference's nonzero()) and the list allocated to size.
+    ``out`` = (edge_index [2, capacity], cell_offsets [capacity, 3] or None): nothing is read back, ``guard`` (_guard_empty /
+    _guard_cut) scans the degrees and applies the capacity.  -> (edge_index, cell_offsets or None, rowptr [N + 1], count [1] or None)."""
+    N, dev = pos.shape[0], pos.device
+    bins = rec.kind in (lib.NEIGHBORS_OPEN_BINS, lib.NEIGHBORS_PBC_BINS)
+    if bins:
+        keys_ = torch.empty(N, dtype=torch.int64, device=dev)
+        call("xeq_neighbors_bin_ids", rec, ptr(keys_), stream())
+        bin_start, bin_atom = csr_by_key(keys_, n_bins)
+        lib.fill(rec, bin_start=bin_start, bin_atom=bin_atom)
     deg = torch.empty(N, dtype=torch.int32, device=dev)
     rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-    call("xeq_radius_graph_count_cl", dt, ptr(pos), ptr(ptr_), G, N, float(cutoff), ptr(lo), ptr(inv_w), ptr(nb), ptr(bin_base),
-         ptr(bin_start), ptr(bin_atom), ptr(deg), stream())
-    _exclusive_scan(deg, N, rowptr)
-    E = int(rowptr[-1].item()) if N > 0 else 0
-    edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
-    tmp_keys = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
-    call("xeq_radius_graph_fill_cl", dt, ptr(pos), ptr(ptr_), G, N, float(cutoff), ptr(lo), ptr(inv_w), ptr(nb), ptr(bin_base),
-         ptr(bin_start), ptr(bin_atom), ptr(rowptr), E, ptr(tmp_keys), ptr(edge_index), stream())
+    call("xeq_neighbors_count", rec, ptr(deg), stream())
+    if out is None:
+        _exclusive_scan(deg, N, rowptr)
+        E, count = int(rowptr[-1].item()) if N > 0 else 0, None
+        edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
+        cell_offsets = torch.empty((E, 3), dtype=pos.dtype, device=dev) if rec.kind >= lib.NEIGHBORS_PBC_ALL else None
+    else:
+        edge_index, cell_offsets = out
+        E = int(edge_index.shape[1])
+        count = guard(deg, N, E, rowptr, running_total)
+    tmp_keys = torch.empty(max(E, 1), dtype=torch.int64, device=dev) if bins else None
+    call("xeq_neighbors_fill", rec, ptr(rowptr), E, ptr(tmp_keys), ptr(edge_index), ptr(cell_offsets), stream())
+    return edge_index, cell_offsets, rowptr, count
+
+
+def _radius_graph_cell_list(pos, ptr_, cutoff):
+    """Open-boundary neighbour list through a per-graph bin grid (XEQ_NEIGHBORS_OPEN_BINS): O(N) instead of O(n_g^2)."""
+    lo, nb, inv_w = _box_grid(pos, ptr_, cutoff)
+    bin_base, n_bins = _bin_base(nb)
+    rec = _search_record(lib.NEIGHBORS_OPEN_BINS, pos, ptr_, cutoff, lo=lo, inv_w=inv_w, nbins=nb, bin_base=bin_base)
+    edge_index, _, rowptr, _ = _neighbor_list(rec, pos, n_bins)
     return edge_index, rowptr
 
 
@@ -316,15 +369,7 @@ def radius_graph_raw(pos: torch.Tensor, ptr_: torch.Tensor, cutoff: float) -> Tu
     N, G = pos.shape[0], ptr_.numel() - 1
     if N > 0 and G > 0 and _use_cell_list(N, G):
         return _radius_graph_cell_list(pos, ptr_, cutoff)
-    dev = pos.device
-    deg = torch.empty(N, dtype=torch.int32, device=dev)
-    rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-    dt = dtype_code(pos)
-    call("xeq_radius_graph_count", dt, ptr(pos), ptr(ptr_), G, N, float(cutoff), ptr(deg), stream())
-    _exclusive_scan(deg, N, rowptr)
-    E = int(rowptr[-1].item()) if N > 0 else 0  # one host sync, as in the reference's nonzero()
-    edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
-    call("xeq_radius_graph_fill", dt, ptr(pos), ptr(ptr_), G, N, float(cutoff), ptr(rowptr), E, ptr(edge_index), stream())
+    edge_index, _, rowptr, _ = _neighbor_list(_search_record(lib.NEIGHBORS_OPEN_SWEEP, pos, ptr_, cutoff), pos)
     return edge_index, rowptr
 
 
@@ -341,89 +386,39 @@ def radius_graph_capacity(pos: torch.Tensor, ptr_: torch.Tensor, cutoff: float, 
     pos = pos.detach().contiguous()
     ptr_ = ptr_.to(torch.int64).contiguous()
     assert edge_index.dim() == 2 and edge_index.shape[0] == 2 and edge_index.dtype == torch.int64 and edge_index.is_contiguous()
-    N, G, cap = pos.shape[0], ptr_.numel() - 1, int(edge_index.shape[1])
-    dev = pos.device
-    deg = torch.empty(N, dtype=torch.int32, device=dev)
-    rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-    dt = dtype_code(pos)
-    call("xeq_radius_graph_count", dt, ptr(pos), ptr(ptr_), G, N, float(cutoff), ptr(deg), stream())
-    count = torch.empty(1, dtype=torch.int32, device=dev)
-    if N <= _scan_one_launch_max():     # scan, total and capacity guard by one workgroup in one launch (three before)
-        call("xeq_rowptr_from_degrees", ptr(deg), N, cap, ptr(rowptr), ptr(count), ptr(running_total), stream())
-    else:
-        raw = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        _exclusive_scan(deg, N, raw)
-        call("xeq_rowptr_guard", ptr(raw), N, cap, ptr(rowptr), ptr(count), stream())
-        if running_total is not None:
-            running_total.add_(count)
-    call("xeq_radius_graph_fill", dt, ptr(pos), ptr(ptr_), G, N, float(cutoff), ptr(rowptr), cap, ptr(edge_index), stream())
+    rec = _search_record(lib.NEIGHBORS_OPEN_SWEEP, pos, ptr_, cutoff)
+    _, _, rowptr, count = _neighbor_list(rec, pos, out=(edge_index, None), guard=_guard_empty, running_total=running_total)
     return rowptr, count
 
 
-def radius_graph_pbc_raw(pos_wrap, ptr_, img, cells, shift, cutoff, prune=None):
-    """PBC neighbour search over precomputed images (see xeq_radius_graph_pbc_* in xeq.h).
-    prune = (recip[G,3,3], thr[G,3], reps) selects the image-pruned kernels (same edges, same order)."""
-    require_hip(pos_wrap, ptr_, img, cells, shift)
+def _pbc_search(pos_wrap, ptr_, img, cells, shift, cutoff, prune):
+    """The record of a periodic search and what it points at: -> (record, wrapped positions as the record has them, the other tensors to
+    keep alive, bin count).  ``prune`` None: all
+    images; (recip, thr, reps): image pruning; (recip, thr, reps, nbins): the bin grid in fractional coordinates."""
     pos_wrap, img, cells, shift = (t.contiguous() for t in (pos_wrap, img, cells, shift))
-    if prune is not None and len(prune) == 4:
-        # cell list (graphs of many atoms): bins in fractional coordinates, see xeq_radius_graph_pbc_*_cl
-        recip, thr, reps, nbins = prune
-        recip, thr = recip.to(pos_wrap.dtype).contiguous(), thr.to(pos_wrap.dtype).contiguous()
-        nbins = nbins.to(torch.int32).contiguous()
-        ptr_ = ptr_.to(torch.int64).contiguous()
-        N, G, n_cells = pos_wrap.shape[0], ptr_.numel() - 1, cells.shape[0]
-        dev, dt = pos_wrap.device, dtype_code(pos_wrap)
-        per_graph = nbins.prod(dim=1)
-        bin_base = torch.zeros(G + 1, dtype=torch.int32, device=dev)
-        bin_base[1:] = torch.cumsum(per_graph, 0)
-        n_bins = int(bin_base[-1].item())
-        keys_ = torch.empty(N, dtype=torch.int64, device=dev)
-        call("xeq_radius_graph_pbc_bin_ids", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(recip), ptr(nbins), ptr(bin_base), ptr(keys_),
-             stream())
-        bin_start, bin_atom = csr_by_key(keys_, n_bins)
-        deg = torch.empty(N, dtype=torch.int32, device=dev)
-        rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        call("xeq_radius_graph_pbc_count_cl", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), n_cells, float(cutoff), ptr(recip),
-             ptr(thr), mul3(reps), ptr(nbins), ptr(bin_base), ptr(bin_start), ptr(bin_atom), ptr(deg), stream())
-        _exclusive_scan(deg, N, rowptr)
-        E = int(rowptr[-1].item()) if N > 0 else 0
-        edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
-        cell_offsets = torch.empty((E, 3), dtype=pos_wrap.dtype, device=dev)
-        tmp_keys = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
-        call("xeq_radius_graph_pbc_fill_cl", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), ptr(cells), ptr(shift), n_cells,
-             float(cutoff), ptr(recip), ptr(thr), mul3(reps), ptr(nbins), ptr(bin_base), ptr(bin_start), ptr(bin_atom), ptr(rowptr),
-             E, ptr(tmp_keys), ptr(edge_index), ptr(cell_offsets), stream())
-        return edge_index, cell_offsets, rowptr
-    if prune is not None:
-        recip, thr, reps = prune
-        recip, thr = recip.to(pos_wrap.dtype).contiguous(), thr.to(pos_wrap.dtype).contiguous()
-        ptr_ = ptr_.to(torch.int64).contiguous()
-        N, G, n_cells = pos_wrap.shape[0], ptr_.numel() - 1, cells.shape[0]
-        dev, dt = pos_wrap.device, dtype_code(pos_wrap)
-        deg = torch.empty(N, dtype=torch.int32, device=dev)
-        rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        call("xeq_radius_graph_pbc_count_pruned", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), n_cells, float(cutoff), ptr(recip),
-             ptr(thr), mul3(reps), ptr(deg), stream())
-        _exclusive_scan(deg, N, rowptr)
-        E = int(rowptr[-1].item()) if N > 0 else 0
-        edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
-        cell_offsets = torch.empty((E, 3), dtype=pos_wrap.dtype, device=dev)
-        call("xeq_radius_graph_pbc_fill_pruned", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), ptr(cells), ptr(shift), n_cells,
-             float(cutoff), ptr(recip), ptr(thr), mul3(reps), ptr(rowptr), E, ptr(edge_index), ptr(cell_offsets), stream())
-        return edge_index, cell_offsets, rowptr
     ptr_ = ptr_.to(torch.int64).contiguous()
-    N, G, n_cells = pos_wrap.shape[0], ptr_.numel() - 1, cells.shape[0]
-    dev = pos_wrap.device
-    dt = dtype_code(pos_wrap)
-    deg = torch.empty(N, dtype=torch.int32, device=dev)
-    rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-    call("xeq_radius_graph_pbc_count", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), n_cells, float(cutoff), ptr(deg), stream())
-    _exclusive_scan(deg, N, rowptr)
-    E = int(rowptr[-1].item()) if N > 0 else 0
-    edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
-    cell_offsets = torch.empty((E, 3), dtype=pos_wrap.dtype, device=dev)
-    call("xeq_radius_graph_pbc_fill", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), ptr(cells), ptr(shift), n_cells,
-         float(cutoff), ptr(rowptr), E, ptr(edge_index), ptr(cell_offsets), stream())
+    kind = lib.NEIGHBORS_PBC_ALL if prune is None else lib.NEIGHBORS_PBC_BINS if len(prune) == 4 else lib.NEIGHBORS_PBC_PRUNED
+    rec = _search_record(kind, pos_wrap, ptr_, cutoff, n_cells=cells.shape[0], img=img, cells=cells, shift=shift)
+    keep, n_bins = [ptr_, img, cells, shift], 0
+    if prune is not None:
+        recip, thr = prune[0].to(pos_wrap.dtype).contiguous(), prune[1].to(pos_wrap.dtype).contiguous()
+        lib.fill(rec, recip=recip, thr=thr, reps=tuple(int(r) for r in prune[2]))
+        keep += [recip, thr]
+    if kind == lib.NEIGHBORS_PBC_BINS:
+        nbins = prune[3].to(torch.int32).contiguous()
+        bin_base, n_bins = _bin_base(nbins)
+        lib.fill(rec, nbins=nbins, bin_base=bin_base)
+        keep += [nbins, bin_base]
+    return rec, pos_wrap, keep, n_bins
+
+
+def radius_graph_pbc_raw(pos_wrap, ptr_, img, cells, shift, cutoff, prune=None):
+    """PBC neighbour search over precomputed images (see the XEQ_NEIGHBORS_PBC_* kinds in xeq.h).
+    prune = (recip[G,3,3], thr[G,3], reps) selects the image-pruned kernels (same edges, same order); a fourth member, nbins[G,3],
+    the cell list (graphs of many atoms): bins in fractional coordinates."""
+    require_hip(pos_wrap, ptr_, img, cells, shift)
+    rec, pos_wrap, _keep, n_bins = _pbc_search(pos_wrap, ptr_, img, cells, shift, cutoff, prune)
+    edge_index, cell_offsets, rowptr, _ = _neighbor_list(rec, pos_wrap, n_bins)
     return edge_index, cell_offsets, rowptr
 
 
@@ -434,25 +429,10 @@ def radius_graph_pbc_capacity(pos_wrap, ptr_, img, cells, shift, cutoff, prune, 
     order as the sized form.  The pair sweep only (the bin grid's size is a host value)."""
     require_hip(pos_wrap, ptr_, img, cells, shift, edge_index, cell_offsets)
     recip, thr, reps = prune
-    pos_wrap, img, cells, shift = (t.contiguous() for t in (pos_wrap, img, cells, shift))
-    recip, thr = recip.to(pos_wrap.dtype).contiguous(), thr.to(pos_wrap.dtype).contiguous()
-    ptr_ = ptr_.to(torch.int64).contiguous()
     assert edge_index.dim() == 2 and edge_index.shape[0] == 2 and edge_index.dtype == torch.int64 and edge_index.is_contiguous()
-    N, G, n_cells, cap = pos_wrap.shape[0], ptr_.numel() - 1, cells.shape[0], int(edge_index.shape[1])
-    assert cell_offsets.shape == (cap, 3) and cell_offsets.dtype == pos_wrap.dtype and cell_offsets.is_contiguous()
-    dev, dt = pos_wrap.device, dtype_code(pos_wrap)
-    deg = torch.empty(N, dtype=torch.int32, device=dev)
-    rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-    call("xeq_radius_graph_pbc_count_pruned", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), n_cells, float(cutoff), ptr(recip),
-         ptr(thr), mul3(reps), ptr(deg), stream())
-    _exclusive_scan(deg, N, rowptr)
-    # every kernel downstream walks by this row pointer: a list that outgrew the capacity must not lead them past the buffers.  The
-    # true count is kept aside for the caller's check, the row pointer is cut at the capacity (rows behind it become empty; the fill
-    # writes nothing at or past `cap`): the step's results are then wrong but every access stays in bounds
-    count = rowptr[N:].clone()
-    rowptr.clamp_(max=cap)
-    call("xeq_radius_graph_pbc_fill_pruned", dt, ptr(pos_wrap), ptr(ptr_), G, N, ptr(img), ptr(cells), ptr(shift), n_cells,
-         float(cutoff), ptr(recip), ptr(thr), mul3(reps), ptr(rowptr), cap, ptr(edge_index), ptr(cell_offsets), stream())
+    assert cell_offsets.shape == (edge_index.shape[1], 3) and cell_offsets.dtype == pos_wrap.dtype and cell_offsets.is_contiguous()
+    rec, pos_wrap, _keep, _ = _pbc_search(pos_wrap, ptr_, img, cells, shift, cutoff, (recip, thr, reps))
+    _, _, rowptr, count = _neighbor_list(rec, pos_wrap, out=(edge_index, cell_offsets), guard=_guard_cut)
     return rowptr, count
 
 
