@@ -978,11 +978,12 @@ int xeq_ewald_layernorm_bwd(const void* g, const void* x, const void* stats, con
 int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const void* pre, int64_t count, void* out, void* stream);
 
 /* Device-resident drivers around a whole-step graph (xequinet_amd/resident.py, csrc/xeq_md.hip): molecular dynamics (md.py, DESIGN.md
- * sections 12 and 15) and batched FIRE geometry optimisation (optimize.py, section 13), f32 / f64.  One step is a FRONT entry, the step's
+ * sections 12 and 15) and batched FIRE and L-BFGS geometry optimisation (optimize.py, sections 13 and 16), f32 / f64.  One step is a FRONT entry, the step's
  * graph on the step object's static buffers, a BACK entry; nothing reaches the host between them.
  *
- * The six entries take their arguments as RECORDS, by pointer: what every driver has (the system, the step graph's outputs, the chunk
- * tables, the recorder) and one record of parameters per driver.  Every member is 8 bytes wide -- a pointer, int64_t, uint64_t or double
+ * The entries take their arguments as RECORDS, by pointer: what every driver has (the system, the step graph's outputs, the chunk
+ * tables, the recorder) and, for the six MD / NPT / FIRE entries, one record of parameters per driver; the two L-BFGS entries take the
+ * shared records and their own state as plain arguments.  Every member is 8 bytes wide -- a pointer, int64_t, uint64_t or double
  * -- so a record's layout is its field order, without padding, on any ABI; xeq_record_bytes(which) gives the library's sizeof for a
  * binding to compare with its own (-1: no such record).  A record is read during the call and not retained.  Pointers are device
  * pointers unless marked HOST; `dtype` below: a buffer of the system record's floating type. */
@@ -1024,8 +1025,8 @@ typedef struct xeq_res_chunks {
   const int32_t* chunk_atom0;
   const int32_t* chunk_n;
   const int32_t* graph_chunk_ptr;
-  double* partial;      /* [n_chunks] (FIRE: [n_chunks, 4]): the chunks' sums */
-  int32_t* partial_bad; /* [n_chunks]: the chunks' non-finite-force flags */
+  double* partial;      /* [n_chunks] (FIRE: [n_chunks, 4]; L-BFGS: [n_chunks, 3 (2 memory + 3) + 1]): the chunks' sums */
+  int32_t* partial_bad; /* [n_chunks] (L-BFGS: [n_chunks, 4]): the chunks' non-finite-force flags */
 } xeq_res_chunks;
 
 /* The trajectory a back entry writes.  A NULL record, every = 0 or rows = 0: nothing is recorded.  When d = book[0] - start behind the
@@ -1168,6 +1169,61 @@ typedef struct xeq_fire_params {
 int xeq_fire_front(const xeq_res_system* sys, const xeq_fire_params* fire, void* stream);
 int xeq_fire_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_fire_params* fire,
                   const xeq_res_recorder* rec, void* stream);
+
+/* Batched limited-memory BFGS without line search (xequinet_amd/optimize.py: LBFGS, csrc/xeq_lbfgs.hip), by the rule
+ * of ASE's optimize.LBFGS with use_line_search=False.  Every graph is its own minimiser: its own history, step clamp and convergence
+ * flag.  The entries take the system, step, chunk and recorder records above and the driver's own state as plain arguments (no record of
+ * their own).  Free atoms only: a fixed atom has force 0 and displacement 0 and enters no sum.  All per-graph and per-atom arithmetic
+ * runs in double whatever `dtype` is and is rounded once where a `dtype` value is stored.  m = memory, K = 2 m + 1.
+ *
+ * State per graph: a ring of at most m pairs (s_j, y_j) in hist_s / hist_y, f64 [m, n, 3], slot j of a graph in its atoms' rows of
+ * plane j; count and head of the ring (a pair goes to slot `head`, then head = (head + 1) mod m and count = min(count + 1, m), so the
+ * filled slots are 0 .. count - 1 and the oldest pair is slot 0 until the ring is full, slot `head` from then on); status; converged_at;
+ * epot; fmax; dropped; the symmetric Gram matrix gram [n_graphs, K, K] of the basis b = (s_0 .. s_{m-1}, y_0 .. y_{m-1}, g) by ring
+ * slot (s_j at index j, y_j at m + j, g = -f at 2 m; entries of empty slots are not defined); delta [n_graphs, K], the direction's
+ * coefficients (0 at empty slots).  sys->frc is f_prev between two backs; sys->vel is not used (NULL is taken).
+ *
+ * xeq_lbfgs_back, behind evaluation number book[0], for a graph that is not converged:
+ *   1. f = frc_step, 0 for a fixed atom; epot = energy_step; fmax = sqrt(max_i |f_i|^2).
+ *   2. fmax < fmax_tol: frc = f, status = converged, converged_at = book[0]; nothing of this graph is written ever after.
+ *   3. otherwise, when the graph is ACTIVE, the candidate pair is s = pending_s (left by the front) and y = f_prev - f.
+ *   4. The pair is stored at slot `head` only when s.y is finite and s.y > 0; a rejected pair leaves the history as it was and adds 1
+ *      to dropped.
+ *   5. frc = f (f_prev of the next back).
+ *   6. The rows and columns of B that changed: the new pair's against everything stored and g's against everything.
+ *   7. The two-loop recursion in coefficient space: delta = e_g; for the stored pairs from newest to oldest
+ *      a_i = (B[s_i, :] . delta) / B[s_i, y_i], delta[y_i] -= a_i; delta *= 1 / alpha; for the pairs from oldest to newest
+ *      beta = (B[y_i, :] . delta) / B[s_i, y_i], delta[s_i] += a_i - beta.  A fresh graph has delta = e_g (1 / alpha) and becomes ACTIVE.
+ *   Orders.  First launch, one workgroup per chunk (chunk tables as for xeq_md_back): per atom the products (a0 b0 + a1 b1) + a2 b2 of
+ *   the candidates s, y, g with every stored s_j, y_j and with one another, and |f_i|^2 for the max; lanes, butterfly, the four waves in
+ *   order; into partial [n_chunks, 3 (2 m + 3) + 1] (candidate-major; columns: the s slots, the y slots, the candidates s, y, g; last
+ *   the max).  partial_bad is int32 [n_chunks, 4] here: the chunk's non-finite-force flag and what the graph's status, head and count
+ *   were in front of this back.  Second launch, one workgroup per chunk: a graph's partials are added chunk after chunk, sequentially,
+ *   by every workgroup of the graph alike; each stores its atoms' rows of the ring and of frc; the workgroup of the graph's first chunk
+ *   refreshes B and runs the recursion in one wave: lane l holds delta_l and delta_{64 + l}, a row product B[r, :] . delta is
+ *   B[r, l] delta_l + B[r, 64 + l] delta_{64 + l} per lane (empty slots contribute 0) and a butterfly (xor 32, 16, .. 1).
+ *   Every back, one lane (of the workgroup that ends last; it is elected by an integer ticket, which is 0 between launches and the only
+ *   atomic -- no sum goes through it): a graph without atoms converges at its first evaluation; book[0] += 1, book[1] = max(book[1],
+ *   n_edges_step[0]), book[2] = 1 on a non-finite force or energy of a graph that is not converged, book[3] = graphs not converged.
+ *   No float atomics; a graph has the same bits alone and anywhere in a batch.
+ * xeq_lbfgs_front, per free atom of an ACTIVE graph: p_i = -sum_k delta_k b_{k,i} in slot order (acc = 0; acc += delta_k b_k over the
+ *   filled s slots, the filled y slots, then g = -(double)frc; p = -acc); longest = sqrt(max_i |p_i|^2) (chunk maxima: lanes,
+ *   butterfly, waves; then over the graph's chunks); scale = maxstep / longest when longest >= maxstep, else 1;
+ *   x_new = dtype(x + (damping scale) p_i); pending_s = (double)x_new - (double)x, exact, taken before the wrap; then the wrap of
+ *   xeq_md_front.  Atoms of fresh or converged graphs and fixed atoms are not written.  First launch: direction (into pending_s) and
+ *   chunk maxima (a chunk's first partial); second launch: the move.
+ * max_graph_chunks: the most chunks any graph has; at most 1: the workgroup that owns a graph does both halves of an entry and each
+ *   entry is ONE launch (a caller that understates it gets sums over a graph's own chunk alone, no access out of bounds).
+ * The recorder's traj_second is fmax.  n = 0: the front does nothing; the back keeps the books. */
+#define XEQ_LBFGS_MAX_MEMORY 32
+enum { XEQ_LBFGS_FRESH = 0, XEQ_LBFGS_ACTIVE = 1, XEQ_LBFGS_CONVERGED = 2 };
+int xeq_lbfgs_front(const xeq_res_system* sys, const xeq_res_chunks* chunks, const uint8_t* fixed, int64_t memory, int64_t max_graph_chunks,
+                    const double* hist_s, const double* hist_y, double* pending_s, const double* delta, const int32_t* count,
+                    const int32_t* status, double maxstep, double damping, void* stream);
+int xeq_lbfgs_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_res_recorder* rec,
+                   const uint8_t* fixed, int64_t memory, int64_t max_graph_chunks, double* hist_s, double* hist_y, const double* pending_s,
+                   double* gram, double* delta, int32_t* count, int32_t* head, int32_t* status, int32_t* dropped, int64_t* converged_at,
+                   void* epot, void* fmax, int32_t* ticket, double fmax_tol, double alpha, void* stream);
 
 /* Batched harmonic analysis behind the Hessian front (xequinet_amd/vibrations.py, csrc/xeq_vib.hip).  Everything is
  * f64; only the Hessian is read as `dtype` and widened on load.  One workgroup per graph, fixed summation orders, no atomics: a graph's

@@ -18,7 +18,7 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(".md", __name__)
-    if name == "optimize":     # device-resident batched FIRE minimiser (optimize.py), likewise
+    if name == "optimize":     # device-resident batched FIRE and L-BFGS minimisers (optimize.py), likewise
         import importlib
 
         return importlib.import_module(".optimize", __name__)

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libxeq_hip.so")
-SOURCES = ["xeq_graph.hip", "xeq_ops.hip", "xeq_message.hip", "xeq_message_sb.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.hip", "xeq_node.hip", "xeq_mlp.hip", "xeq_linear.hip", "xeq_update.hip", "xeq_nodeblock.hip", "xeq_tp.hip", "xeq_train.hip", "xeq_train_node.hip", "xeq_train_edge.hip", "xeq_electronic.hip", "xeq_painn.hip", "xeq_heads.hip", "xeq_ewald.hip", "xeq_md.hip", "xeq_vib.hip"]
+SOURCES = ["xeq_graph.hip", "xeq_ops.hip", "xeq_message.hip", "xeq_message_sb.hip", "xeq_message_wq.hip", "xeq_message_wq_bwd.hip", "xeq_node.hip", "xeq_mlp.hip", "xeq_linear.hip", "xeq_update.hip", "xeq_nodeblock.hip", "xeq_tp.hip", "xeq_train.hip", "xeq_train_node.hip", "xeq_train_edge.hip", "xeq_electronic.hip", "xeq_painn.hip", "xeq_heads.hip", "xeq_ewald.hip", "xeq_md.hip", "xeq_vib.hip", "xeq_lbfgs.hip"]
 HEADERS = ["xeq_common.h", "xeq_packed_w.h", "xeq_linear_s.h", "xeq_message_wq.h", "xeq_pbc_tables.h", os.path.join("..", "..", "include", "xeq.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # per-source extras.  The matrix-core message kernels: LLVM's max-ILP machine scheduler instead of the default (measured in round 1 on
@@ -33,7 +33,9 @@ EXTRA_FLAGS = {"xeq_nodeblock.hip": [],
                "xeq_message_wq_bwd.hip": ["-ffp-contract=off"],
                # md: the integrator's double expressions are the ones written, operation by operation (tests/md_oracle.py restates them);
                # an explicit -ffp-contract=fast on the command line overrides a pragma in the source, so the switch is here
-               "xeq_md.hip": ["-ffp-contract=off"]}
+               "xeq_md.hip": ["-ffp-contract=off"],
+               # lbfgs: as md (tests/lbfgs_oracle.py restates its double expressions)
+               "xeq_lbfgs.hip": ["-ffp-contract=off"]}
 for _src in MFMA_SOURCES:
     EXTRA_FLAGS[_src] = EXTRA_FLAGS.get(_src, []) + NO_PACKED
 LLVM_BIN = os.environ.get("XEQ_LLVM_BIN", "/opt/rocm/lib/llvm/bin")

@@ -22,6 +22,7 @@ MD_CHUNK = 256          # XEQ_MD_CHUNK of include/xeq.h: atoms per kinetic-energ
 MD_NVE, MD_LANGEVIN, MD_BERENDSEN, MD_PURPOSE_LANGEVIN, MD_PURPOSE_MAXWELL = 0, 1, 2, 0, 1      # XEQ_MD_* of include/xeq.h (md.py)
 NPT_BOX, NPT_CELL, NPT_INV, NPT_CELL_NEXT, NPT_INV_NEXT, NPT_MU, NPT_P, NPT_V = 40, 0, 9, 18, 27, 36, 37, 38      # XEQ_NPT_* of include/xeq.h (md.py)
 FIRE_FRESH, FIRE_ACTIVE, FIRE_CONVERGED = 0, 1, 2      # XEQ_FIRE_* of include/xeq.h
+LBFGS_FRESH, LBFGS_ACTIVE, LBFGS_CONVERGED, LBFGS_MAX_MEMORY = 0, 1, 2, 32      # XEQ_LBFGS_* of include/xeq.h (optimize.LBFGS)
 VIB_MAX_DIM, VIB_MAX_SWEEPS = 96, 30     # XEQ_VIB_MAX_DIM, XEQ_VIB_MAX_SWEEPS of include/xeq.h (vibrations.py)
 VIB_LARGE_MAX_DIM = 768              # XEQ_VIB_LARGE_MAX_DIM: the cap of xeq_vib_eigh_large
 VIB_ROTORS = ("atom", "linear", "nonlinear")      # XEQ_VIB_ATOM, _LINEAR, _NONLINEAR
@@ -272,6 +273,9 @@ _PROTOS = {
     "xeq_npt_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(MdParams), _R(NptParams), _R(ResRecorder), c_int, _P],
     "xeq_fire_front": [_R(ResSystem), _R(FireParams), _P],
     "xeq_fire_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(FireParams), _R(ResRecorder), _P],
+    "xeq_lbfgs_front": [_R(ResSystem), _R(ResChunks), _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_double, c_double, _P],
+    "xeq_lbfgs_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(ResRecorder), _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                       _P, _P, c_double, c_double, _P],
     "xeq_vib_project": [c_int, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "xeq_vib_eigh": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],
     "xeq_vib_eigh_large": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],

@@ -1,4 +1,5 @@
-"""Geometry optimisation that stays on the GPU: a batched FIRE minimiser next to the whole-step graphs of runtime.py.
+"""Geometry optimisation that stays on the GPU: a batched FIRE minimiser and a batched L-BFGS minimiser (``LBFGS``)
+next to the whole-step graphs of runtime.py.
 
 ``FIRE`` lives next to a ``runtime.GraphedStep`` (a batch of open-boundary molecules, ``ptr``) or a ``runtime.GraphedStepPBC`` (one periodic
 box with a fixed cell, ``cell``) exactly as ``md.Dynamics`` does, and one iteration is
@@ -18,6 +19,7 @@ import ctypes
 import math
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import keys, lib
@@ -35,9 +37,79 @@ def time_step_factor(energy_unit: str, length_unit: str) -> float:
     return math.sqrt((e_ev / l_a) * (1.0 / l_a))
 
 
-class FIRE(ResidentDriver):
+class _Minimiser(ResidentDriver):
+    """What the two minimisers share beyond ResidentDriver: the run loop over windows, the lazy evaluation 0 and the read-only surface.
+    A subclass sets ``_CONVERGED`` (its status value of a converged graph), ``status``, ``_converged_at``, ``frc``, ``epot``, ``fmax``,
+    ``_active_host`` and defines ``reset()``."""
+
+    _CONVERGED = None
+
+    def _bad_message(self, first: int, n: int) -> str:
+        return (f"{type(self).__name__}: non-finite force or energy in evaluations {first} .. {first + n}; the state is that "
+                + (f"behind evaluation {first - 1}" if first else "of the start"))
+
+    def _window(self, n: int) -> None:
+        super()._window(n)
+        self._active_host = self._book_extra
+
+    # ------------------------------------------------------------------------------------------------ public
+    def run(self, max_steps: int, check_every: int = 20, record_every: int = 0) -> bool:
+        """At most ``max_steps`` iterations in windows of ``check_every``; True when every graph has converged.  With ``record_every`` the
+        state behind every ``record_every``-th evaluation of this run goes to ``trajectory`` (pos, epot, fmax, step; rows the run did not
+        reach stay zero)."""
+        max_steps, check_every, record_every = int(max_steps), max(1, int(check_every)), max(0, int(record_every))
+        if max_steps < 0:
+            raise ValueError(f"{type(self).__name__}.run: max_steps < 0")
+        self._record_run(max_steps, record_every, "fmax", self.step_count)
+        if not self._fresh:
+            self._window(0)            # evaluation 0: a start that is already relaxed moves nothing
+        done = 0
+        while done < max_steps and self._active_host > 0:
+            w = min(check_every, max_steps - done)
+            self._window(w)
+            done += w
+        return self._active_host == 0
+
+    def _settle(self) -> None:
+        if not self._fresh:
+            self._window(0)
+
+    @property
+    def step_count(self) -> int:
+        """Iterations done: the number of the latest evaluation (the first one is 0)."""
+        return max(self._steps_host - 1, 0)
+
+    @property
+    def forces(self) -> torch.Tensor:
+        self._settle()
+        return self.frc.clone()
+
+    @property
+    def potential_energy(self) -> torch.Tensor:
+        self._settle()
+        return self.epot.clone()
+
+    @property
+    def max_force(self) -> torch.Tensor:
+        self._settle()
+        return self.fmax.clone()
+
+    @property
+    def converged(self) -> torch.Tensor:
+        self._settle()
+        return self.status == self._CONVERGED
+
+    @property
+    def converged_at(self) -> torch.Tensor:
+        self._settle()
+        return self._converged_at.clone()
+
+
+class FIRE(_Minimiser):
     """``FIRE(model, pos, atomic_numbers, ptr=... | cell=..., fmax=...)``: see the module text and DESIGN.md section 13.  ``fixed``: bool [N],
     atoms that never move.  ``fmax`` in the model's force unit, ``maxstep`` in its length unit, ``dt`` / ``dtmax`` as ASE gives them."""
+
+    _CONVERGED = lib.FIRE_CONVERGED
 
     def __init__(self, model, pos: torch.Tensor, atomic_numbers: torch.Tensor, *, ptr: Optional[torch.Tensor] = None, cell: Optional[torch.Tensor] = None,
                  pbc=None, fixed: Optional[torch.Tensor] = None, fmax: float, dt: float = 0.1, maxstep: float = 0.2, dtmax: float = 1.0, n_min: int = 5,
@@ -109,32 +181,6 @@ class FIRE(ResidentDriver):
         return [self._pos, self.image, self.vel, self.frc, self.epot, self.fmax, self.dt, self.alpha, self.n_pos, self.status, self._converged_at,
                 self.coef, self.book]
 
-    def _bad_message(self, first: int, n: int) -> str:
-        return (f"FIRE: non-finite force or energy in evaluations {first} .. {first + n}; the state is that "
-                + (f"behind evaluation {first - 1}" if first else "of the start"))
-
-    def _window(self, n: int) -> None:
-        super()._window(n)
-        self._active_host = self._book_extra
-
-    # ------------------------------------------------------------------------------------------------ public
-    def run(self, max_steps: int, check_every: int = 20, record_every: int = 0) -> bool:
-        """At most ``max_steps`` iterations in windows of ``check_every``; True when every graph has converged.  With ``record_every`` the
-        state behind every ``record_every``-th evaluation of this run goes to ``trajectory`` (pos, epot, fmax, step; rows the run did not
-        reach stay zero)."""
-        max_steps, check_every, record_every = int(max_steps), max(1, int(check_every)), max(0, int(record_every))
-        if max_steps < 0:
-            raise ValueError("FIRE.run: max_steps < 0")
-        self._record_run(max_steps, record_every, "fmax", self.step_count)
-        if not self._fresh:
-            self._window(0)            # evaluation 0: a start that is already relaxed moves nothing
-        done = 0
-        while done < max_steps and self._active_host > 0:
-            w = min(check_every, max_steps - done)
-            self._window(w)
-            done += w
-        return self._active_host == 0
-
     def reset(self) -> None:
         """Every graph fresh and active again, v = 0, from the current positions; the evaluation count starts over."""
         self.vel.zero_()
@@ -147,50 +193,136 @@ class FIRE(ResidentDriver):
         self.book.zero_()
         self._steps_host, self._active_host, self._fresh = 0, self.n_graphs, False
 
-    def _settle(self) -> None:
-        if not self._fresh:
-            self._window(0)
-
-    @property
-    def step_count(self) -> int:
-        """Iterations done: the number of the latest evaluation (the first one is 0)."""
-        return max(self._steps_host - 1, 0)
-
-    @property
-    def forces(self) -> torch.Tensor:
-        self._settle()
-        return self.frc.clone()
-
-    @property
-    def potential_energy(self) -> torch.Tensor:
-        self._settle()
-        return self.epot.clone()
-
-    @property
-    def max_force(self) -> torch.Tensor:
-        self._settle()
-        return self.fmax.clone()
-
-    @property
-    def converged(self) -> torch.Tensor:
-        self._settle()
-        return self.status == lib.FIRE_CONVERGED
-
-    @property
-    def converged_at(self) -> torch.Tensor:
-        self._settle()
-        return self._converged_at.clone()
-
     @property
     def time_steps(self) -> torch.Tensor:
         return self.dt.clone()
 
 
-def minimize(model, data: Dict[str, torch.Tensor], fmax: float, max_steps: int = 500, check_every: int = 20, **kw) -> Dict[str, torch.Tensor]:
-    """``FIRE`` on a data dict (``pos``, ``atomic_numbers``, ``ptr`` or ``cell`` [, ``pbc``]): -> ``pos``, ``energy`` [G], ``forces``,
-    ``converged`` [G] and ``n_steps`` (iterations done)."""
+def curvature_factor(energy_unit: str, length_unit: str) -> float:
+    """(energy unit / length unit^2) per (eV / Angstrom^2): ``alpha`` of ``LBFGS`` is given in eV / Angstrom^2 as ASE gives it and is
+    multiplied by this once, so the kernels see no unit."""
+    e_ev = _units.eval_unit(energy_unit) / _units.eval_unit("eV")               # one energy unit in eV
+    l_a = _units.eval_unit(length_unit) / _units.eval_unit("Angstrom")          # one length unit in Angstrom
+    return (l_a * l_a) / e_ev
+
+
+class LBFGS(_Minimiser):
+    """``LBFGS(model, pos, atomic_numbers, ptr=... | cell=..., fmax=...)``: limited-memory BFGS without line search, ASE's
+    ``optimize.LBFGS`` rule, EVERY GRAPH ITS OWN MINIMISER (its own history, step clamp and convergence flag; a converged graph is frozen
+    bit for bit).  One iteration is xeq_lbfgs_front (direction from the coefficients, clamp, move, wrap), the step's graph, xeq_lbfgs_back
+    (the new pair, three rows of the per-graph Gram matrix, the two-loop recursion in coefficient space): include/xeq.h has the arithmetic,
+    DESIGN.md section 16 the reasons.  ``fmax`` in the model's force unit, ``maxstep`` in its length unit, ``alpha`` in eV / Angstrom^2
+    as ASE gives it, ``memory`` pairs (1 .. 32).  ``fixed``: bool [N], atoms that never move.  There is no CPU fallback."""
+
+    _CONVERGED = lib.LBFGS_CONVERGED
+
+    def __init__(self, model, pos: torch.Tensor, atomic_numbers: torch.Tensor, *, ptr: Optional[torch.Tensor] = None, cell: Optional[torch.Tensor] = None,
+                 pbc=None, fixed: Optional[torch.Tensor] = None, fmax: float, memory: int = 16, alpha: float = 70.0, maxstep: float = 0.2,
+                 damping: float = 1.0, edge_capacity: Optional[int] = None, energy_unit: Optional[str] = None,
+                 length_unit: Optional[str] = None) -> None:
+        for name, v in (("fmax", fmax), ("alpha", alpha), ("maxstep", maxstep), ("damping", damping)):
+            if not (math.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError(f"LBFGS: {name} {v} (> 0 is needed)")
+        if int(memory) != memory or not 1 <= int(memory) <= lib.LBFGS_MAX_MEMORY:
+            raise ValueError(f"LBFGS: memory {memory} (1 .. {lib.LBFGS_MAX_MEMORY})")
+        N = int(pos.shape[0])
+        if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,):
+            raise ValueError("LBFGS: pos [N, 3] and atomic_numbers [N] are needed")
+        if fixed is not None and fixed.shape != (N,):
+            raise ValueError(f"LBFGS: fixed {tuple(fixed.shape)}, [N] = [{N}] is needed")
+        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, ptr, cell, fixed))
+        dev, dt_ = self.device, self.dtype
+
+        u = _units.get_default_units()
+        self.energy_unit = energy_unit or u.get(keys.TOTAL_ENERGY, "eV")
+        self.length_unit = length_unit or u.get(keys.POSITIONS, "Angstrom")
+        self.fmax_tol, self.maxstep, self.damping, self.memory = float(fmax), float(maxstep), float(damping), int(memory)
+        self.alpha = float(alpha) * curvature_factor(self.energy_unit, self.length_unit)
+
+        G, C, M = self.n_graphs, max(self.n_chunks, 1), self.memory
+        K = 2 * M + 1
+        self._max_graph_chunks = int(np.diff(self._graph_chunk_ptr.cpu().numpy()).max()) if G else 0
+        self.fixed = None if fixed is None else fixed.detach().to(torch.bool).contiguous().clone()
+        f64 = dict(dtype=torch.float64, device=dev)
+        self._partial = torch.zeros((C, 3 * (2 * M + 3) + 1), **f64)
+        self._partial_bad = torch.zeros((C, 4), dtype=torch.int32, device=dev)
+        self.vel = None                # (no velocities: the record's member stays NULL)
+        self.frc = torch.zeros((N, 3), dtype=dt_, device=dev)          # f of the latest evaluation = f_prev of the next back
+        self.image = torch.zeros((N, 3), dtype=torch.int32, device=dev)
+        self.hist_s = torch.zeros((M, N, 3), **f64)
+        self.hist_y = torch.zeros((M, N, 3), **f64)
+        self.pending_s = torch.zeros((N, 3), **f64)
+        self.gram = torch.zeros((G, K, K), **f64)
+        self.delta = torch.zeros((G, K), **f64)
+        self.count = torch.zeros(G, dtype=torch.int32, device=dev)
+        self.head = torch.zeros(G, dtype=torch.int32, device=dev)
+        self.status = torch.full((G,), lib.LBFGS_FRESH, dtype=torch.int32, device=dev)
+        self.dropped = torch.zeros(G, dtype=torch.int32, device=dev)
+        self._converged_at = torch.full((G,), -1, dtype=torch.int64, device=dev)
+        self.epot = torch.zeros(G, dtype=dt_, device=dev)
+        self.fmax = torch.zeros(G, dtype=dt_, device=dev)
+        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # evaluations done, largest n_edges, non-finite flag, graphs not converged
+        self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ck = None
+        self._steps_host = 0           # evaluations done
+        self._active_host = G
+        self._fresh = False            # frc / epot / fmax / delta belong to the current positions
+        self._front_name, self._back_name = "xeq_lbfgs_front", "xeq_lbfgs_back"
+
+        self._load_system(pos, atomic_numbers, cell, pbc)
+        if self._any_pbc:              # the wrap alone (every coefficient and force is zero): the search sweeps images around the box
+            every = torch.full((G,), lib.LBFGS_ACTIVE, dtype=torch.int32, device=dev)
+            call("xeq_lbfgs_front", *self._front_args(status=every), lib.stream())
+
+    # ------------------------------------------------------------------------------------------------ launches
+    def _front_args(self, status=None):
+        p = lib.ptr
+        return (ctypes.byref(self._sys), ctypes.byref(self._chunks), p(self.fixed), self.memory, self._max_graph_chunks, p(self.hist_s),
+                p(self.hist_y), p(self.pending_s), p(self.delta), p(self.count), p(self.status if status is None else status), self.maxstep,
+                self.damping)
+
+    def _back_args(self, advance: bool):
+        p = lib.ptr
+        return (ctypes.byref(self._sys), ctypes.byref(self._step_record()), ctypes.byref(self._chunks), ctypes.byref(self._rec), p(self.fixed),
+                self.memory, self._max_graph_chunks, p(self.hist_s), p(self.hist_y), p(self.pending_s), p(self.gram), p(self.delta),
+                p(self.count), p(self.head), p(self.status), p(self.dropped), p(self._converged_at), p(self.epot), p(self.fmax),
+                p(self._ticket), self.fmax_tol, self.alpha)
+
+    # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
+    def _state(self):
+        return [self._pos, self.image, self.frc, self.hist_s, self.hist_y, self.pending_s, self.gram, self.delta, self.count, self.head,
+                self.status, self.dropped, self._converged_at, self.epot, self.fmax, self.book]
+
+    def reset(self) -> None:
+        """Every graph fresh again with an empty history, from the current positions; the evaluation count starts over."""
+        for t in (self.hist_s, self.hist_y, self.pending_s, self.gram, self.delta, self.count, self.head, self.dropped, self.book):
+            t.zero_()
+        self.status.fill_(lib.LBFGS_FRESH)
+        self._converged_at.fill_(-1)
+        self._steps_host, self._active_host, self._fresh = 0, self.n_graphs, False
+
+    @property
+    def history_length(self) -> torch.Tensor:
+        """Pairs each graph's ring holds, [G]."""
+        return self.count.clone()
+
+    @property
+    def dropped_pairs(self) -> torch.Tensor:
+        """Pairs each graph rejected (s.y <= 0 or not finite), [G]."""
+        return self.dropped.clone()
+
+
+METHODS = {"fire": FIRE, "lbfgs": LBFGS}
+
+
+def minimize(model, data: Dict[str, torch.Tensor], fmax: float, max_steps: int = 500, check_every: int = 20, method: str = "fire",
+             **kw) -> Dict[str, torch.Tensor]:
+    """``FIRE`` (``method="fire"``, the default) or ``LBFGS`` (``"lbfgs"``) on a data dict (``pos``, ``atomic_numbers``, ``ptr`` or
+    ``cell`` [, ``pbc``]): -> ``pos``, ``energy`` [G], ``forces``, ``converged`` [G] and ``n_steps`` (iterations done)."""
+    if method not in METHODS:
+        raise ValueError(f"minimize: method {method!r} (one of {sorted(METHODS)})")
     cell = data.get(keys.CELL)
-    opt = FIRE(model, data[keys.POSITIONS], data[keys.ATOMIC_NUMBERS], ptr=None if cell is not None else data.get("ptr"), cell=cell,
-               pbc=data.get(keys.PBC) if cell is not None else None, fmax=fmax, **kw)
+    opt = METHODS[method](model, data[keys.POSITIONS], data[keys.ATOMIC_NUMBERS], ptr=None if cell is not None else data.get("ptr"), cell=cell,
+                          pbc=data.get(keys.PBC) if cell is not None else None, fmax=fmax, **kw)
     opt.run(max_steps, check_every=check_every)
     return {"pos": opt.positions, "energy": opt.potential_energy, "forces": opt.forces, "converged": opt.converged, "n_steps": opt.step_count}

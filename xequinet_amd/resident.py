@@ -1,4 +1,4 @@
-"""What the drivers that live next to a whole-step graph share (md.Dynamics, optimize.FIRE; DESIGN.md sections 12 and 13): the step object
+"""What the drivers that live next to a whole-step graph share (md.Dynamics, optimize.FIRE, optimize.LBFGS; DESIGN.md sections 12, 13, 16): the step object
 and its static buffers, the chunk tables of the fixed-order per-graph sums, the argument records of the front / back entries that every
 driver fills alike (include/xeq.h: system, step, chunks, recorder), the loop that enqueues front, step graph and back, the one read-back
 per window, and the window / checkpoint / restore / grow protocol for a neighbour list that outgrows its capacity.  A driver supplies the
