@@ -458,7 +458,9 @@ int xeq_to_bt(const void* x, int64_t n_nodes, const int32_t mul[3], void* out, v
  * xeq_train_uv: uv[l] = [N (2l+1), 2 mul_l] row-major (U | V of update_U / update_V in BT rows) -> out[N, 2C] = [Invariant(V) | sum_m U V]
  *   (nn/o3layer.py:40-44, :61-68; eps of the Invariant).  reverse: g = dL/dout, d_uv[l] = dL/duv[l].
  * xeq_train_out: (uv, a[N, C + 2F] = [a_vv | a_sv | a_ss], inner[N, F]) -> out0[N, F] = a_sv inner + a_ss, out1[N, D] = U a_vv (e3nn row)
- *   (nn/xpainn.py:226-230 without the residual).  reverse: g_s, g_x = dL/dout0, dL/dout1; out0 = dL/da, out1 = dL/dinner, d_uv. */
+ *   (nn/xpainn.py:226-230 without the residual).  reverse: g_s, g_x = dL/dout0, dL/dout1; out0 = dL/da, out1 = dL/dinner, d_uv.
+ * N == 0: every entry returns XEQ_OK without a launch once the sizes (and the layout) are accepted, whatever the pointers are -- the
+ *   tensors of an empty batch have null pointers. */
 int xeq_train_norm(int dtype, int reverse, int64_t n, const void* s, const void* s_tan, const void* x, const void* x_tan, const void* ln_w,
                    const void* ln_b, const void* eq_w, const void* eq_b, const void* g_s, const void* g_x, int node_dim,
                    const int32_t mul[3], double eps_ln, double eps_eq, int xhat_layout, void* out_s, void* out_x, void* rows, void* stream);

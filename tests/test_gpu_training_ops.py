@@ -2,6 +2,8 @@
 the sb-family kernels, second order by multilinearity) and nn/training_ops (norms, Invariant / channel dot, update products: second
 order from the same kernel bodies on dual numbers), against finite differences of themselves (``gradcheck`` / ``gradgradcheck``, fp64)
 and against the tensor form of the same arithmetic (nn/training.py with the kernel forms switched off) on a whole model.
+The node functions here run at a toy width (F = 6, mul = (5, 3, 2)); tests/test_gpu_train_node.py runs their entries at model widths and
+row counts, in f32 and f64.
 
 Tolerances: fp64; gradcheck's defaults (atol 1e-5 on difference quotients of step 1e-6); kernel form vs tensor form of the model:
 1e-9 of the largest entry of each gradient (two op orders of the same arithmetic)."""

@@ -372,10 +372,10 @@ int xeq_train_norm(int dtype, int reverse, int64_t n, const void* s, const void*
   Irreps ir{};
   int rc = tn_sizes("xeq_train_norm", n, node_dim, mul, ir);
   if (rc != XEQ_OK) return rc;
-  XEQ_CHECK_ARG((s_tan == nullptr) == (x_tan == nullptr), "xeq_train_norm: tangents of s and x come together");
   XEQ_CHECK_ARG(xhat_layout == 0 || xhat_layout == 1, "xeq_train_norm: layout %d", xhat_layout);
+  if (n == 0) return XEQ_OK;   // before the pointer checks: the tensors of an empty batch have null pointers
+  XEQ_CHECK_ARG((s_tan == nullptr) == (x_tan == nullptr), "xeq_train_norm: tangents of s and x come together");
   XEQ_CHECK_ARG(!reverse || (g_s && g_x && rows), "xeq_train_norm: the reverse form needs g_s, g_x and rows");
-  if (n == 0) return XEQ_OK;
   const bool dual = s_tan != nullptr;
   dim3 grid((unsigned)((n + 3) / 4 < 4096 ? (n + 3) / 4 : 4096));
   XEQ_DISPATCH_FLOAT(dtype, {
@@ -410,8 +410,8 @@ int xeq_train_uv(int dtype, int reverse, int64_t n, const void* const uv[3], con
   Irreps ir{};
   int rc = tn_sizes("xeq_train_uv", n, 1, mul, ir);
   if (rc != XEQ_OK) return rc;
-  XEQ_CHECK_ARG(!reverse || g, "xeq_train_uv: the reverse form needs g");
   if (n == 0) return XEQ_OK;
+  XEQ_CHECK_ARG(!reverse || g, "xeq_train_uv: the reverse form needs g");
   const bool dual = uv_tan != nullptr;
   XEQ_DISPATCH_FLOAT(dtype, {
     UvArgs<T> a{};
@@ -437,10 +437,10 @@ int xeq_train_out(int dtype, int reverse, int64_t n, const void* const uv[3], co
   Irreps ir{};
   int rc = tn_sizes("xeq_train_out", n, node_dim, mul, ir);
   if (rc != XEQ_OK) return rc;
+  if (n == 0) return XEQ_OK;
   XEQ_CHECK_ARG(!reverse || (g_s && g_x && d_uv), "xeq_train_out: the reverse form needs g_s, g_x and d_uv");
   XEQ_CHECK_ARG((uv_tan == nullptr) == (a_tan == nullptr) && (a_tan == nullptr) == (inner_tan == nullptr),
                 "xeq_train_out: the tangents come together");
-  if (n == 0) return XEQ_OK;
   const bool dual = uv_tan != nullptr;
   XEQ_DISPATCH_FLOAT(dtype, {
     UvArgs<T> a{};
