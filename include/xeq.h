@@ -347,10 +347,14 @@ int xeq_compare_many(int n, const void* const* a, const void* const* b, const in
  * (weight_stride 0) or per sample; coeff[p] (host).  The reverse passes w.r.t. x1 / x2 are the same entry on (grad_out, x2) / (x1, grad_out)
  * with permuted tables and the connection mode of the transposed contraction (xequinet_amd/tp.py::_REVERSE).
  * xeq_tensor_product_wgrad: dL/dW of the weighted paths (same table; w_off increasing, w_numel[p] weights per path): shared = 1 writes
- * parts [xeq_tensor_product_wgrad_chunks(n), w_total] (the caller adds the chunks in order), shared = 0 writes dW [n, w_total]. */
+ * parts [xeq_tensor_product_wgrad_chunks(n), w_total] (the caller adds the chunks in order), shared = 0 writes dW [n, w_total].
+ * xeq_tensor_product_form: the form xeq_tensor_product takes for a pass (no launch, no GPU needed): -1 the tied form (every path 'uuu' /
+ * 'uuw' / 'uvu' / 'uvv': a wave per node, a lane per channel), t > 0 the tile form on t nodes per workgroup, 0 when not one row of x1 | x2
+ * fits the LDS tile behind the 3j tables -- xeq_tensor_product refuses such a pass, the caller launches xeq_tensor_product_path per path. */
 int xeq_tensor_product(int dtype, const void* x1, const void* x2, int64_t n, int dim1, int dim2, int dim_out, int n_paths,
                        const int32_t* paths, const void* cg, const int32_t* cg_off, int cg_floats, const void* weight, int64_t weight_stride,
                        const int32_t* w_off, const double* coeff, void* out, void* stream);
+int xeq_tensor_product_form(int dtype, int64_t n, int dim1, int dim2, int n_paths, const int32_t* paths, int cg_floats);
 int64_t xeq_tensor_product_wgrad_chunks(int64_t n);
 int xeq_tensor_product_wgrad(int dtype, const void* x1, const void* x2, const void* g, int64_t n, int dim1, int dim2, int dim_out, int n_paths,
                              const int32_t* paths, const void* cg, const int32_t* cg_off, const int32_t* w_off, const int32_t* w_numel, int w_total,

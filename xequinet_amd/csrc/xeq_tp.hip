@@ -366,6 +366,33 @@ __global__ void __launch_bounds__(256) k_tp_wgrad(TpWArgs a, const T* __restrict
 
 using namespace xeq;
 
+// THE form decision and tile rule of a pass of xeq_tensor_product (the launch and the query xeq_tensor_product_form both call it; paths
+// as the entry takes them, sorted by output block).  TP_FORM_TIED: every path is 'uuu' / 'uuw' / 'uvu' / 'uvv', no output block mixes
+// 'uuw' with the others, every 2 l + 1 <= TP_DMAX -> k_tp_tied, a wave per node.  Otherwise k_tp_fused on a tile of nodes: as many rows
+// of x1 | x2 as fit 60000 bytes of LDS behind the 3j tables, at most 16, halved (rounding up) while fewer than 1024 workgroups would
+// start -- the returned tile; 0: not even one row fits.
+constexpr int TP_FORM_TIED = -1;
+static int tp_form(int dtype, int64_t n, int dim1, int dim2, int n_paths, const int32_t* paths, int cg_floats) {
+  bool tied = true;
+  int first_mode = -1;
+  for (int p = 0; p < n_paths && tied; ++p) {
+    const int32_t* q = paths + 10 * p;
+    const int m = q[9];
+    if (p == 0 || q[2] != paths[10 * (p - 1) + 2]) first_mode = m;   // first path of an output block
+    tied = (m == TP_UUU || m == TP_UUW || m == TP_UVU || m == TP_UVV) && ((m == TP_UUW) == (first_mode == TP_UUW)) &&
+           2 * q[6] + 1 <= TP_DMAX && 2 * q[7] + 1 <= TP_DMAX && 2 * q[8] + 1 <= TP_DMAX;
+  }
+  if (tied) return TP_FORM_TIED;
+  const size_t esz = dtype == XEQ_F64 ? 8 : 4;
+  const size_t row = (size_t)(dim1 + dim2) * esz, fixed = (size_t)cg_floats * esz;
+  if (fixed + row > 60000) return 0;
+  int tn = (int)((60000 - fixed) / row);
+  tn = tn > 16 ? 16 : tn;
+  // enough workgroups to fill the chip before tiles grow
+  while (tn > 1 && (n + tn - 1) / tn < 1024) tn = (tn + 1) / 2;
+  return tn;
+}
+
 extern "C" {
 
 int xeq_tensor_product_path(int dtype, const void* x1, const void* x2, int64_t n, int dim1, int dim2, int dim_out, int off1,
@@ -440,14 +467,8 @@ int xeq_tensor_product(int dtype, const void* x1, const void* x2, int64_t n, int
     for (int p = a.slot[s].p0; p < a.slot[s].p1; ++p)
       XEQ_CHECK_ARG(!a.slot[s].blocked || a.path[p].mode == TP_UVW || a.path[p].mode == TP_UUW, "xeq_tensor_product: an output block mixes 'uvw' / 'uuw' with other modes");
   XEQ_CHECK_ARG(!any_w || weight, "xeq_tensor_product: weighted paths need the weight buffer");
-  bool tied = true;
-  for (int s = 0; s < a.n_slots && tied; ++s)
-    for (int p = a.slot[s].p0; p < a.slot[s].p1; ++p) {
-      const int m = a.path[p].mode;
-      tied = tied && (m == TP_UUU || m == TP_UUW || m == TP_UVU || m == TP_UVV) && ((m == TP_UUW) == (a.path[a.slot[s].p0].mode == TP_UUW)) &&
-             a.path[p].d1 <= TP_DMAX && a.path[p].d2 <= TP_DMAX && a.slot[s].d3 <= TP_DMAX;
-    }
-  if (tied) {
+  const int form = tp_form(dtype, n, dim1, dim2, n_paths, paths, cg_floats);
+  if (form == TP_FORM_TIED) {
     XEQ_DISPATCH_FLOAT(dtype, {
       hipLaunchKernelGGL((k_tp_tied<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, (const T*)x1, (const T*)x2, (const T*)cg,
                          (const T*)weight, (T*)out);
@@ -455,13 +476,10 @@ int xeq_tensor_product(int dtype, const void* x1, const void* x2, int64_t n, int
     XEQ_CHECK_LAUNCH("xeq_tensor_product");
     return XEQ_OK;
   }
+  XEQ_CHECK_ARG(form > 0, "xeq_tensor_product: rows of %d + %d elements and %d table entries do not fit the LDS tile", dim1, dim2, cg_floats);
   const size_t esz = dtype == XEQ_F64 ? 8 : 4;
   const size_t row = (size_t)(dim1 + dim2) * esz, fixed = (size_t)cg_floats * esz;
-  XEQ_CHECK_ARG(fixed + row <= 60000, "xeq_tensor_product: rows of %d + %d elements and %d table entries do not fit the LDS tile", dim1, dim2, cg_floats);
-  int tn = (int)((60000 - fixed) / row);
-  tn = tn > 16 ? 16 : tn;
-  // enough workgroups to fill the chip before tiles grow
-  while (tn > 1 && (n + tn - 1) / tn < 1024) tn = (tn + 1) / 2;
+  const int tn = form;
   a.tn = tn;
   const size_t lds = fixed + (size_t)tn * row;
   XEQ_DISPATCH_FLOAT(dtype, {
@@ -470,6 +488,16 @@ int xeq_tensor_product(int dtype, const void* x1, const void* x2, int64_t n, int
   });
   XEQ_CHECK_LAUNCH("xeq_tensor_product");
   return XEQ_OK;
+}
+
+/* The form a pass of xeq_tensor_product takes for these arguments: -1 the tied form (a wave per node), t > 0 the tile form on t nodes per
+ * workgroup, 0 the tile form when not one row fits the LDS tile (xeq_tensor_product then refuses; the caller launches per path). */
+int xeq_tensor_product_form(int dtype, int64_t n, int dim1, int dim2, int n_paths, const int32_t* paths, int cg_floats) {
+  if (!(n >= 0 && n_paths > 0 && n_paths <= TP_MAXP && paths && dim1 > 0 && dim2 > 0 && cg_floats >= 0 && (dtype == XEQ_F32 || dtype == XEQ_F64))) {
+    xeq::set_error("xeq_tensor_product_form: bad arguments (at most %d paths per launch)", TP_MAXP);
+    return 0;
+  }
+  return tp_form(dtype, n, dim1, dim2, n_paths, paths, cg_floats);
 }
 
 /* Weight gradients of the weighted paths of a product (same path table; w_off[p] >= 0 and w_numel[p] for weighted paths, in increasing

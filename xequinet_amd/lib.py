@@ -137,6 +137,7 @@ _PROTOS = {
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_int,
                                  ctypes.POINTER(c_double), c_int, _P, _P],
     "xeq_tensor_product_wgrad_chunks": [c_int64],
+    "xeq_tensor_product_form": [c_int, c_int64, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int],
     "xeq_scatter_add": [c_int, _P, _P, c_int64, c_int64, _P, c_int64, _P],
     "xeq_message_fwd": [c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                         c_int, c_int, c_int, c_double, c_int, _I3, _P, _P, c_int, _P],
