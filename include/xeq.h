@@ -988,13 +988,12 @@ int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const 
  * graph on the step object's static buffers, a BACK entry; nothing reaches the host between them.
  *
  * The entries take their arguments as RECORDS, by pointer: what every driver has (the system, the step graph's outputs, the chunk
- * tables, the recorder) and, for the six MD / NPT / FIRE entries, one record of parameters per driver; the two L-BFGS entries take the
- * shared records and their own state as plain arguments.  Every member is 8 bytes wide -- a pointer, int64_t, uint64_t or double
+ * tables, the recorder) and one record of parameters per driver.  Every member is 8 bytes wide -- a pointer, int64_t, uint64_t or double
  * -- so a record's layout is its field order, without padding, on any ABI; xeq_record_bytes(which) gives the library's sizeof for a
  * binding to compare with its own (-1: no such record).  A record is read during the call and not retained.  Pointers are device
  * pointers unless marked HOST; `dtype` below: a buffer of the system record's floating type. */
 enum { XEQ_REC_SYSTEM = 0, XEQ_REC_STEP = 1, XEQ_REC_CHUNKS = 2, XEQ_REC_RECORDER = 3, XEQ_REC_MD = 4, XEQ_REC_NPT = 5, XEQ_REC_FIRE = 6,
-       XEQ_REC_NEIGHBORS = 7 /* xeq_neighbor_search, with the neighbour search above */ };
+       XEQ_REC_NEIGHBORS = 7 /* xeq_neighbor_search, with the neighbour search above */, XEQ_REC_LBFGS = 8 };
 int64_t xeq_record_bytes(int which);
 
 typedef struct xeq_res_system {
@@ -1042,7 +1041,7 @@ typedef struct xeq_res_recorder {
   int64_t every, start, rows;
   void* traj_pos;         /* [rows, n, 3] `dtype`, unwrapped: pos + image . cell (xeq_npt_back: by the current cell) */
   void* traj_epot;        /* [rows, n_graphs] `dtype` */
-  void* traj_second;      /* [rows, n_graphs] `dtype`: the kinetic energy (dynamics), fmax (FIRE) */
+  void* traj_second;      /* [rows, n_graphs] `dtype`: the kinetic energy (dynamics), fmax (FIRE, L-BFGS) */
   int64_t* traj_step;     /* [rows] */
   void* traj_cell;        /* xeq_npt_back alone: [rows, 3, 3] `dtype` */
   double* traj_pressure;  /* xeq_npt_back alone: [rows], P p_unit */
@@ -1178,8 +1177,8 @@ int xeq_fire_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq
 
 /* Batched limited-memory BFGS without line search (xequinet_amd/optimize.py: LBFGS, csrc/xeq_lbfgs.hip), by the rule
  * of ASE's optimize.LBFGS with use_line_search=False.  Every graph is its own minimiser: its own history, step clamp and convergence
- * flag.  The entries take the system, step, chunk and recorder records above and the driver's own state as plain arguments (no record of
- * their own).  Free atoms only: a fixed atom has force 0 and displacement 0 and enters no sum.  All per-graph and per-atom arithmetic
+ * flag.  The entries take the system, step, chunk and recorder records above and the driver's own state and parameters in
+ * xeq_lbfgs_params.  Free atoms only: a fixed atom has force 0 and displacement 0 and enters no sum.  All per-graph and per-atom arithmetic
  * runs in double whatever `dtype` is and is rounded once where a `dtype` value is stored.  m = memory, K = 2 m + 1.
  *
  * State per graph: a ring of at most m pairs (s_j, y_j) in hist_s / hist_y, f64 [m, n, 3], slot j of a graph in its atoms' rows of
@@ -1220,16 +1219,34 @@ int xeq_fire_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq
  *   chunk maxima (a chunk's first partial); second launch: the move.
  * max_graph_chunks: the most chunks any graph has; at most 1: the workgroup that owns a graph does both halves of an entry and each
  *   entry is ONE launch (a caller that understates it gets sums over a graph's own chunk alone, no access out of bounds).
- * The recorder's traj_second is fmax.  n = 0: the front does nothing; the back keeps the books. */
+ * The recorder's traj_second is fmax.  n = 0: the front does nothing; the back keeps the books.
+ * Of the record, the front does not read gram, head, dropped, converged_at, epot, fmax, ticket, fmax_tol or alpha (they may be NULL / 0
+ * there); the back does not read maxstep or damping. */
 #define XEQ_LBFGS_MAX_MEMORY 32
 enum { XEQ_LBFGS_FRESH = 0, XEQ_LBFGS_ACTIVE = 1, XEQ_LBFGS_CONVERGED = 2 };
-int xeq_lbfgs_front(const xeq_res_system* sys, const xeq_res_chunks* chunks, const uint8_t* fixed, int64_t memory, int64_t max_graph_chunks,
-                    const double* hist_s, const double* hist_y, double* pending_s, const double* delta, const int32_t* count,
-                    const int32_t* status, double maxstep, double damping, void* stream);
-int xeq_lbfgs_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_res_recorder* rec,
-                   const uint8_t* fixed, int64_t memory, int64_t max_graph_chunks, double* hist_s, double* hist_y, const double* pending_s,
-                   double* gram, double* delta, int32_t* count, int32_t* head, int32_t* status, int32_t* dropped, int64_t* converged_at,
-                   void* epot, void* fmax, int32_t* ticket, double fmax_tol, double alpha, void* stream);
+typedef struct xeq_lbfgs_params {
+  const uint8_t* fixed;       /* [n] or NULL; nonzero = the atom never moves, its force is left out of every sum and its entry in frc is 0 */
+  double* hist_s;             /* [memory, n, 3]: the ring's s_j, plane j */
+  double* hist_y;             /* [memory, n, 3]: the ring's y_j */
+  double* pending_s;          /* [n, 3]: the direction between the front's two launches, the displacement s behind the front */
+  double* gram;               /* [n_graphs, K, K]; the front does not read it */
+  double* delta;              /* [n_graphs, K]: the direction's coefficients, written by the back, read by the front */
+  int32_t* count;             /* [n_graphs]: pairs in the ring */
+  int32_t* head;              /* [n_graphs]: the slot of the next pair; the front does not read it */
+  int32_t* status;            /* [n_graphs]: XEQ_LBFGS_FRESH (no evaluation yet), _ACTIVE, _CONVERGED */
+  int32_t* dropped;           /* [n_graphs]: rejected pairs; the front does not read it */
+  int64_t* converged_at;      /* [n_graphs]: the evaluation at which the graph converged, counted from 0; the caller starts it at -1 */
+  void* epot;                 /* [n_graphs] `dtype` */
+  void* fmax;                 /* [n_graphs] `dtype` */
+  int32_t* ticket;            /* [1]: the back's election, 0 between launches */
+  int64_t memory;             /* m, 1 .. XEQ_LBFGS_MAX_MEMORY */
+  int64_t max_graph_chunks;   /* the most chunks any graph has (above) */
+  double fmax_tol, alpha;     /* read and checked by the back alone */
+  double maxstep, damping;    /* read and checked by the front alone */
+} xeq_lbfgs_params;
+int xeq_lbfgs_front(const xeq_res_system* sys, const xeq_res_chunks* chunks, const xeq_lbfgs_params* lbfgs, void* stream);
+int xeq_lbfgs_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_lbfgs_params* lbfgs,
+                   const xeq_res_recorder* rec, void* stream);
 
 /* Batched harmonic analysis behind the Hessian front (xequinet_amd/vibrations.py, csrc/xeq_vib.hip).  Everything is
  * f64; only the Hessian is read as `dtype` and widened on load.  One workgroup per graph, fixed summation orders, no atomics: a graph's

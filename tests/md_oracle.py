@@ -60,7 +60,7 @@ def normals(seed, purpose, step, rng_id):
 
 
 def inverse_cell(cell):
-    """The adjugate formula of csrc/xeq_md.hip (md_box), in its operation order: frac_k = sum_j x_j inv[j, k]."""
+    """The adjugate formula of csrc/xeq_resident.h (md_inverse), in its operation order: frac_k = sum_j x_j inv[j, k]."""
     c = np.asarray(cell, dtype=np.float64).reshape(9)
     det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6])
     m = [c[4] * c[8] - c[5] * c[7], c[2] * c[7] - c[1] * c[8], c[1] * c[5] - c[2] * c[4],
@@ -70,7 +70,7 @@ def inverse_cell(cell):
 
 
 def wrap(x, image, cell, inv, pbc, dtype):
-    """md_wrap: two passes of (round to dtype, floor of the fractional coordinate, subtract); x f64 [n, 3] -> (x f64 holding dtype values
+    """res_wrap (csrc/xeq_resident.h): two passes of (round to dtype, floor of the fractional coordinate, subtract); x f64 [n, 3] -> (x f64 holding dtype values
     after the caller's final rounding, image)."""
     per = np.asarray(pbc, dtype=bool)
     image = image.copy()

@@ -194,17 +194,17 @@ def _device_round(dtype, ptr, st, x, frc0, f_step, fixed, energy, book, memory, 
                       book=g["book"], cell=cell_c, pbc=pbc_c)
     step = lib.fill(lib.ResStep(), frc_step=g["fs"], energy_step=g["en"], n_edges_step=g["ne"])
     chunks = lib.fill(lib.ResChunks(), chunk_atom0=g["a0"], chunk_n=g["cn"], graph_chunk_ptr=g["gp"], partial=g["partial"], partial_bad=g["pbad"])
-    p = lib.ptr
+    params = lib.fill(lib.LbfgsParams(), fixed=g["fixed"], hist_s=g["hist_s"], hist_y=g["hist_y"], pending_s=g["pending"], gram=g["gram"],
+                      delta=g["delta"], count=g["count"], head=g["head"], status=g["status"], dropped=g["dropped"], converged_at=g["converged_at"],
+                      epot=g["epot"], fmax=g["fmax"], ticket=g["ticket"], memory=memory, max_graph_chunks=most, fmax_tol=FMAX, alpha=ALPHA,
+                      maxstep=MAXSTEP, damping=DAMPING)
     first = lib.launch_count()
-    lib.call("xeq_lbfgs_back", ctypes.byref(system), ctypes.byref(step), ctypes.byref(chunks), None, p(g["fixed"]), memory, most, p(g["hist_s"]),
-             p(g["hist_y"]), p(g["pending"]), p(g["gram"]), p(g["delta"]), p(g["count"]), p(g["head"]), p(g["status"]), p(g["dropped"]),
-             p(g["converged_at"]), p(g["epot"]), p(g["fmax"]), p(g["ticket"]), FMAX, ALPHA, lib.stream())
+    lib.call("xeq_lbfgs_back", ctypes.byref(system), ctypes.byref(step), ctypes.byref(chunks), ctypes.byref(params), None, lib.stream())
     torch.cuda.synchronize()
     gb.check(*g.values())
     behind_back = {k: t.cpu().numpy() for k, t in g.items()}
     assert lib.launch_count() - first == (1 if most <= 1 else 2)
-    lib.call("xeq_lbfgs_front", ctypes.byref(system), ctypes.byref(chunks), p(g["fixed"]), memory, most, p(g["hist_s"]), p(g["hist_y"]),
-             p(g["pending"]), p(g["delta"]), p(g["count"]), p(g["status"]), MAXSTEP, DAMPING, lib.stream())
+    lib.call("xeq_lbfgs_front", ctypes.byref(system), ctypes.byref(chunks), ctypes.byref(params), lib.stream())
     torch.cuda.synchronize()
     gb.check(*g.values())
     assert lib.launch_count() - first == (2 if most <= 1 else 4)

@@ -191,9 +191,14 @@ def test_entries_report_argument_errors_without_a_gpu():
     def system(dtype=0, n=4, g=1, c=1, cell=None, pbc=None):
         return ref(fill(lib.ResSystem(), dtype=dtype, n=n, n_graphs=g, n_chunks=c, cell=cell, pbc=pbc))
 
-    def front(memory=4, most=1, maxstep=0.2, damping=1.0, sys=None, chunks=True, buf=None):
-        return L.xeq_lbfgs_front(sys or system(), ref(lib.ResChunks()) if chunks else None, None, memory, most, buf, buf, buf, buf, buf, buf,
-                                 maxstep, damping, None)
+    def params(buf, **members):
+        """The parameter record with every buffer but ``fixed`` at ``buf``."""
+        state = "hist_s hist_y pending_s gram delta count head status dropped converged_at epot fmax ticket"
+        return ref(fill(lib.LbfgsParams(), **dict.fromkeys(state.split(), buf), **members))
+
+    def front(memory=4, most=1, maxstep=0.2, damping=1.0, sys=None, chunks=True, buf=None, record=True):
+        rec = params(buf, memory=memory, max_graph_chunks=most, maxstep=maxstep, damping=damping) if record else None
+        return L.xeq_lbfgs_front(sys or system(), ref(lib.ResChunks()) if chunks else None, rec, None)
 
     assert front(sys=system(dtype=2)) == 1 and b"dtype" in L.xeq_last_error()
     assert front(sys=system(n=-1)) == 1 and b"atoms" in L.xeq_last_error()
@@ -208,14 +213,17 @@ def test_entries_report_argument_errors_without_a_gpu():
     assert front(damping=-1.0) == 1 and b"damping" in L.xeq_last_error()
     assert front() == 1 and b"null state buffer" in L.xeq_last_error()
     assert front(chunks=False) == 1 and b"null argument record" in L.xeq_last_error()
-    assert L.xeq_lbfgs_front(None, ref(lib.ResChunks()), None, 4, 1, *([None] * 6), 0.2, 1.0, None) == 1 and b"record" in L.xeq_last_error()
+    assert front(record=False) == 1 and b"null argument record" in L.xeq_last_error()
+    assert L.xeq_lbfgs_front(None, ref(lib.ResChunks()), params(None, memory=4, max_graph_chunks=1, maxstep=0.2, damping=1.0), None) == 1
+    assert b"record" in L.xeq_last_error()
     sing = (ctypes.c_double * 9)(1, 0, 0, 1, 0, 0, 0, 0, 1)
     assert front(sys=system(cell=sing, pbc=(ctypes.c_int32 * 3)(1, 1, 1))) == 1 and b"singular" in L.xeq_last_error()
     assert front(sys=system(n=0, c=0), most=0) == 0                                          # nothing to do: no launch
 
-    def back(memory=4, most=1, fmax=0.05, alpha=70.0, sys=None, step=True, every=0, buf=None):
-        return L.xeq_lbfgs_back(sys or system(), ref(lib.ResStep()) if step else None, ref(lib.ResChunks()), ref(fill(lib.ResRecorder(), every=every)),
-                                None, memory, most, *([buf] * 13), fmax, alpha, None)
+    def back(memory=4, most=1, fmax=0.05, alpha=70.0, sys=None, step=True, every=0, buf=None, record=True):
+        rec = params(buf, memory=memory, max_graph_chunks=most, fmax_tol=fmax, alpha=alpha) if record else None
+        return L.xeq_lbfgs_back(sys or system(), ref(lib.ResStep()) if step else None, ref(lib.ResChunks()), rec,
+                                ref(fill(lib.ResRecorder(), every=every)), None)
 
     assert back(sys=system(dtype=-1)) == 1 and b"dtype" in L.xeq_last_error()
     assert back(sys=system(g=-1)) == 1 and b"graphs" in L.xeq_last_error()
@@ -228,6 +236,7 @@ def test_entries_report_argument_errors_without_a_gpu():
     assert back(alpha=-70.0) == 1 and b"alpha" in L.xeq_last_error()
     assert back(every=-2) == 1 and b"recorder" in L.xeq_last_error()
     assert back(step=False) == 1 and b"null argument record" in L.xeq_last_error()
+    assert back(record=False) == 1 and b"null argument record" in L.xeq_last_error()
     assert back() == 1 and b"null" in L.xeq_last_error()
     assert back(buf=one, sys=ref(fill(lib.ResSystem(), n=4, n_graphs=1, n_chunks=1, book=one))) == 1 and b"null" in L.xeq_last_error()      # the records' buffers
     assert lib.launch_count() == first

@@ -48,7 +48,7 @@ def test_records_match_the_header_member_for_member():
     L = lib.load()
     assert sorted(records) == sorted(r.__name__ for r in lib.RECORDS)              # every record of the header has its mirror, and no other
     which = {"xeq_res_system": "SYSTEM", "xeq_res_step": "STEP", "xeq_res_chunks": "CHUNKS", "xeq_res_recorder": "RECORDER", "xeq_md_params": "MD",
-             "xeq_npt_params": "NPT", "xeq_fire_params": "FIRE", "xeq_neighbor_search": "NEIGHBORS"}
+             "xeq_npt_params": "NPT", "xeq_fire_params": "FIRE", "xeq_neighbor_search": "NEIGHBORS", "xeq_lbfgs_params": "LBFGS"}
     for index, rec in enumerate(lib.RECORDS):
         members = records[rec.__name__]
         assert const["XEQ_REC_" + which[rec.__name__]] == index, rec.__name__      # lib.RECORDS is in the order of XEQ_REC_*
@@ -67,6 +67,7 @@ def test_records_match_the_header_member_for_member():
     assert L.xeq_record_bytes(len(lib.RECORDS)) == -1 and L.xeq_record_bytes(-1) == -1
     # the entries take them by pointer
     assert L.xeq_npt_back.argtypes[:6] == [ctypes.POINTER(r) for r in (lib.ResSystem, lib.ResStep, lib.ResChunks, lib.MdParams, lib.NptParams, lib.ResRecorder)]
+    assert L.xeq_lbfgs_back.argtypes[:5] == [ctypes.POINTER(r) for r in (lib.ResSystem, lib.ResStep, lib.ResChunks, lib.LbfgsParams, lib.ResRecorder)]
 
 
 def test_fill_refuses_a_member_the_record_does_not_have():
@@ -87,10 +88,10 @@ def test_restated_constants_are_the_headers():
     from xequinet_amd import lib
 
     const = _constants(_header())
-    names = [k for k in const if re.match(r"XEQ_(MD|NPT|FIRE)_", k)]
+    names = [k for k in const if re.match(r"XEQ_(MD|NPT|FIRE|LBFGS)_", k)]
     assert {"XEQ_MD_CHUNK", "XEQ_MD_NVE", "XEQ_MD_LANGEVIN", "XEQ_MD_BERENDSEN", "XEQ_MD_PURPOSE_LANGEVIN", "XEQ_MD_PURPOSE_MAXWELL", "XEQ_NPT_BOX",
             "XEQ_NPT_CELL", "XEQ_NPT_INV", "XEQ_NPT_CELL_NEXT", "XEQ_NPT_INV_NEXT", "XEQ_NPT_MU", "XEQ_NPT_P", "XEQ_NPT_V", "XEQ_FIRE_FRESH",
-            "XEQ_FIRE_ACTIVE", "XEQ_FIRE_CONVERGED"} == set(names)
+            "XEQ_FIRE_ACTIVE", "XEQ_FIRE_CONVERGED", "XEQ_LBFGS_FRESH", "XEQ_LBFGS_ACTIVE", "XEQ_LBFGS_CONVERGED", "XEQ_LBFGS_MAX_MEMORY"} == set(names)
     for k in names:
         assert getattr(lib, k[len("XEQ_"):]) == const[k], k
     from xequinet_amd import md

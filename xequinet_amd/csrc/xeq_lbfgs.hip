@@ -14,6 +14,7 @@
 // atomic, and no sum goes through it.  The file is built with -ffp-contract=off (csrc/build.py): the double expressions are the ones
 // written here, operation by operation.
 #include "xeq_common.h"
+#include "xeq_resident.h"
 
 namespace xeq {
 
@@ -23,13 +24,6 @@ constexpr int LB_MAX_M = XEQ_LBFGS_MAX_MEMORY;
 constexpr int LB_MAX_K = 2 * LB_MAX_M + 1;   // basis vectors: s slots, y slots, g
 constexpr int LB_GROUP = 4;               // columns of the back's first half whose loads are in flight together
 constexpr int LB_MAX_W = 2 * LB_MAX_M + 3;   // columns of a candidate's partial row: s slots, y slots, the candidates s, y, g
-
-struct LbBox {
-  double cell[9];   // rows: lattice vectors
-  double inv[9];    // frac_k = sum_j x_j inv[3 j + k]
-  int periodic[3];
-  int any;
-};
 
 template <typename T>
 struct LbArgs {
@@ -64,7 +58,7 @@ struct LbArgs {
   int32_t* ticket;
   double fmax_tol, inv_alpha, maxstep, damping;
   int32_t* image;
-  LbBox box;
+  ResBox box;
   int64_t record_every, record_start, record_rows;
   T* traj_pos;
   T* traj_epot;
@@ -72,40 +66,7 @@ struct LbArgs {
   int64_t* traj_step;
 };
 
-__device__ __forceinline__ double lb_wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double lb_wave_max(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 __device__ __forceinline__ double lb_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ int64_t lb_record_row(int64_t every, int64_t start, int64_t rows, int64_t eval) {
-  if (every <= 0) return -1;
-  const int64_t d = eval - start;
-  if (d <= 0 || d % every) return -1;
-  const int64_t row = d / every - 1;
-  return row < rows ? row : -1;
-}
-
-// The wrap of xeq_md_front (csrc/xeq_md.hip: md_wrap), operation by operation.
-template <typename T>
-__device__ __forceinline__ void lb_wrap(const LbBox& b, double x[3], int32_t img[3]) {
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int k = 0; k < 3; ++k) x[k] = (double)(T)x[k];
-    double s[3];
-    for (int k = 0; k < 3; ++k) {
-      const double fr = (x[0] * b.inv[k] + x[1] * b.inv[3 + k]) + x[2] * b.inv[6 + k];
-      s[k] = b.periodic[k] ? floor(fr) : 0.0;
-    }
-    for (int j = 0; j < 3; ++j) x[j] = x[j] - ((s[0] * b.cell[j] + s[1] * b.cell[3 + j]) + s[2] * b.cell[6 + j]);
-    for (int k = 0; k < 3; ++k) img[k] += (int32_t)s[k];
-  }
-}
 
 // What every workgroup knows of its chunk: its atoms, its graph and that graph's chunks.
 struct LbChunk {
@@ -164,16 +125,8 @@ __device__ __forceinline__ void lb_back_chunk(const LbArgs<T>& a, int64_t c, dou
         cand[1][j] = (double)a.frc[3 * i + j] - f;
       }
     }
-    const int64_t row = lb_record_row(a.record_every, a.record_start, a.record_rows, a.book[0]);
-    if (row >= 0) {
-      for (int j = 0; j < 3; ++j) {
-        double x = (double)a.pos[3 * i + j];
-        if (a.box.any)
-          x = x + (((double)a.image[3 * i] * a.box.cell[j] + (double)a.image[3 * i + 1] * a.box.cell[3 + j]) +
-                   (double)a.image[3 * i + 2] * a.box.cell[6 + j]);
-        a.traj_pos[(row * a.n + i) * 3 + j] = (T)x;
-      }
-    }
+    const int64_t row = res_record_row(a.record_every, a.record_start, a.record_rows, a.book[0]);
+    if (row >= 0) res_store_unwrapped(a.traj_pos, row, a.n, i, a.pos, a.image, a.box.any, a.box.cell);
   }
   const int any_bad = __syncthreads_or(bad);
   if (!frozen) {
@@ -204,12 +157,12 @@ __device__ __forceinline__ void lb_back_chunk(const LbArgs<T>& a, int64_t c, dou
         const int col = c0 + u;
         if (col >= W) break;
         for (int q = 0; q < 3; ++q) {
-          const double v = lb_wave_sum(lb_dot(cand[q], b[u]));
+          const double v = res_wave_sum(lb_dot(cand[q], b[u]));
           if (lane == 0) wsum[q * W + col][wave] = empty[u] ? 0.0 : v;
         }
       }
     }
-    const double m2 = lb_wave_max(lb_dot(cand[2], cand[2]));
+    const double m2 = res_wave_max(lb_dot(cand[2], cand[2]));
     if (lane == 0) wsum[3 * W][wave] = m2;
   }
   __syncthreads();
@@ -241,7 +194,7 @@ __device__ __forceinline__ void lb_back_graph(const LbArgs<T>& a, int64_t c, dou
   const bool first = c == k.cb;
   const int st = a.meta[4 * c + 1], hd = a.meta[4 * c + 2] & 255, cnt = a.meta[4 * c + 2] >> 8;
   const int64_t eval = a.book[0];
-  const int64_t row = lb_record_row(a.record_every, a.record_start, a.record_rows, eval);
+  const int64_t row = res_record_row(a.record_every, a.record_start, a.record_rows, eval);
   if (st == XEQ_LBFGS_CONVERGED) {   // left alone, bit for bit; only its recorder row is filled, from what it kept
     if (first && tid == 0) {
       a.meta[4 * c + 3] = 0;
@@ -328,7 +281,7 @@ __device__ __forceinline__ void lb_back_graph(const LbArgs<T>& a, int64_t c, dou
     auto rowdot = [&](int r) {
       double t = on0 ? Bl[r * K + k0] * d0 : 0.0;
       if (on1) t = t + Bl[r * K + k1] * d1;
-      return lb_wave_sum(t);
+      return res_wave_sum(t);
     };
     for (int t = 0; t < cnt2; ++t) {   // newest to oldest
       const int slot = (hd2 - 1 - t + 2 * m) % m;
@@ -367,7 +320,7 @@ __device__ __forceinline__ void lb_books(const LbArgs<T>& a, int* slast) {
   if (!*slast) return;
   __threadfence();
   const int64_t eval = a.book[0];
-  const int64_t row = lb_record_row(a.record_every, a.record_start, a.record_rows, eval);
+  const int64_t row = res_record_row(a.record_every, a.record_start, a.record_rows, eval);
   int bad = 0;
   int64_t active = 0;
   for (int64_t base = 0; base < a.n_graphs; base += LB_CHUNK) {
@@ -473,7 +426,7 @@ __device__ __forceinline__ void lb_front_direction(const LbArgs<T>& a, int64_t c
     }
     p2 = lb_dot(p, p);
   }
-  p2 = lb_wave_max(p2);
+  p2 = res_wave_max(p2);
   if (lane == 0) wmax[wave] = p2;
   __syncthreads();
   if (tid == 0) {
@@ -505,7 +458,7 @@ __device__ __forceinline__ void lb_front_move(const LbArgs<T>& a, int64_t c) {
   }
   if (a.box.any) {
     int32_t img[3] = {a.image[3 * i], a.image[3 * i + 1], a.image[3 * i + 2]};
-    lb_wrap<T>(a.box, x, img);
+    res_wrap<T>(a.box, x, img);
     for (int j = 0; j < 3; ++j) a.image[3 * i + j] = img[j];
   }
   for (int j = 0; j < 3; ++j) a.pos[3 * i + j] = (T)x[j];
@@ -532,39 +485,28 @@ __global__ void __launch_bounds__(LB_CHUNK) k_lbfgs_front_fused(LbArgs<T> a) {
 }
 
 // --------------------------------------------------------------------------------------------------------------- host
-static inline bool lb_finite(double x) { return x - x == 0.0; }
-
-static bool lb_box(const double* cell, const int32_t* pbc, LbBox* b) {
-  b->any = 0;
-  for (int k = 0; k < 9; ++k) b->cell[k] = b->inv[k] = 0.0;
-  for (int k = 0; k < 3; ++k) b->periodic[k] = (cell && pbc && pbc[k]) ? 1 : 0;
-  if (!cell || !(b->periodic[0] || b->periodic[1] || b->periodic[2])) return true;
-  if (xeq_md_inverse_cell(cell, b->inv) != XEQ_OK) return false;   // the inverse the wrap of every resident driver uses
-  for (int k = 0; k < 9; ++k) b->cell[k] = cell[k];
-  b->any = 1;
-  return true;
-}
-
-static const int64_t LB_MAX_ATOMS = ((int64_t)1 << 31) / 3;
-
-// What both entries ask of the sizes; `who`: the entry's name.
-static int lb_sizes(const char* who, const xeq_res_system* s, int64_t memory, int64_t max_graph_chunks) {
-  XEQ_CHECK_ARG(s->dtype == XEQ_F32 || s->dtype == XEQ_F64, "%s: dtype %lld (0 f32, 1 f64)", who, (long long)s->dtype);
-  XEQ_CHECK_ARG(s->n >= 0 && s->n < LB_MAX_ATOMS && s->n_graphs >= 0 && s->n_chunks >= 0 && s->n_chunks < ((int64_t)1 << 29),
-                "%s: %lld atoms, %lld graphs, %lld chunks", who, (long long)s->n, (long long)s->n_graphs, (long long)s->n_chunks);
-  XEQ_CHECK_ARG(s->n == 0 || s->n_graphs >= 1, "%s: %lld atoms in no graph", who, (long long)s->n);
-  XEQ_CHECK_ARG(s->n_chunks <= s->n && s->n_chunks * XEQ_MD_CHUNK >= s->n, "%s: %lld chunks of at most %d atoms cannot hold %lld atoms", who,
-                (long long)s->n_chunks, XEQ_MD_CHUNK, (long long)s->n);
-  XEQ_CHECK_ARG(memory >= 1 && memory <= XEQ_LBFGS_MAX_MEMORY, "%s: memory %lld (1 .. XEQ_LBFGS_MAX_MEMORY = %d)", who, (long long)memory,
+// What both entries ask of the memory and of what it makes of the chunk count; `who`: the entry's name.
+static int lb_memory(const char* who, const xeq_res_system* s, const xeq_lbfgs_params* p) {
+  XEQ_CHECK_ARG(p->memory >= 1 && p->memory <= XEQ_LBFGS_MAX_MEMORY, "%s: memory %lld (1 .. XEQ_LBFGS_MAX_MEMORY = %d)", who, (long long)p->memory,
                 XEQ_LBFGS_MAX_MEMORY);
-  XEQ_CHECK_ARG(max_graph_chunks >= 0 && max_graph_chunks <= s->n_chunks, "%s: at most %lld chunks in a graph, of %lld chunks", who,
-                (long long)max_graph_chunks, (long long)s->n_chunks);
-  XEQ_CHECK_ARG(s->n_chunks * (3 * (2 * memory + 3) + 1) < ((int64_t)1 << 31) && s->n * memory * 3 < ((int64_t)1 << 40),
-                "%s: %lld chunks with memory %lld: the partial sums do not fit", who, (long long)s->n_chunks, (long long)memory);
+  XEQ_CHECK_ARG(p->max_graph_chunks >= 0 && p->max_graph_chunks <= s->n_chunks, "%s: at most %lld chunks in a graph, of %lld chunks", who,
+                (long long)p->max_graph_chunks, (long long)s->n_chunks);
+  XEQ_CHECK_ARG(s->n_chunks * (3 * (2 * p->memory + 3) + 1) < ((int64_t)1 << 31) && s->n * p->memory * 3 < ((int64_t)1 << 40),
+                "%s: %lld chunks with memory %lld: the partial sums do not fit", who, (long long)s->n_chunks, (long long)p->memory);
   return XEQ_OK;
 }
 
-static const xeq_res_recorder LB_NO_RECORDER = {};
+// The kernel arguments both entries fill alike; the back adds the step's outputs, its own state and the recorder.
+template <typename T>
+static LbArgs<T> lb_args(const xeq_res_system* sys, const xeq_res_chunks* chunks, const xeq_lbfgs_params* p, const ResBox& box) {
+  LbArgs<T> a{};
+  a.n = sys->n, a.n_graphs = sys->n_graphs, a.n_chunks = sys->n_chunks, a.m = (int)p->memory, a.fused = p->max_graph_chunks <= 1;
+  a.pos = (T*)sys->pos, a.frc = (T*)sys->frc, a.fixed = p->fixed, a.batch = sys->batch;
+  a.chunk_atom0 = chunks->chunk_atom0, a.chunk_n = chunks->chunk_n, a.graph_chunk_ptr = chunks->graph_chunk_ptr, a.partial = chunks->partial;
+  a.hist_s = p->hist_s, a.hist_y = p->hist_y, a.pending = p->pending_s, a.delta = p->delta;
+  a.count = p->count, a.status = p->status, a.image = sys->image, a.box = box;
+  return a;
+}
 
 }  // namespace xeq
 
@@ -572,29 +514,27 @@ using namespace xeq;
 
 extern "C" {
 
-int xeq_lbfgs_front(const xeq_res_system* sys, const xeq_res_chunks* chunks, const uint8_t* fixed, int64_t memory, int64_t max_graph_chunks,
-                    const double* hist_s, const double* hist_y, double* pending_s, const double* delta, const int32_t* count,
-                    const int32_t* status, double maxstep, double damping, void* stream) {
+int xeq_lbfgs_front(const xeq_res_system* sys, const xeq_res_chunks* chunks, const xeq_lbfgs_params* lbfgs, void* stream) {
   const char* who = "xeq_lbfgs_front";
-  XEQ_CHECK_ARG(sys && chunks, "%s: null argument record", who);
-  if (int e = lb_sizes(who, sys, memory, max_graph_chunks)) return e;
-  XEQ_CHECK_ARG(maxstep > 0.0 && lb_finite(maxstep), "%s: maxstep %g", who, maxstep);
-  XEQ_CHECK_ARG(damping > 0.0 && lb_finite(damping), "%s: damping %g", who, damping);
-  LbBox box;
-  XEQ_CHECK_ARG(lb_box(sys->cell, sys->pbc, &box), "%s: the cell is singular or not finite", who);
+  RES_TRY(res_dtype(who, sys, chunks && lbfgs));
+  const xeq_lbfgs_params& p = *lbfgs;
+  RES_TRY(res_batch_sizes(who, sys, (int64_t)1 << 29));
+  RES_TRY(res_in_graph(who, sys));
+  RES_TRY(res_chunks_hold(who, sys));
+  RES_TRY(lb_memory(who, sys, lbfgs));
+  XEQ_CHECK_ARG(p.maxstep > 0.0 && res_finite(p.maxstep), "%s: maxstep %g", who, p.maxstep);
+  XEQ_CHECK_ARG(p.damping > 0.0 && res_finite(p.damping), "%s: damping %g", who, p.damping);
+  ResBox box;
+  RES_TRY(res_box(who, sys, &box));
   const int64_t n = sys->n;
   XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->frc && sys->batch && chunks->chunk_atom0 && chunks->chunk_n && chunks->graph_chunk_ptr &&
-                           chunks->partial && hist_s && hist_y && pending_s && delta && count && status),
+                           chunks->partial && p.hist_s && p.hist_y && p.pending_s && p.delta && p.count && p.status),
                 "%s: null state buffer", who);
   XEQ_CHECK_ARG(n == 0 || !box.any || sys->image, "%s: a periodic system needs the image counts", who);
   if (n == 0) return XEQ_OK;
   XEQ_DISPATCH_FLOAT(sys->dtype, {
-    LbArgs<T> a{};
-    a.n = n, a.n_graphs = sys->n_graphs, a.n_chunks = sys->n_chunks, a.m = (int)memory, a.fused = max_graph_chunks <= 1;
-    a.pos = (T*)sys->pos, a.frc = (T*)sys->frc, a.fixed = fixed, a.batch = sys->batch;
-    a.chunk_atom0 = chunks->chunk_atom0, a.chunk_n = chunks->chunk_n, a.graph_chunk_ptr = chunks->graph_chunk_ptr, a.partial = chunks->partial;
-    a.hist_s = (double*)hist_s, a.hist_y = (double*)hist_y, a.pending = pending_s, a.delta = (double*)delta;
-    a.count = (int32_t*)count, a.status = (int32_t*)status, a.maxstep = maxstep, a.damping = damping, a.image = sys->image, a.box = box;
+    LbArgs<T> a = lb_args<T>(sys, chunks, lbfgs, box);
+    a.maxstep = p.maxstep, a.damping = p.damping;
     const dim3 grid((unsigned)sys->n_chunks), block(LB_CHUNK);
     if (a.fused) {
       hipLaunchKernelGGL(k_lbfgs_front_fused<T>, grid, block, 0, (hipStream_t)stream, a);
@@ -609,44 +549,35 @@ int xeq_lbfgs_front(const xeq_res_system* sys, const xeq_res_chunks* chunks, con
   return XEQ_OK;
 }
 
-int xeq_lbfgs_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_res_recorder* rec,
-                   const uint8_t* fixed, int64_t memory, int64_t max_graph_chunks, double* hist_s, double* hist_y, const double* pending_s,
-                   double* gram, double* delta, int32_t* count, int32_t* head, int32_t* status, int32_t* dropped, int64_t* converged_at,
-                   void* epot, void* fmax, int32_t* ticket, double fmax_tol, double alpha, void* stream) {
+int xeq_lbfgs_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_lbfgs_params* lbfgs,
+                   const xeq_res_recorder* rec, void* stream) {
   const char* who = "xeq_lbfgs_back";
-  XEQ_CHECK_ARG(sys && step && chunks, "%s: null argument record", who);
-  if (!rec) rec = &LB_NO_RECORDER;
-  if (int e = lb_sizes(who, sys, memory, max_graph_chunks)) return e;
-  XEQ_CHECK_ARG(fmax_tol > 0.0 && lb_finite(fmax_tol), "%s: fmax %g", who, fmax_tol);
-  XEQ_CHECK_ARG(alpha > 0.0 && lb_finite(alpha), "%s: alpha %g", who, alpha);
-  XEQ_CHECK_ARG(rec->every >= 0 && rec->rows >= 0 && rec->start >= 0, "%s: recorder (%lld, %lld, %lld)", who, (long long)rec->every,
-                (long long)rec->start, (long long)rec->rows);
-  LbBox box;
-  XEQ_CHECK_ARG(lb_box(sys->cell, sys->pbc, &box), "%s: the cell is singular or not finite", who);
+  RES_TRY(res_dtype(who, sys, step && chunks && lbfgs));
+  if (!rec) rec = &RES_NO_RECORDER;
+  const xeq_lbfgs_params& p = *lbfgs;
+  RES_TRY(res_batch_sizes(who, sys, (int64_t)1 << 29));
+  RES_TRY(res_in_graph(who, sys));
+  RES_TRY(res_chunks_hold(who, sys));
+  RES_TRY(lb_memory(who, sys, lbfgs));
+  XEQ_CHECK_ARG(p.fmax_tol > 0.0 && res_finite(p.fmax_tol), "%s: fmax %g", who, p.fmax_tol);
+  XEQ_CHECK_ARG(p.alpha > 0.0 && res_finite(p.alpha), "%s: alpha %g", who, p.alpha);
+  RES_TRY(res_recorder(who, rec));
+  ResBox box;
+  RES_TRY(res_box(who, sys, &box));
   const int64_t n = sys->n, n_graphs = sys->n_graphs;
-  XEQ_CHECK_ARG(sys->book && step->n_edges_step && ticket, "%s: null evaluation counter, edge count or ticket", who);
-  XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->frc && sys->batch && step->frc_step && chunks->chunk_atom0 && chunks->chunk_n && chunks->partial &&
-                           chunks->partial_bad && hist_s && hist_y && pending_s),
+  XEQ_CHECK_ARG(sys->book && step->n_edges_step && p.ticket, "%s: null evaluation counter, edge count or ticket", who);
+  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks, false) && sys->batch && p.hist_s && p.hist_y && p.pending_s),
                 "%s: null per-atom or per-chunk buffer", who);
-  XEQ_CHECK_ARG(n_graphs == 0 || (step->energy_step && chunks->graph_chunk_ptr && gram && delta && count && head && status && dropped &&
-                                  converged_at && epot && fmax),
+  XEQ_CHECK_ARG(n_graphs == 0 || (step->energy_step && chunks->graph_chunk_ptr && p.gram && p.delta && p.count && p.head && p.status && p.dropped &&
+                                  p.converged_at && p.epot && p.fmax),
                 "%s: null per-graph buffer", who);
   const bool on = rec->every > 0 && rec->rows > 0;
-  if (on) {
-    XEQ_CHECK_ARG((n == 0 || rec->traj_pos) && (n_graphs == 0 || (rec->traj_epot && rec->traj_second)) && rec->traj_step,
-                  "%s: null trajectory buffer", who);
-    XEQ_CHECK_ARG(n == 0 || !box.any || sys->image, "%s: a periodic system's recorder needs the image counts", who);
-  }
+  if (on) RES_TRY(res_trajectory(who, sys, rec, box));
   XEQ_DISPATCH_FLOAT(sys->dtype, {
-    LbArgs<T> a{};
-    a.n = n, a.n_graphs = n_graphs, a.n_chunks = sys->n_chunks, a.m = (int)memory, a.fused = max_graph_chunks <= 1;
-    a.pos = (T*)sys->pos, a.frc = (T*)sys->frc, a.frc_step = (const T*)step->frc_step, a.energy_step = (const T*)step->energy_step;
-    a.n_edges_step = step->n_edges_step, a.fixed = fixed, a.batch = sys->batch;
-    a.chunk_atom0 = chunks->chunk_atom0, a.chunk_n = chunks->chunk_n, a.graph_chunk_ptr = chunks->graph_chunk_ptr;
-    a.partial = chunks->partial, a.meta = chunks->partial_bad;
-    a.hist_s = hist_s, a.hist_y = hist_y, a.pending = (double*)pending_s, a.gram = gram, a.delta = delta;
-    a.count = count, a.head = head, a.status = status, a.dropped = dropped, a.converged_at = converged_at, a.epot = (T*)epot, a.fmax = (T*)fmax;
-    a.book = sys->book, a.ticket = ticket, a.fmax_tol = fmax_tol, a.inv_alpha = 1.0 / alpha, a.image = sys->image, a.box = box;
+    LbArgs<T> a = lb_args<T>(sys, chunks, lbfgs, box);
+    a.frc_step = (const T*)step->frc_step, a.energy_step = (const T*)step->energy_step, a.n_edges_step = step->n_edges_step;
+    a.meta = chunks->partial_bad, a.gram = p.gram, a.head = p.head, a.dropped = p.dropped, a.converged_at = p.converged_at;
+    a.epot = (T*)p.epot, a.fmax = (T*)p.fmax, a.book = sys->book, a.ticket = p.ticket, a.fmax_tol = p.fmax_tol, a.inv_alpha = 1.0 / p.alpha;
     a.record_every = on ? rec->every : 0, a.record_start = rec->start, a.record_rows = rec->rows;
     a.traj_pos = (T*)rec->traj_pos, a.traj_epot = (T*)rec->traj_epot, a.traj_fmax = (T*)rec->traj_second, a.traj_step = rec->traj_step;
     const dim3 grid((unsigned)(sys->n_chunks > 0 ? sys->n_chunks : 1)), block(LB_CHUNK);

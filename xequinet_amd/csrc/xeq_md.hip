@@ -3,7 +3,8 @@
 // xeq_md_normals; behind them the two halves of the batched FIRE minimiser (xequinet_amd/optimize.py), which share
 // the wrap, the chunk sums and the join; the Berendsen barostat's two halves (xeq_npt_front / xeq_npt_back), which
 // are the MD halves with a box that lives on the device, and the kernel that forms the periodic search's cell tables from that box
-// (xeq_pbc_tables_device).  Plain vector code, f32 and f64 state.
+// (xeq_pbc_tables_device).  Plain vector code, f32 and f64 state.  The box, the wrap, the recorder's rules and the entries' shared argument
+// checks are in xeq_resident.h, which xeq_lbfgs.hip includes too.
 //
 // Arithmetic.  Every per-atom update is evaluated in double whatever the state's type and rounded ONCE when it is stored: the state of an
 // f32 run is within half an ulp of the f64 value of the same expression on the same stored inputs, and no result depends on how the compiler
@@ -16,6 +17,7 @@
 // order depends on the graph's own atom count alone, so a graph has the same bits alone and anywhere in a batch.
 #include "xeq_common.h"
 #include "xeq_pbc_tables.h"
+#include "xeq_resident.h"
 
 namespace xeq {
 
@@ -84,13 +86,6 @@ __global__ void __launch_bounds__(256) k_md_normals(uint64_t seed, int purpose, 
 }
 
 // ------------------------------------------------------------------------------------------------------------- front
-struct MdBox {
-  double cell[9];   // rows: lattice vectors
-  double inv[9];    // frac_k = sum_j x_j inv[3 j + k]
-  int periodic[3];
-  int any;
-};
-
 template <typename T>
 struct MdFrontArgs {
   int64_t n, n_graphs;
@@ -107,29 +102,13 @@ struct MdFrontArgs {
   uint64_t seed;
   double dt, c1, noise2, dt_over_tau, t0;
   int32_t* image;
-  MdBox box;
+  ResBox box;
 };
-
-// Fractional coordinate by the inverse cell, floor, subtract along the periodic axes; twice, because the rounding of the wrapped coordinate
-// to T can land an atom that was a hair below a face exactly ON the opposite face.
-template <typename T>
-__device__ __forceinline__ void md_wrap(const MdBox& b, double x[3], int32_t img[3]) {
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int k = 0; k < 3; ++k) x[k] = (double)(T)x[k];
-    double s[3];
-    for (int k = 0; k < 3; ++k) {
-      const double fr = (x[0] * b.inv[k] + x[1] * b.inv[3 + k]) + x[2] * b.inv[6 + k];
-      s[k] = b.periodic[k] ? floor(fr) : 0.0;
-    }
-    for (int j = 0; j < 3; ++j) x[j] = x[j] - ((s[0] * b.cell[j] + s[1] * b.cell[3 + j]) + s[2] * b.cell[6 + j]);
-    for (int k = 0; k < 3; ++k) img[k] += (int32_t)s[k];
-  }
-}
 
 // One atom's front half against `box`.  SCALE (the barostat, k_npt_front): x <- mu x for EVERY atom, fixed ones included, between the
 // thermostat's scaling and the half kick.
 template <typename T, bool SCALE>
-__device__ __forceinline__ void md_front_atom(const MdFrontArgs<T>& a, int64_t i, const MdBox& box, double mu) {
+__device__ __forceinline__ void md_front_atom(const MdFrontArgs<T>& a, int64_t i, const ResBox& box, double mu) {
   const double im = (double)a.inv_mass[i];
   double v[3], x[3], f[3];
   for (int k = 0; k < 3; ++k) {
@@ -175,7 +154,7 @@ __device__ __forceinline__ void md_front_atom(const MdFrontArgs<T>& a, int64_t i
   }
   if (box.any) {
     int32_t img[3] = {a.image[3 * i], a.image[3 * i + 1], a.image[3 * i + 2]};
-    md_wrap<T>(box, x, img);
+    res_wrap<T>(box, x, img);
     for (int k = 0; k < 3; ++k) a.image[3 * i + k] = img[k];
   }
   for (int k = 0; k < 3; ++k) {
@@ -201,7 +180,7 @@ __global__ void __launch_bounds__(256) k_npt_front(MdFrontArgs<T> a, double* rec
   const bool moves = a.dt > 0.0;
   const double* c = rec + (moves ? XEQ_NPT_CELL_NEXT : XEQ_NPT_CELL);
   const double* m = rec + (moves ? XEQ_NPT_INV_NEXT : XEQ_NPT_INV);
-  MdBox box;
+  ResBox box;
   for (int k = 0; k < 9; ++k) {
     box.cell[k] = c[k];
     box.inv[k] = m[k];
@@ -241,7 +220,7 @@ struct MdBackArgs {
   int64_t* book;
   double half_dt;
   const int32_t* image;
-  MdBox box;
+  ResBox box;
   int64_t record_every, record_start, record_rows;
   T* traj_pos;
   T* traj_epot;
@@ -249,23 +228,10 @@ struct MdBackArgs {
   int64_t* traj_step;
 };
 
-// The trajectory row a step fills (-1: none): row (step - record_start) / record_every - 1 of the run's buffers, `step` counted behind it.
-__device__ __forceinline__ int64_t md_record_row_of(int64_t record_every, int64_t record_start, int64_t record_rows, int64_t step_after) {
-  if (record_every <= 0) return -1;
-  const int64_t d = step_after - record_start;
-  if (d <= 0 || d % record_every) return -1;
-  const int64_t row = d / record_every - 1;
-  return row < record_rows ? row : -1;
-}
-
+// The MD backs record with `advance` alone.
 template <typename T>
 __device__ __forceinline__ int64_t md_record_row(const MdBackArgs<T>& a, int64_t step_after) {
-  return a.advance ? md_record_row_of(a.record_every, a.record_start, a.record_rows, step_after) : -1;
-}
-
-__device__ __forceinline__ double md_wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
+  return a.advance ? res_record_row(a.record_every, a.record_start, a.record_rows, step_after) : -1;
 }
 
 // One workgroup joins every graph's chunk partials in chunk order.  A graph of at most MD_JOIN_SERIAL chunks is summed by one lane, chunk
@@ -312,7 +278,7 @@ struct MdKeSum {
     bad |= partial_bad[c];
   }
   __device__ __forceinline__ void wave() {
-    s = md_wave_sum(s);
+    s = res_wave_sum(s);
     for (int off = 32; off > 0; off >>= 1) bad |= __shfl_xor(bad, off, 64);   // (the one lane that stores carries every lane's flag)
   }
 };
@@ -338,26 +304,6 @@ struct MdNoBox {
   template <typename T>
   __device__ __forceinline__ void finish(const MdBackArgs<T>&, int64_t) const {}
 };
-
-__host__ __device__ __forceinline__ double md_det(const double* c) {
-  return c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-}
-
-// inv [9] with frac_k = sum_j x_j inv[3 j + k] by the adjugate; -> the determinant (inv is not written unless it is finite and not zero).
-__host__ __device__ __forceinline__ double md_inverse(const double* c, double* m) {
-  const double det = md_det(c);
-  if (!(det != 0.0) || !(det - det == 0.0)) return det;
-  m[0] = (c[4] * c[8] - c[5] * c[7]) / det;
-  m[1] = (c[2] * c[7] - c[1] * c[8]) / det;
-  m[2] = (c[1] * c[5] - c[2] * c[4]) / det;
-  m[3] = (c[5] * c[6] - c[3] * c[8]) / det;
-  m[4] = (c[0] * c[8] - c[2] * c[6]) / det;
-  m[5] = (c[2] * c[3] - c[0] * c[5]) / det;
-  m[6] = (c[3] * c[7] - c[4] * c[6]) / det;
-  m[7] = (c[1] * c[6] - c[0] * c[7]) / det;
-  m[8] = (c[0] * c[4] - c[1] * c[3]) / det;
-  return det;
-}
 
 // The Berendsen barostat (xeq_npt_back), run by the ONE lane that keeps the books, behind them: the pressure of the state this launch
 // leaves, the scale factor of the NEXT step and the cell it will have, into the f64 record.  All in double, in the order written.
@@ -483,17 +429,9 @@ __device__ __forceinline__ void md_back_chunk(const MdBackArgs<T>& a, const Box&
     }
     e = (double)a.half_mass[i] * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);   // of the STORED velocity: a function of the state alone
     const int64_t row = md_record_row(a, a.book[0] + 1);
-    if (row >= 0) {
-      const double* cell = bx.cell(a);
-      for (int j = 0; j < 3; ++j) {
-        double x = (double)a.pos[3 * i + j];
-        if (a.box.any)
-          x = x + (((double)a.image[3 * i] * cell[j] + (double)a.image[3 * i + 1] * cell[3 + j]) + (double)a.image[3 * i + 2] * cell[6 + j]);
-        a.traj_pos[(row * a.n + i) * 3 + j] = (T)x;
-      }
-    }
+    if (row >= 0) res_store_unwrapped(a.traj_pos, row, a.n, i, a.pos, a.image, a.box.any, bx.cell(a));
   }
-  e = md_wave_sum(e);
+  e = res_wave_sum(e);
   const int any_bad = __syncthreads_or(bad);
   if ((tid & 63) == 0) wsum[tid >> 6] = e;
   __syncthreads();
@@ -587,18 +525,13 @@ struct FireBackArgs {
   double fmax_tol, maxstep, dtmax, f_inc, f_dec, alpha_start, f_alpha;
   int n_min;
   const int32_t* image;
-  MdBox box;
+  ResBox box;
   int64_t record_every, record_start, record_rows;
   T* traj_pos;
   T* traj_epot;
   T* traj_fmax;
   int64_t* traj_step;
 };
-
-__device__ __forceinline__ double md_wave_max(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 struct FireSums {
   const double* partial;
@@ -613,10 +546,10 @@ struct FireSums {
     bad |= partial_bad[c];
   }
   __device__ __forceinline__ void wave() {
-    p = md_wave_sum(p);
-    ff = md_wave_sum(ff);
-    vv = md_wave_sum(vv);
-    m2 = md_wave_max(m2);
+    p = res_wave_sum(p);
+    ff = res_wave_sum(ff);
+    vv = res_wave_sum(vv);
+    m2 = res_wave_max(m2);
     for (int off = 32; off > 0; off >>= 1) bad |= __shfl_xor(bad, off, 64);
   }
 };
@@ -678,7 +611,7 @@ __device__ __forceinline__ void fire_decide(const FireBackArgs<T>& a, int64_t g,
 template <typename T>
 __device__ __forceinline__ void fire_join(const FireBackArgs<T>& a) {
   const int64_t eval = a.book[0];   // this evaluation's number: the first one is 0
-  const int64_t row = md_record_row_of(a.record_every, a.record_start, a.record_rows, eval);
+  const int64_t row = res_record_row(a.record_every, a.record_start, a.record_rows, eval);
   int bad = 0;
   md_join_graphs(
       a.n_graphs, a.n_chunks, a.graph_chunk_ptr, [&]() { return FireSums{a.partial, a.partial_bad, 0.0, 0.0, 0.0, 0.0, 0}; },
@@ -732,8 +665,8 @@ __global__ void __launch_bounds__(MD_CHUNK) k_fire_back(FireBackArgs<T> a) {
     p = (f[0] * v[0] + f[1] * v[1]) + f[2] * v[2];
     ff = (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2];
     vv = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-    const int64_t row = md_record_row_of(a.record_every, a.record_start, a.record_rows, a.book[0]);
-    if (row >= 0) {
+    const int64_t row = res_record_row(a.record_every, a.record_start, a.record_rows, a.book[0]);
+    if (row >= 0) {   // res_store_unwrapped, written out: through the helper this kernel takes 8 more SGPRs (profiles/resident_shared_refactor.txt)
       for (int j = 0; j < 3; ++j) {
         double x = (double)a.pos[3 * i + j];
         if (a.box.any)
@@ -743,10 +676,10 @@ __global__ void __launch_bounds__(MD_CHUNK) k_fire_back(FireBackArgs<T> a) {
       }
     }
   }
-  const double m2 = md_wave_max(ff);   // (a lane's ff IS its atom's |f|^2)
-  p = md_wave_sum(p);
-  ff = md_wave_sum(ff);
-  vv = md_wave_sum(vv);
+  const double m2 = res_wave_max(ff);   // (a lane's ff IS its atom's |f|^2)
+  p = res_wave_sum(p);
+  ff = res_wave_sum(ff);
+  vv = res_wave_sum(vv);
   const int any_bad = __syncthreads_or(bad);
   if ((tid & 63) == 0) {
     wsum[0][tid >> 6] = p;
@@ -779,7 +712,7 @@ struct FireFrontArgs {
   const int32_t* status;
   const double* coef;
   int32_t* image;
-  MdBox box;
+  ResBox box;
 };
 
 // Per free atom of a graph that is not converged: v = c_v v + c_f f, x += d v, the wrap.  Nothing else is written.
@@ -799,7 +732,7 @@ __global__ void __launch_bounds__(256) k_fire_front(FireFrontArgs<T> a) {
   }
   if (a.box.any) {
     int32_t img[3] = {a.image[3 * i], a.image[3 * i + 1], a.image[3 * i + 2]};
-    md_wrap<T>(a.box, x, img);
+    res_wrap<T>(a.box, x, img);
     for (int k = 0; k < 3; ++k) a.image[3 * i + k] = img[k];
   }
   for (int k = 0; k < 3; ++k) {
@@ -808,84 +741,10 @@ __global__ void __launch_bounds__(256) k_fire_front(FireFrontArgs<T> a) {
   }
 }
 
-// (host) finite: not NaN and not an infinity
-static inline bool md_finite(double x) { return x - x == 0.0; }
-
-static bool md_box(const double* cell, const int32_t* pbc, MdBox* b) {
-  b->any = 0;
-  for (int k = 0; k < 9; ++k) b->cell[k] = b->inv[k] = 0.0;
-  for (int k = 0; k < 3; ++k) b->periodic[k] = (cell && pbc && pbc[k]) ? 1 : 0;
-  if (!cell || !(b->periodic[0] || b->periodic[1] || b->periodic[2])) return true;
-  const double det = md_inverse(cell, b->inv);
-  if (!(det != 0.0) || !md_finite(det)) return false;
-  for (int k = 0; k < 9; ++k) b->cell[k] = cell[k];
-  b->any = 1;
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------------------- argument records
-// The checks the six front / back entries share (include/xeq.h: the records), each under the entry's own name `who`.
-#define RES_TRY(check)               \
-  do {                               \
-    if (int e_ = (check)) return e_; \
-  } while (0)
-
-static int res_dtype(const char* who, const xeq_res_system* s, bool records) {
-  XEQ_CHECK_ARG(s && records, "%s: null argument record", who);
-  XEQ_CHECK_ARG(s->dtype == XEQ_F32 || s->dtype == XEQ_F64, "%s: dtype %lld (0 f32, 1 f64)", who, (long long)s->dtype);
-  return XEQ_OK;
-}
-
-static const int64_t RES_MAX_ATOMS = ((int64_t)1 << 31) / 3;
-
-// A front's sizes.
-static int res_atoms_graphs(const char* who, const xeq_res_system* s) {
-  XEQ_CHECK_ARG(s->n >= 0 && s->n < RES_MAX_ATOMS && s->n_graphs >= 0, "%s: %lld atoms, %lld graphs", who, (long long)s->n, (long long)s->n_graphs);
-  return XEQ_OK;
-}
-
-static int res_chunks_hold(const char* who, const xeq_res_system* s) {
-  XEQ_CHECK_ARG(s->n_chunks <= s->n && s->n_chunks * XEQ_MD_CHUNK >= s->n, "%s: %lld chunks of at most %d atoms cannot hold %lld atoms", who,
-                (long long)s->n_chunks, XEQ_MD_CHUNK, (long long)s->n);
-  return XEQ_OK;
-}
-
-// A batch's back: its sizes (fewer than `chunk_cap` chunks), then the chunk count against the atom count.
-static int res_back_sizes(const char* who, const xeq_res_system* s, int64_t chunk_cap) {
-  XEQ_CHECK_ARG(s->n >= 0 && s->n < RES_MAX_ATOMS && s->n_graphs >= 0 && s->n_chunks >= 0 && s->n_chunks < chunk_cap,
-                "%s: %lld atoms, %lld graphs, %lld chunks", who, (long long)s->n, (long long)s->n_graphs, (long long)s->n_chunks);
-  return res_chunks_hold(who, s);
-}
-
-static int res_recorder(const char* who, const xeq_res_recorder* r) {
-  XEQ_CHECK_ARG(r->every >= 0 && r->rows >= 0 && r->start >= 0, "%s: recorder (%lld, %lld, %lld)", who, (long long)r->every, (long long)r->start,
-                (long long)r->rows);
-  return XEQ_OK;
-}
-
-static int res_box(const char* who, const xeq_res_system* s, MdBox* box) {
-  XEQ_CHECK_ARG(md_box(s->cell, s->pbc, box), "%s: the cell is singular or not finite", who);
-  return XEQ_OK;
-}
-
-// The buffers every back reads or writes per atom and per chunk.
-static bool res_back_buffers(const xeq_res_system* s, const xeq_res_step* st, const xeq_res_chunks* c) {
-  return s->pos && s->vel && s->frc && st->frc_step && c->chunk_atom0 && c->chunk_n && c->partial && c->partial_bad;
-}
-
-// The rows of a batch's recorder that is on (xeq_md_back, xeq_fire_back).
-static int res_trajectory(const char* who, const xeq_res_system* s, const xeq_res_recorder* r, const MdBox& box) {
-  XEQ_CHECK_ARG((s->n == 0 || r->traj_pos) && (s->n_graphs == 0 || (r->traj_epot && r->traj_second)) && r->traj_step, "%s: null trajectory buffer", who);
-  XEQ_CHECK_ARG(s->n == 0 || !box.any || s->image, "%s: a periodic system's recorder needs the image counts", who);
-  return XEQ_OK;
-}
-
-static const xeq_res_recorder RES_NO_RECORDER = {};
-
 // The kernel arguments of xeq_md_back and xeq_npt_back from the records; `on`: the recorder records in this call.
 template <typename T>
 static MdBackArgs<T> md_back_args(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
-                                  const xeq_res_recorder* rec, int64_t n_graphs, int advance, const MdBox& box, bool on) {
+                                  const xeq_res_recorder* rec, int64_t n_graphs, int advance, const ResBox& box, bool on) {
   return MdBackArgs<T>{sys->n, n_graphs, sys->n_chunks, advance ? 1 : 0, (const T*)sys->pos, (T*)sys->vel, (T*)sys->frc, (const T*)step->frc_step,
                        (const T*)step->energy_step, step->n_edges_step, (const T*)md->inv_mass, (const T*)md->half_mass, chunks->chunk_atom0,
                        chunks->chunk_n, chunks->graph_chunk_ptr, chunks->partial, chunks->partial_bad, (T*)md->ke, (T*)md->epot, sys->book, md->half_dt,
@@ -901,9 +760,9 @@ extern "C" {
 
 int xeq_md_inverse_cell(const double* cell, double* inv) {
   XEQ_CHECK_ARG(cell && inv, "xeq_md_inverse_cell: null pointer");
-  MdBox b;
+  ResBox b;
   const int32_t all[3] = {1, 1, 1};
-  XEQ_CHECK_ARG(md_box(cell, all, &b), "xeq_md_inverse_cell: the cell is singular or not finite");
+  XEQ_CHECK_ARG(res_box_of(cell, all, &b), "xeq_md_inverse_cell: the cell is singular or not finite");
   for (int k = 0; k < 9; ++k) inv[k] = b.inv[k];
   return XEQ_OK;
 }
@@ -935,6 +794,7 @@ int64_t xeq_record_bytes(int which) {
     case XEQ_REC_NPT: return sizeof(xeq_npt_params);
     case XEQ_REC_FIRE: return sizeof(xeq_fire_params);
     case XEQ_REC_NEIGHBORS: return sizeof(xeq_neighbor_search);
+    case XEQ_REC_LBFGS: return sizeof(xeq_lbfgs_params);
   }
   return -1;
 }
@@ -947,14 +807,14 @@ int xeq_md_front(const xeq_res_system* sys, const xeq_md_params* md, double dt, 
   int ensemble = (int)md->ensemble;
   const int64_t n = sys->n, n_graphs = sys->n_graphs;
   RES_TRY(res_atoms_graphs(who, sys));
-  XEQ_CHECK_ARG(md_finite(dt) && dt >= 0.0, "xeq_md_front: time step %g", dt);
-  XEQ_CHECK_ARG(ensemble != XEQ_MD_LANGEVIN || (md->c1 >= 0.0 && md->c1 <= 1.0 && md_finite(md->noise2) && md->noise2 >= 0.0),
+  XEQ_CHECK_ARG(res_finite(dt) && dt >= 0.0, "xeq_md_front: time step %g", dt);
+  XEQ_CHECK_ARG(ensemble != XEQ_MD_LANGEVIN || (md->c1 >= 0.0 && md->c1 <= 1.0 && res_finite(md->noise2) && md->noise2 >= 0.0),
                 "xeq_md_front: langevin needs 0 <= c1 <= 1 and a finite noise2 >= 0 (got %g, %g)", md->c1, md->noise2);
   XEQ_CHECK_ARG(ensemble != XEQ_MD_BERENDSEN ||
-                    (md_finite(md->dt_over_tau) && md->dt_over_tau >= 0.0 && md_finite(md->t0) && md->t0 >= 0.0 && n_graphs >= 1),
+                    (res_finite(md->dt_over_tau) && md->dt_over_tau >= 0.0 && res_finite(md->t0) && md->t0 >= 0.0 && n_graphs >= 1),
                 "xeq_md_front: berendsen needs dt / tau >= 0, a target temperature >= 0 and a graph (got %g, %g, %lld)", md->dt_over_tau, md->t0,
                 (long long)n_graphs);
-  MdBox box;
+  ResBox box;
   RES_TRY(res_box(who, sys, &box));
   XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->vel && sys->frc && md->inv_mass), "xeq_md_front: null state buffer");
   XEQ_CHECK_ARG(n == 0 || !box.any || sys->image, "xeq_md_front: a periodic system needs the image counts");
@@ -978,12 +838,12 @@ int xeq_md_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_r
   if (!rec) rec = &RES_NO_RECORDER;
   const int64_t n = sys->n, n_graphs = sys->n_graphs, n_chunks = sys->n_chunks;
   RES_TRY(res_back_sizes(who, sys, (int64_t)1 << 31));
-  XEQ_CHECK_ARG(md_finite(md->half_dt) && md->half_dt >= 0.0, "xeq_md_back: half time step %g", md->half_dt);
+  XEQ_CHECK_ARG(res_finite(md->half_dt) && md->half_dt >= 0.0, "xeq_md_back: half time step %g", md->half_dt);
   RES_TRY(res_recorder(who, rec));
-  MdBox box;
+  ResBox box;
   RES_TRY(res_box(who, sys, &box));
   XEQ_CHECK_ARG(sys->book && step->n_edges_step, "xeq_md_back: null step counter or edge count");
-  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks) && md->inv_mass && md->half_mass), "xeq_md_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks, true) && md->inv_mass && md->half_mass), "xeq_md_back: null per-atom or per-chunk buffer");
   XEQ_CHECK_ARG(n_graphs == 0 || (step->energy_step && chunks->graph_chunk_ptr && md->ke && md->epot), "xeq_md_back: null per-graph buffer");
   const bool on = advance && rec->every > 0 && rec->rows > 0;
   if (on) RES_TRY(res_trajectory(who, sys, rec, box));
@@ -1003,7 +863,7 @@ int xeq_pbc_tables_device(int dtype, const void* cell, const int32_t reps[3], co
                           int32_t* reps_needed, void* stream) {
   XEQ_CHECK_ARG(dtype == XEQ_F32 || dtype == XEQ_F64, "xeq_pbc_tables_device: dtype %d (0 f32, 1 f64)", dtype);
   XEQ_CHECK_ARG(cell && out && reps && pbc, "xeq_pbc_tables_device: null pointer");
-  XEQ_CHECK_ARG(md_finite(cutoff) && cutoff > 0.0, "xeq_pbc_tables_device: cutoff %g", cutoff);
+  XEQ_CHECK_ARG(res_finite(cutoff) && cutoff > 0.0, "xeq_pbc_tables_device: cutoff %g", cutoff);
   XEQ_CHECK_ARG(reps[0] >= 0 && reps[1] >= 0 && reps[2] >= 0 && reps[0] <= 64 && reps[1] <= 64 && reps[2] <= 64,
                 "xeq_pbc_tables_device: %d x %d x %d images per axis (0 .. 64 each)", reps[0], reps[1], reps[2]);
   const int64_t nc = (int64_t)(2 * reps[0] + 1) * (2 * reps[1] + 1) * (2 * reps[2] + 1);
@@ -1026,8 +886,8 @@ int xeq_npt_front(const xeq_res_system* sys, const xeq_md_params* md, const xeq_
   RES_TRY(res_dtype(who, sys, md && npt));
   const int64_t n = sys->n;
   XEQ_CHECK_ARG(n >= 0 && n < RES_MAX_ATOMS, "xeq_npt_front: %lld atoms", (long long)n);
-  XEQ_CHECK_ARG(md_finite(dt) && dt >= 0.0, "xeq_npt_front: time step %g", dt);
-  XEQ_CHECK_ARG(md_finite(md->dt_over_tau) && md->dt_over_tau >= 0.0 && md_finite(md->t0) && md->t0 >= 0.0,
+  XEQ_CHECK_ARG(res_finite(dt) && dt >= 0.0, "xeq_npt_front: time step %g", dt);
+  XEQ_CHECK_ARG(res_finite(md->dt_over_tau) && md->dt_over_tau >= 0.0 && res_finite(md->t0) && md->t0 >= 0.0,
                 "xeq_npt_front: berendsen needs dt / tau >= 0 and a target temperature >= 0 (got %g, %g)", md->dt_over_tau, md->t0);
   XEQ_CHECK_ARG(npt->box && npt->step_cell, "xeq_npt_front: null box record or cell");
   XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->vel && sys->frc && md->inv_mass && sys->image), "xeq_npt_front: null state buffer");
@@ -1035,7 +895,7 @@ int xeq_npt_front(const xeq_res_system* sys, const xeq_md_params* md, const xeq_
   if (n == 0) return XEQ_OK;
   XEQ_DISPATCH_FLOAT(sys->dtype, {
     MdFrontArgs<T> a{n, 1, dt == 0.0 ? XEQ_MD_NVE : XEQ_MD_BERENDSEN, (T*)sys->pos, (T*)sys->vel, (const T*)sys->frc, (const T*)md->inv_mass, sys->batch,
-                     (const T*)md->ke, (const T*)md->tfac, nullptr, nullptr, 0, dt, 1.0, 0.0, md->dt_over_tau, md->t0, sys->image, MdBox{}};
+                     (const T*)md->ke, (const T*)md->tfac, nullptr, nullptr, 0, dt, 1.0, 0.0, md->dt_over_tau, md->t0, sys->image, ResBox{}};
     hipLaunchKernelGGL(k_npt_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, npt->box, (T*)npt->step_cell);
   });
   XEQ_CHECK_LAUNCH("xeq_npt_front");
@@ -1051,20 +911,20 @@ int xeq_npt_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_
   XEQ_CHECK_ARG(n >= 1 && n < RES_MAX_ATOMS && n_chunks >= 1 && n_chunks < ((int64_t)1 << 31), "xeq_npt_back: %lld atoms, %lld chunks", (long long)n,
                 (long long)n_chunks);
   RES_TRY(res_chunks_hold(who, sys));
-  XEQ_CHECK_ARG(md_finite(md->half_dt) && md->half_dt >= 0.0, "xeq_npt_back: half time step %g", md->half_dt);
-  XEQ_CHECK_ARG(md_finite(npt->kappa) && npt->kappa >= 0.0 && md_finite(npt->p0) && md_finite(npt->p_unit),
+  XEQ_CHECK_ARG(res_finite(md->half_dt) && md->half_dt >= 0.0, "xeq_npt_back: half time step %g", md->half_dt);
+  XEQ_CHECK_ARG(res_finite(npt->kappa) && npt->kappa >= 0.0 && res_finite(npt->p0) && res_finite(npt->p_unit),
                 "xeq_npt_back: barostat (dt / taup * beta / 3 = %g >= 0, target pressure %g, pressure unit %g)", npt->kappa, npt->p0, npt->p_unit);
   RES_TRY(res_recorder(who, rec));
   XEQ_CHECK_ARG(sys->book && step->n_edges_step && npt->box && step->virial_step && npt->virial,
                 "xeq_npt_back: null step counter, edge count, box record or virial");
   XEQ_CHECK_ARG(!step->reps_needed || npt->reps_seen, "xeq_npt_back: image counts of the step without the captured counts or the running maximum");
-  XEQ_CHECK_ARG(res_back_buffers(sys, step, chunks) && md->inv_mass && md->half_mass, "xeq_npt_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(res_back_buffers(sys, step, chunks, true) && md->inv_mass && md->half_mass, "xeq_npt_back: null per-atom or per-chunk buffer");
   XEQ_CHECK_ARG(step->energy_step && chunks->graph_chunk_ptr && md->ke && md->epot, "xeq_npt_back: null per-graph buffer");
   const bool on = advance && rec->every > 0 && rec->rows > 0;
   XEQ_CHECK_ARG(!on || (rec->traj_pos && rec->traj_epot && rec->traj_second && rec->traj_step && rec->traj_cell && rec->traj_pressure && sys->image),
                 "xeq_npt_back: null trajectory buffer");
   XEQ_DISPATCH_FLOAT(sys->dtype, {
-    MdBox any{};
+    ResBox any{};
     any.any = any.periodic[0] = any.periodic[1] = any.periodic[2] = 1;   // (the recorder's cell is the record's: NptBox::cell)
     const MdBackArgs<T> a = md_back_args<T>(sys, step, chunks, md, rec, 1, advance, any, on);
     NptBox<T> bx{(const T*)step->virial_step, (T*)npt->virial, npt->box, step->reps_needed, npt->reps_seen,
@@ -1083,8 +943,8 @@ int xeq_fire_front(const xeq_res_system* sys, const xeq_fire_params* fire, void*
   RES_TRY(res_dtype(who, sys, fire));
   const int64_t n = sys->n, n_graphs = sys->n_graphs;
   RES_TRY(res_atoms_graphs(who, sys));
-  XEQ_CHECK_ARG(n == 0 || n_graphs >= 1, "xeq_fire_front: %lld atoms in no graph", (long long)n);
-  MdBox box;
+  RES_TRY(res_in_graph(who, sys));
+  ResBox box;
   RES_TRY(res_box(who, sys, &box));
   XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->vel && sys->frc && sys->batch && fire->status && fire->coef), "xeq_fire_front: null state buffer");
   XEQ_CHECK_ARG(n == 0 || !box.any || sys->image, "xeq_fire_front: a periodic system needs the image counts");
@@ -1105,19 +965,19 @@ int xeq_fire_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq
   const int64_t n = sys->n, n_graphs = sys->n_graphs, n_chunks = sys->n_chunks;
   const xeq_fire_params& f = *fire;
   RES_TRY(res_back_sizes(who, sys, (int64_t)1 << 29));
-  XEQ_CHECK_ARG(n == 0 || n_graphs >= 1, "xeq_fire_back: %lld atoms in no graph", (long long)n);
-  XEQ_CHECK_ARG(f.fmax_tol > 0.0 && md_finite(f.fmax_tol), "xeq_fire_back: fmax %g", f.fmax_tol);
-  XEQ_CHECK_ARG(f.maxstep > 0.0 && f.dtmax > 0.0 && md_finite(f.maxstep) && md_finite(f.dtmax), "xeq_fire_back: maxstep %g, dtmax %g", f.maxstep,
+  RES_TRY(res_in_graph(who, sys));
+  XEQ_CHECK_ARG(f.fmax_tol > 0.0 && res_finite(f.fmax_tol), "xeq_fire_back: fmax %g", f.fmax_tol);
+  XEQ_CHECK_ARG(f.maxstep > 0.0 && f.dtmax > 0.0 && res_finite(f.maxstep) && res_finite(f.dtmax), "xeq_fire_back: maxstep %g, dtmax %g", f.maxstep,
                 f.dtmax);
-  XEQ_CHECK_ARG(f.f_inc >= 1.0 && md_finite(f.f_inc) && f.f_dec > 0.0 && f.f_dec < 1.0 && f.alpha_start >= 0.0 && f.alpha_start <= 1.0 &&
+  XEQ_CHECK_ARG(f.f_inc >= 1.0 && res_finite(f.f_inc) && f.f_dec > 0.0 && f.f_dec < 1.0 && f.alpha_start >= 0.0 && f.alpha_start <= 1.0 &&
                     f.f_alpha > 0.0 && f.f_alpha <= 1.0 && f.n_min >= 0 && f.n_min < ((int64_t)1 << 31),
                 "xeq_fire_back: mixing parameters (f_inc %g, f_dec %g, alpha_start %g, f_alpha %g, n_min %lld)", f.f_inc, f.f_dec, f.alpha_start,
                 f.f_alpha, (long long)f.n_min);
   RES_TRY(res_recorder(who, rec));
-  MdBox box;
+  ResBox box;
   RES_TRY(res_box(who, sys, &box));
   XEQ_CHECK_ARG(sys->book && step->n_edges_step, "xeq_fire_back: null evaluation counter or edge count");
-  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks) && sys->batch), "xeq_fire_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks, true) && sys->batch), "xeq_fire_back: null per-atom or per-chunk buffer");
   XEQ_CHECK_ARG(n_graphs == 0 || (step->energy_step && chunks->graph_chunk_ptr && f.epot && f.fmax && f.dt && f.alpha && f.n_pos && f.status &&
                                   f.converged_at && f.coef),
                 "xeq_fire_back: null per-graph buffer");

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("XEQ_LIB_PATH") or os.path.join(_HERE, "libxeq_hip.so"
 
 XEQ_F32, XEQ_F64 = 0, 1
 COPY_MANY_MAX = 16       # XEQ_COPY_MANY_MAX of include/xeq.h
-# (tests/test_resident_records_host.py holds the next four lines against the header)
+# (tests/test_resident_records_host.py holds the next five lines against the header)
 MD_CHUNK = 256          # XEQ_MD_CHUNK of include/xeq.h: atoms per kinetic-energy chunk (md.py, optimize.py)
 MD_NVE, MD_LANGEVIN, MD_BERENDSEN, MD_PURPOSE_LANGEVIN, MD_PURPOSE_MAXWELL = 0, 1, 2, 0, 1      # XEQ_MD_* of include/xeq.h (md.py)
 NPT_BOX, NPT_CELL, NPT_INV, NPT_CELL_NEXT, NPT_INV_NEXT, NPT_MU, NPT_P, NPT_V = 40, 0, 9, 18, 27, 36, 37, 38      # XEQ_NPT_* of include/xeq.h (md.py)
@@ -61,7 +61,9 @@ FireParams = _record("xeq_fire_params", (_P, "fixed epot fmax dt alpha n_pos sta
 NeighborSearch = _record("xeq_neighbor_search", (c_int64, "dtype kind n_graphs n_nodes n_cells"), (c_double, "cutoff"), (c_int64 * 3, "reps"),
                          (_P, "pos ptr img cells shift recip thr lo inv_w nbins bin_base bin_start bin_atom"))
 NEIGHBORS_OPEN_SWEEP, NEIGHBORS_OPEN_BINS, NEIGHBORS_PBC_ALL, NEIGHBORS_PBC_PRUNED, NEIGHBORS_PBC_BINS = range(5)
-RECORDS = [ResSystem, ResStep, ResChunks, ResRecorder, MdParams, NptParams, FireParams, NeighborSearch]
+LbfgsParams = _record("xeq_lbfgs_params", (_P, "fixed hist_s hist_y pending_s gram delta count head status dropped converged_at epot fmax ticket"),
+                      (c_int64, "memory max_graph_chunks"), (c_double, "fmax_tol alpha maxstep damping"))
+RECORDS = [ResSystem, ResStep, ResChunks, ResRecorder, MdParams, NptParams, FireParams, NeighborSearch, LbfgsParams]
 _R = ctypes.POINTER
 
 
@@ -274,9 +276,8 @@ _PROTOS = {
     "xeq_npt_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(MdParams), _R(NptParams), _R(ResRecorder), c_int, _P],
     "xeq_fire_front": [_R(ResSystem), _R(FireParams), _P],
     "xeq_fire_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(FireParams), _R(ResRecorder), _P],
-    "xeq_lbfgs_front": [_R(ResSystem), _R(ResChunks), _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_double, c_double, _P],
-    "xeq_lbfgs_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(ResRecorder), _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                       _P, _P, c_double, c_double, _P],
+    "xeq_lbfgs_front": [_R(ResSystem), _R(ResChunks), _R(LbfgsParams), _P],
+    "xeq_lbfgs_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(LbfgsParams), _R(ResRecorder), _P],
     "xeq_vib_project": [c_int, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "xeq_vib_eigh": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],
     "xeq_vib_eigh_large": [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P],

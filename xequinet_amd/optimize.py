@@ -38,11 +38,46 @@ def time_step_factor(energy_unit: str, length_unit: str) -> float:
 
 
 class _Minimiser(ResidentDriver):
-    """What the two minimisers share beyond ResidentDriver: the run loop over windows, the lazy evaluation 0 and the read-only surface.
-    A subclass sets ``_CONVERGED`` (its status value of a converged graph), ``status``, ``_converged_at``, ``frc``, ``epot``, ``fmax``,
-    ``_active_host`` and defines ``reset()``."""
+    """What the two minimisers share beyond ResidentDriver: the set-up of the system and of the state both keep, the run loop over
+    windows, the lazy evaluation 0 and the read-only surface.  A subclass sets ``_CONVERGED`` (its status value of a converged graph),
+    validates its own parameters, calls ``_init_minimiser``, allocates its own state (``vel``, ``_partial``, ``_partial_bad`` among it),
+    calls ``_load_system``, fills its record and defines ``reset()``."""
 
     _CONVERGED = None
+
+    def _init_minimiser(self, model, pos: torch.Tensor, atomic_numbers: torch.Tensor, ptr, cell, fixed, edge_capacity, energy_unit, length_unit,
+                        fresh: int) -> None:
+        """The shape checks, ``_init_system``, the units and the state every minimiser has, every graph at status ``fresh``."""
+        who = type(self).__name__
+        N = int(pos.shape[0])
+        if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,):
+            raise ValueError(f"{who}: pos [N, 3] and atomic_numbers [N] are needed")
+        if fixed is not None and fixed.shape != (N,):
+            raise ValueError(f"{who}: fixed {tuple(fixed.shape)}, [N] = [{N}] is needed")
+        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, ptr, cell, fixed))
+        dev, dt_, G = self.device, self.dtype, self.n_graphs
+        u = _units.get_default_units()
+        self.energy_unit = energy_unit or u.get(keys.TOTAL_ENERGY, "eV")
+        self.length_unit = length_unit or u.get(keys.POSITIONS, "Angstrom")
+        self.fixed = None if fixed is None else fixed.detach().to(torch.bool).contiguous().clone()
+        self.frc = torch.zeros((N, 3), dtype=dt_, device=dev)          # f of the latest evaluation
+        self.image = torch.zeros((N, 3), dtype=torch.int32, device=dev)
+        self.epot = torch.zeros(G, dtype=dt_, device=dev)
+        self.fmax = torch.zeros(G, dtype=dt_, device=dev)
+        self.status = torch.full((G,), fresh, dtype=torch.int32, device=dev)
+        self._converged_at = torch.full((G,), -1, dtype=torch.int64, device=dev)
+        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # evaluations done, largest n_edges, non-finite flag, graphs not converged
+        self._ck = None
+        self._steps_host = 0           # evaluations done
+        self._active_host = G
+        self._fresh = False            # frc / epot / fmax and the driver's coefficients belong to the current positions
+
+    def _reset_common(self, fresh: int) -> None:
+        """The tail of every ``reset()``: every graph at status ``fresh``, the evaluation count starts over."""
+        self.status.fill_(fresh)
+        self._converged_at.fill_(-1)
+        self.book.zero_()
+        self._steps_host, self._active_host, self._fresh = 0, self.n_graphs, False
 
     def _bad_message(self, first: int, n: int) -> str:
         return (f"{type(self).__name__}: non-finite force or energy in evaluations {first} .. {first + n}; the state is that "
@@ -124,42 +159,20 @@ class FIRE(_Minimiser):
             raise ValueError(f"FIRE: f_inc {f_inc} (>= 1)")
         if not (0.0 <= float(alpha_start) <= 1.0 and 0.0 < float(f_alpha) <= 1.0 and int(n_min) >= 0):
             raise ValueError(f"FIRE: alpha_start {alpha_start} (in [0, 1]), f_alpha {f_alpha} (in (0, 1]), n_min {n_min} (>= 0)")
-        N = int(pos.shape[0])
-        if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,):
-            raise ValueError("FIRE: pos [N, 3] and atomic_numbers [N] are needed")
-        if fixed is not None and fixed.shape != (N,):
-            raise ValueError(f"FIRE: fixed {tuple(fixed.shape)}, [N] = [{N}] is needed")
-        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, ptr, cell, fixed))
-        dev, dt_ = self.device, self.dtype
-
-        u = _units.get_default_units()
-        self.energy_unit = energy_unit or u.get(keys.TOTAL_ENERGY, "eV")
-        self.length_unit = length_unit or u.get(keys.POSITIONS, "Angstrom")
+        self._init_minimiser(model, pos, atomic_numbers, ptr, cell, fixed, edge_capacity, energy_unit, length_unit, lib.FIRE_FRESH)
+        N, G, C, dev = self.n_atoms, self.n_graphs, max(self.n_chunks, 1), self.device
         scale = time_step_factor(self.energy_unit, self.length_unit)
         self.fmax_tol, self.maxstep = float(fmax), float(maxstep)
         self.dt0, self.dtmax = float(dt) * scale, float(dtmax) * scale
         self.n_min, self.f_inc, self.f_dec, self.alpha_start, self.f_alpha = int(n_min), float(f_inc), float(f_dec), float(alpha_start), float(f_alpha)
 
-        G, C = self.n_graphs, max(self.n_chunks, 1)
-        self.fixed = None if fixed is None else fixed.detach().to(torch.bool).contiguous().clone()
         self._partial = torch.zeros((C, 4), dtype=torch.float64, device=dev)
         self._partial_bad = torch.zeros(C, dtype=torch.int32, device=dev)
-        self.vel = torch.zeros((N, 3), dtype=dt_, device=dev)
-        self.frc = torch.zeros((N, 3), dtype=dt_, device=dev)
-        self.image = torch.zeros((N, 3), dtype=torch.int32, device=dev)
-        self.epot = torch.zeros(G, dtype=dt_, device=dev)
-        self.fmax = torch.zeros(G, dtype=dt_, device=dev)
+        self.vel = torch.zeros((N, 3), dtype=self.dtype, device=dev)
         self.dt = torch.full((G,), self.dt0, dtype=torch.float64, device=dev)
         self.alpha = torch.full((G,), self.alpha_start, dtype=torch.float64, device=dev)
         self.n_pos = torch.zeros(G, dtype=torch.int32, device=dev)
-        self.status = torch.full((G,), lib.FIRE_FRESH, dtype=torch.int32, device=dev)
-        self._converged_at = torch.full((G,), -1, dtype=torch.int64, device=dev)
         self.coef = torch.zeros((G, 3), dtype=torch.float64, device=dev)
-        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # evaluations done, largest n_edges, non-finite flag, graphs not converged
-        self._ck = None
-        self._steps_host = 0           # evaluations done
-        self._active_host = G
-        self._fresh = False            # frc / epot / fmax / coef belong to the current positions
         self._front_name, self._back_name = "xeq_fire_front", "xeq_fire_back"
 
         self._load_system(pos, atomic_numbers, cell, pbc)
@@ -187,11 +200,8 @@ class FIRE(_Minimiser):
         self.dt.fill_(self.dt0)
         self.alpha.fill_(self.alpha_start)
         self.n_pos.zero_()
-        self.status.fill_(lib.FIRE_FRESH)
-        self._converged_at.fill_(-1)
         self.coef.zero_()
-        self.book.zero_()
-        self._steps_host, self._active_host, self._fresh = 0, self.n_graphs, False
+        self._reset_common(lib.FIRE_FRESH)
 
     @property
     def time_steps(self) -> torch.Tensor:
@@ -225,30 +235,17 @@ class LBFGS(_Minimiser):
                 raise ValueError(f"LBFGS: {name} {v} (> 0 is needed)")
         if int(memory) != memory or not 1 <= int(memory) <= lib.LBFGS_MAX_MEMORY:
             raise ValueError(f"LBFGS: memory {memory} (1 .. {lib.LBFGS_MAX_MEMORY})")
-        N = int(pos.shape[0])
-        if pos.dim() != 2 or pos.shape[1] != 3 or atomic_numbers.shape != (N,):
-            raise ValueError("LBFGS: pos [N, 3] and atomic_numbers [N] are needed")
-        if fixed is not None and fixed.shape != (N,):
-            raise ValueError(f"LBFGS: fixed {tuple(fixed.shape)}, [N] = [{N}] is needed")
-        self._init_system(model, N, ptr, cell, edge_capacity, (pos, atomic_numbers, ptr, cell, fixed))
-        dev, dt_ = self.device, self.dtype
-
-        u = _units.get_default_units()
-        self.energy_unit = energy_unit or u.get(keys.TOTAL_ENERGY, "eV")
-        self.length_unit = length_unit or u.get(keys.POSITIONS, "Angstrom")
-        self.fmax_tol, self.maxstep, self.damping, self.memory = float(fmax), float(maxstep), float(damping), int(memory)
+        self._init_minimiser(model, pos, atomic_numbers, ptr, cell, fixed, edge_capacity, energy_unit, length_unit, lib.LBFGS_FRESH)
+        N, G, C, M, dev = self.n_atoms, self.n_graphs, max(self.n_chunks, 1), int(memory), self.device
+        self.fmax_tol, self.maxstep, self.damping, self.memory = float(fmax), float(maxstep), float(damping), M
         self.alpha = float(alpha) * curvature_factor(self.energy_unit, self.length_unit)
 
-        G, C, M = self.n_graphs, max(self.n_chunks, 1), self.memory
         K = 2 * M + 1
         self._max_graph_chunks = int(np.diff(self._graph_chunk_ptr.cpu().numpy()).max()) if G else 0
-        self.fixed = None if fixed is None else fixed.detach().to(torch.bool).contiguous().clone()
         f64 = dict(dtype=torch.float64, device=dev)
         self._partial = torch.zeros((C, 3 * (2 * M + 3) + 1), **f64)
         self._partial_bad = torch.zeros((C, 4), dtype=torch.int32, device=dev)
-        self.vel = None                # (no velocities: the record's member stays NULL)
-        self.frc = torch.zeros((N, 3), dtype=dt_, device=dev)          # f of the latest evaluation = f_prev of the next back
-        self.image = torch.zeros((N, 3), dtype=torch.int32, device=dev)
+        self.vel = None                # (no velocities: the record's member stays NULL; frc is f_prev of the next back)
         self.hist_s = torch.zeros((M, N, 3), **f64)
         self.hist_y = torch.zeros((M, N, 3), **f64)
         self.pending_s = torch.zeros((N, 3), **f64)
@@ -256,37 +253,27 @@ class LBFGS(_Minimiser):
         self.delta = torch.zeros((G, K), **f64)
         self.count = torch.zeros(G, dtype=torch.int32, device=dev)
         self.head = torch.zeros(G, dtype=torch.int32, device=dev)
-        self.status = torch.full((G,), lib.LBFGS_FRESH, dtype=torch.int32, device=dev)
         self.dropped = torch.zeros(G, dtype=torch.int32, device=dev)
-        self._converged_at = torch.full((G,), -1, dtype=torch.int64, device=dev)
-        self.epot = torch.zeros(G, dtype=dt_, device=dev)
-        self.fmax = torch.zeros(G, dtype=dt_, device=dev)
-        self.book = torch.zeros(4, dtype=torch.int64, device=dev)     # evaluations done, largest n_edges, non-finite flag, graphs not converged
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._ck = None
-        self._steps_host = 0           # evaluations done
-        self._active_host = G
-        self._fresh = False            # frc / epot / fmax / delta belong to the current positions
         self._front_name, self._back_name = "xeq_lbfgs_front", "xeq_lbfgs_back"
 
         self._load_system(pos, atomic_numbers, cell, pbc)
+        members = dict(fixed=self.fixed, hist_s=self.hist_s, hist_y=self.hist_y, pending_s=self.pending_s, gram=self.gram, delta=self.delta,
+                       count=self.count, head=self.head, status=self.status, dropped=self.dropped, converged_at=self._converged_at, epot=self.epot,
+                       fmax=self.fmax, ticket=self._ticket, memory=self.memory, max_graph_chunks=self._max_graph_chunks, fmax_tol=self.fmax_tol,
+                       alpha=self.alpha, maxstep=self.maxstep, damping=self.damping)
+        self._lbfgs = lib.fill(lib.LbfgsParams(), **members)
         if self._any_pbc:              # the wrap alone (every coefficient and force is zero): the search sweeps images around the box
             every = torch.full((G,), lib.LBFGS_ACTIVE, dtype=torch.int32, device=dev)
-            call("xeq_lbfgs_front", *self._front_args(status=every), lib.stream())
+            call("xeq_lbfgs_front", ctypes.byref(self._sys), ctypes.byref(self._chunks),
+                 ctypes.byref(lib.fill(lib.LbfgsParams(), **dict(members, status=every))), lib.stream())
 
     # ------------------------------------------------------------------------------------------------ launches
-    def _front_args(self, status=None):
-        p = lib.ptr
-        return (ctypes.byref(self._sys), ctypes.byref(self._chunks), p(self.fixed), self.memory, self._max_graph_chunks, p(self.hist_s),
-                p(self.hist_y), p(self.pending_s), p(self.delta), p(self.count), p(self.status if status is None else status), self.maxstep,
-                self.damping)
+    def _front_args(self):
+        return (ctypes.byref(self._sys), ctypes.byref(self._chunks), ctypes.byref(self._lbfgs))
 
     def _back_args(self, advance: bool):
-        p = lib.ptr
-        return (ctypes.byref(self._sys), ctypes.byref(self._step_record()), ctypes.byref(self._chunks), ctypes.byref(self._rec), p(self.fixed),
-                self.memory, self._max_graph_chunks, p(self.hist_s), p(self.hist_y), p(self.pending_s), p(self.gram), p(self.delta),
-                p(self.count), p(self.head), p(self.status), p(self.dropped), p(self._converged_at), p(self.epot), p(self.fmax),
-                p(self._ticket), self.fmax_tol, self.alpha)
+        return (ctypes.byref(self._sys), ctypes.byref(self._step_record()), ctypes.byref(self._chunks), ctypes.byref(self._lbfgs), ctypes.byref(self._rec))
 
     # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
     def _state(self):
@@ -295,11 +282,9 @@ class LBFGS(_Minimiser):
 
     def reset(self) -> None:
         """Every graph fresh again with an empty history, from the current positions; the evaluation count starts over."""
-        for t in (self.hist_s, self.hist_y, self.pending_s, self.gram, self.delta, self.count, self.head, self.dropped, self.book):
+        for t in (self.hist_s, self.hist_y, self.pending_s, self.gram, self.delta, self.count, self.head, self.dropped):
             t.zero_()
-        self.status.fill_(lib.LBFGS_FRESH)
-        self._converged_at.fill_(-1)
-        self._steps_host, self._active_host, self._fresh = 0, self.n_graphs, False
+        self._reset_common(lib.LBFGS_FRESH)
 
     @property
     def history_length(self) -> torch.Tensor:
