@@ -984,7 +984,7 @@ int xeq_ewald_layernorm_bwd(const void* g, const void* x, const void* stats, con
 int xeq_ewald_combine(const void* a, double sa, const void* b, double sb, const void* pre, int64_t count, void* out, void* stream);
 
 /* Device-resident drivers around a whole-step graph (xequinet_amd/resident.py, csrc/xeq_md.hip): molecular dynamics (md.py, DESIGN.md
- * sections 12 and 15) and batched FIRE and L-BFGS geometry optimisation (optimize.py, sections 13 and 16), f32 / f64.  One step is a FRONT entry, the step's
+ * sections 12, 15 and 17) and batched FIRE and L-BFGS geometry optimisation (optimize.py, sections 13 and 16), f32 / f64.  One step is a FRONT entry, the step's
  * graph on the step object's static buffers, a BACK entry; nothing reaches the host between them.
  *
  * The entries take their arguments as RECORDS, by pointer: what every driver has (the system, the step graph's outputs, the chunk
@@ -1133,6 +1133,66 @@ typedef struct xeq_npt_params {
 int xeq_npt_front(const xeq_res_system* sys, const xeq_md_params* md, const xeq_npt_params* npt, double dt, void* stream);
 int xeq_npt_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
                  const xeq_npt_params* npt, const xeq_res_recorder* rec, int advance, void* stream);
+
+/* Canonical thermostats: a Nose-Hoover chain per graph (Martyna, Tuckerman, Tobias, Klein, Mol. Phys. 87, 1117 (1996)) and stochastic
+ * velocity rescaling (Bussi, Donadio, Parrinello, J. Chem. Phys. 126, 014101 (2007)); DESIGN.md section 17.  Both are ONE factor s per
+ * graph and step, a function of the graph's kinetic energy, so they ride on the two halves above: xeq_nvt_front is xeq_md_front's nve
+ * step with the factor, xeq_nvt_back is xeq_md_back with the thermostat in its join.  The entries of xeq_md_params they read: inv_mass,
+ * half_mass, ke, epot, seed, half_dt.  Every per-graph value is double whatever `dtype` is, in the order written here; exp, log, sqrt are
+ * the double library functions.
+ *
+ * State: state [n_graphs, XEQ_NVT_ROW] doubles; a row holds the PENDING factor (XEQ_NVT_SCALE; the host starts it at 1), the thermostat's
+ * energy term (XEQ_NVT_BATH; 0), and the chain's positions xi [8] and velocities vxi [8] (XEQ_NVT_XI, XEQ_NVT_VXI; 0).
+ *
+ * xeq_nvt_back: xeq_md_back, except that the lane that holds graph g's kinetic-energy sum K (the double, before it is rounded) runs, with
+ * `advance`, one thermostat step for a whole `dt` and stores state[g][SCALE] = s and ke[g] = (dtype)((s s) K), which the recorder's row
+ * takes too.  vel holds the velocities BEFORE the factor: it is pending until the next front.  With advance = 0, or Nf = 3 n_free[g] = 0,
+ * or K not positive: s = 1 and the rest of the row is untouched; a step whose s is not finite and positive leaves s = 1 and the row
+ * untouched too, and sets book[2] when s was not finite.  With nfkT = Nf kT, tau2 = tau tau, Q1 = nfkT tau2, Q = kT tau2 (Q_1 = Q1,
+ * Q_k = Q beyond), M = chain_length:
+ *
+ *   XEQ_NVT_NOSE_HOOVER: s = 1; twice, with delta = dt / 2, hd = 0.5 delta, qd = 0.25 delta:
+ *     for k = M .. 1:  G_1 = (2 K - nfkT) / Q1, G_k = (Q_{k-1} (vxi_{k-1} vxi_{k-1}) - kT) / Q;
+ *                      k = M: vxi_M = vxi_M + hd G_M;  k < M: e = exp(-(qd vxi_{k+1})), vxi_k = vxi_k e, vxi_k = vxi_k + hd G_k,
+ *                      vxi_k = vxi_k e;
+ *     sigma = exp(-(delta vxi_1)), K = (sigma sigma) K, s = s sigma, xi_k = xi_k + delta vxi_k for every k;
+ *     for k = 1 .. M: the same velocity update, every G from the values of that moment.
+ *     bath = (sum_k 0.5 (Q_k (vxi_k vxi_k)), k rising, from 0) + nfkT xi_1 + kT (sum_{k >= 2} xi_k, k rising, from 0).
+ *
+ *   XEQ_NVT_BUSSI: c = exp(-(dt / tau)), q = ((1 - c) (0.5 nfkT)) / (Nf K), s2 = (c + q (R R + S)) + (2 R) sqrt(c q), s = sqrt(s2),
+ *     bath = bath - (s2 - 1) K.  R is a standard normal, S a chi-square variate with Nf - 1 degrees of freedom, from the generator of
+ *     xeq_md_normals under purpose XEQ_NVT_PURPOSE = 2 (xeq_md_normals itself serves purposes 0 and 1 alone): block j of the step is the
+ *     block of (seed, 2, graph_rng_id[g] | j, book[0] before the increment); graph_rng_id [n_graphs] has a zero low word.  Of a block,
+ *     z0 and z1 are the transform above evaluated in double and u = (word_2 + 1) 2^-32.  R = z0 of block 0.  Nf - 1 even: a = (Nf - 1) / 2,
+ *     S = 2 Gamma(a); odd: a = (Nf - 2) / 2, S = 2 Gamma(a) + z1 z1 with z1 of block 0 (Nf is a multiple of 3: a >= 1).  Gamma(a) by
+ *     Marsaglia and Tsang (ACM TOMS 26, 363 (2000)): d = a - 1 / 3, c' = 1 / sqrt(9 d); attempt j = 1, 2, ... takes x = z0 and u of block
+ *     j, t = 1 + c' x, v = (t t) t, and is accepted when v > 0 and log(u) < ((0.5 (x x) + d) - d v) + d log(v); the result is d v.
+ *     After XEQ_NVT_GAMMA_TRIES = 16 refused attempts the result is d |v| of the last one (probability below 1e-20).
+ *
+ * xeq_nvt_front, dt > 0: v = state[batch[i]][SCALE] v for every atom (double, where xeq_md_front applies the Berendsen lambda), then
+ * xeq_md_front's nve step.  dt = 0: the wrap alone; the factor stays pending.  The front never writes the row. */
+#define XEQ_NVT_ROW 18
+#define XEQ_NVT_MAX_CHAIN 8
+#define XEQ_NVT_GAMMA_TRIES 16
+#define XEQ_NVT_PURPOSE 2
+enum { XEQ_NVT_SCALE = 0, XEQ_NVT_BATH = 1, XEQ_NVT_XI = 2, XEQ_NVT_VXI = 10 };
+enum { XEQ_NVT_NOSE_HOOVER = 0, XEQ_NVT_BUSSI = 1 };
+/* Its record's number stands apart from the run 0 .. 8 above, which bindings walk as a dense table. */
+enum { XEQ_REC_NVT = 16 };
+struct xeq_nvt_params {
+  int64_t kind;                /* XEQ_NVT_NOSE_HOOVER / XEQ_NVT_BUSSI */
+  double* state;               /* [n_graphs, XEQ_NVT_ROW] */
+  const int64_t* n_free;       /* [n_graphs]: the graph's free atoms; Nf = 3 n_free */
+  const int64_t* graph_rng_id; /* [n_graphs] (bussi): the graphs' generator ids, low word zero */
+  int64_t chain_length;        /* (nose-hoover) 1 .. XEQ_NVT_MAX_CHAIN */
+  double kT;                   /* k_B T in the caller's energy unit, > 0 */
+  double tau;                  /* the coupling time, > 0, in the unit of dt */
+  double dt;                   /* the step the thermostat acts for */
+};
+typedef struct xeq_nvt_params xeq_nvt_params;
+int xeq_nvt_front(const xeq_res_system* sys, const xeq_md_params* md, const xeq_nvt_params* nvt, double dt, void* stream);
+int xeq_nvt_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
+                 const xeq_nvt_params* nvt, const xeq_res_recorder* rec, int advance, void* stream);
 
 /* Batched geometry optimisation (FIRE; xequinet_amd/optimize.py).  Every graph is its own FIRE system.  Per-atom
  * and per-graph arithmetic runs in double whatever `dtype` is and is rounded once where it is stored.

@@ -2,8 +2,9 @@
 // halves -- xeq_md_front in front of the step's graph, xeq_md_back behind it -- and the counter-based generator they share with
 // xeq_md_normals; behind them the two halves of the batched FIRE minimiser (xequinet_amd/optimize.py), which share
 // the wrap, the chunk sums and the join; the Berendsen barostat's two halves (xeq_npt_front / xeq_npt_back), which
-// are the MD halves with a box that lives on the device, and the kernel that forms the periodic search's cell tables from that box
-// (xeq_pbc_tables_device).  Plain vector code, f32 and f64 state.  The box, the wrap, the recorder's rules and the entries' shared argument
+// are the MD halves with a box that lives on the device, the canonical thermostats' two halves (xeq_nvt_front / xeq_nvt_back, DESIGN.md
+// section 17), which are the MD halves with a per-graph factor and the thermostat's step in the join, and the kernel that forms the periodic
+// search's cell tables from that box (xeq_pbc_tables_device).  Plain vector code, f32 and f64 state.  The box, the wrap, the recorder's rules and the entries' shared argument
 // checks are in xeq_resident.h, which xeq_lbfgs.hip includes too.
 //
 // Arithmetic.  Every per-atom update is evaluated in double whatever the state's type and rounded ONCE when it is stored: the state of an
@@ -105,10 +106,30 @@ struct MdFrontArgs {
   ResBox box;
 };
 
+// What a canonical thermostat adds to the front half: nothing (xeq_md_front, xeq_npt_front) ...
+struct MdNoFactor {
+  template <typename T>
+  __device__ __forceinline__ void apply(const MdFrontArgs<T>&, int64_t, double*) const {}
+};
+
+// ... or the graph's pending factor (xeq_nvt_front; include/xeq.h: XEQ_NVT_*), which nobody writes in this launch.
+struct NvtFactor {
+  const double* state;
+  bool on;   // dt > 0
+  template <typename T>
+  __device__ __forceinline__ void apply(const MdFrontArgs<T>& a, int64_t i, double* v) const {
+    if (!on) return;
+    int64_t g = a.batch[i];
+    g = g < 0 ? 0 : (g >= a.n_graphs ? a.n_graphs - 1 : g);
+    const double s = state[g * XEQ_NVT_ROW + XEQ_NVT_SCALE];
+    for (int k = 0; k < 3; ++k) v[k] = s * v[k];
+  }
+};
+
 // One atom's front half against `box`.  SCALE (the barostat, k_npt_front): x <- mu x for EVERY atom, fixed ones included, between the
-// thermostat's scaling and the half kick.
-template <typename T, bool SCALE>
-__device__ __forceinline__ void md_front_atom(const MdFrontArgs<T>& a, int64_t i, const ResBox& box, double mu) {
+// thermostat's scaling and the half kick.  `th`: MdNoFactor or NvtFactor.
+template <typename T, bool SCALE, typename Factor>
+__device__ __forceinline__ void md_front_atom(const MdFrontArgs<T>& a, int64_t i, const ResBox& box, double mu, const Factor& th) {
   const double im = (double)a.inv_mass[i];
   double v[3], x[3], f[3];
   for (int k = 0; k < 3; ++k) {
@@ -127,6 +148,7 @@ __device__ __forceinline__ void md_front_atom(const MdFrontArgs<T>& a, int64_t i
     }
     for (int k = 0; k < 3; ++k) v[k] = lam * v[k];
   }
+  th.apply(a, i, v);
   if (SCALE) {
     for (int k = 0; k < 3; ++k) x[k] = mu * x[k];
   }
@@ -167,7 +189,14 @@ template <typename T>
 __global__ void __launch_bounds__(256) k_md_front(MdFrontArgs<T> a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
-  md_front_atom<T, false>(a, i, a.box, 1.0);
+  md_front_atom<T, false>(a, i, a.box, 1.0, MdNoFactor{});
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_nvt_front(MdFrontArgs<T> a, NvtFactor th) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  md_front_atom<T, false>(a, i, a.box, 1.0, th);
 }
 
 // The barostat's front (xeq_npt_front): the box is the f64 record on the device (include/xeq.h: XEQ_NPT_*).  With dt > 0 every thread
@@ -187,7 +216,7 @@ __global__ void __launch_bounds__(256) k_npt_front(MdFrontArgs<T> a, double* rec
   }
   box.periodic[0] = box.periodic[1] = box.periodic[2] = box.any = 1;
   const double mu = moves ? rec[XEQ_NPT_MU] : 1.0;
-  md_front_atom<T, true>(a, i, box, mu);
+  md_front_atom<T, true>(a, i, box, mu, MdNoFactor{});
   if (i == 0 && moves) {
     for (int k = 0; k < 9; ++k) {
       rec[XEQ_NPT_CELL + k] = box.cell[k];
@@ -295,6 +324,144 @@ __device__ __forceinline__ void md_join_store(const MdBackArgs<T>& a, int64_t g,
   }
 }
 
+// What a canonical thermostat adds to the join: nothing, the graph's kinetic energy is its sum (xeq_md_back, xeq_npt_back) ...
+struct MdNoThermostat {
+  template <typename T>
+  __device__ __forceinline__ double kinetic(const MdBackArgs<T>&, int64_t, int64_t, double k, int*) const {
+    return k;
+  }
+};
+
+// ... or one thermostat step of the graph (xeq_nvt_back), run by the lane that holds the graph's sum K behind step number `step`: the
+// statement of include/xeq.h (XEQ_NVT_*), operation by operation; tests/nvt_oracle.py restates it in numpy.  O(1) whatever the graph's size.
+struct NvtThermostat {
+  int kind, chain;
+  double* state;
+  const int64_t* n_free;
+  const int64_t* graph_rng_id;
+  uint64_t seed;
+  double kT, tau, dt;
+
+  // One pass of the chain's velocity updates: k = M .. 1 (`down`) or 1 .. M.  Fully unrolled: vxi stays in registers.
+  __device__ __forceinline__ void chain_velocities(double* vxi, double k_now, double nfkT, double q1, double q, double hd, double qd, bool down) const {
+#pragma unroll
+    for (int j = 0; j < XEQ_NVT_MAX_CHAIN; ++j) {
+      const int k = down ? XEQ_NVT_MAX_CHAIN - 1 - j : j;   // (0-based)
+      if (k >= chain) continue;
+      double gk;
+      if (k == 0) {
+        gk = (2.0 * k_now - nfkT) / q1;
+      } else {
+        const double qp = k == 1 ? q1 : q;
+        gk = (qp * (vxi[k - 1] * vxi[k - 1]) - kT) / q;
+      }
+      if (k == chain - 1) {
+        vxi[k] = vxi[k] + hd * gk;
+      } else {
+        const double e = exp(-(qd * vxi[k + 1 < XEQ_NVT_MAX_CHAIN ? k + 1 : k]));
+        vxi[k] = vxi[k] * e;
+        vxi[k] = vxi[k] + hd * gk;
+        vxi[k] = vxi[k] * e;
+      }
+    }
+  }
+
+  __device__ __forceinline__ double nose_hoover(double* row, double k_now, double nf) const {
+    double xi[XEQ_NVT_MAX_CHAIN], vxi[XEQ_NVT_MAX_CHAIN];
+#pragma unroll
+    for (int k = 0; k < XEQ_NVT_MAX_CHAIN; ++k) {
+      xi[k] = row[XEQ_NVT_XI + k];
+      vxi[k] = row[XEQ_NVT_VXI + k];
+    }
+    const double nfkT = nf * kT, tau2 = tau * tau;
+    const double q1 = nfkT * tau2, q = kT * tau2;
+    const double delta = dt / 2.0, hd = 0.5 * delta, qd = 0.25 * delta;
+    double s = 1.0;
+    for (int half = 0; half < 2; ++half) {
+      chain_velocities(vxi, k_now, nfkT, q1, q, hd, qd, true);
+      const double sigma = exp(-(delta * vxi[0]));
+      k_now = (sigma * sigma) * k_now;
+      s = s * sigma;
+#pragma unroll
+      for (int k = 0; k < XEQ_NVT_MAX_CHAIN; ++k) {
+        if (k < chain) xi[k] = xi[k] + delta * vxi[k];
+      }
+      chain_velocities(vxi, k_now, nfkT, q1, q, hd, qd, false);
+    }
+    if (!(isfinite(s) && s > 0.0)) return s;
+    double b = 0.0, t = 0.0;
+#pragma unroll
+    for (int k = 0; k < XEQ_NVT_MAX_CHAIN; ++k) {
+      if (k < chain) b = b + 0.5 * ((k == 0 ? q1 : q) * (vxi[k] * vxi[k]));
+    }
+    b = b + nfkT * xi[0];
+#pragma unroll
+    for (int k = 1; k < XEQ_NVT_MAX_CHAIN; ++k) {
+      if (k < chain) t = t + xi[k];
+    }
+    b = b + kT * t;
+    row[XEQ_NVT_BATH] = b;
+#pragma unroll
+    for (int k = 0; k < XEQ_NVT_MAX_CHAIN; ++k) {
+      if (k < chain) {
+        row[XEQ_NVT_XI + k] = xi[k];
+        row[XEQ_NVT_VXI + k] = vxi[k];
+      }
+    }
+    return s;
+  }
+
+  // z0, z1 in double and u = (word_2 + 1) 2^-32 of block j of (graph, step).
+  __device__ __forceinline__ void draw(int64_t id, int j, int64_t step, double z[3], double* u) const {
+    uint32_t w[4];
+    md_block(seed, XEQ_NVT_PURPOSE, id | (int64_t)j, (uint64_t)step, w);
+    md_normals3<double>(w, z);
+    *u = ((double)w[2] + 1.0) * 2.3283064365386962890625e-10;
+  }
+
+  __device__ __forceinline__ double bussi(double* row, int64_t g, int64_t step, double k_now, int64_t nf_int) const {
+    const double nf = (double)nf_int;
+    const int64_t id = graph_rng_id[g];
+    double z[3], u;
+    draw(id, 0, step, z, &u);
+    const double r = z[0];
+    const bool even = ((nf_int - 1) & 1) == 0;
+    const double a = (double)((even ? nf_int - 1 : nf_int - 2) / 2);
+    const double d = a - 1.0 / 3.0, cp = 1.0 / sqrt(9.0 * d);
+    double gam = 0.0;
+    for (int j = 1; j <= XEQ_NVT_GAMMA_TRIES; ++j) {
+      double zj[3];
+      draw(id, j, step, zj, &u);
+      const double x = zj[0], t = 1.0 + cp * x, v = (t * t) * t;
+      gam = d * fabs(v);
+      if (v > 0.0 && log(u) < ((0.5 * (x * x) + d) - d * v) + d * log(v)) break;
+    }
+    const double sdraw = even ? 2.0 * gam : 2.0 * gam + z[1] * z[1];
+    const double c = exp(-(dt / tau));
+    const double q = ((1.0 - c) * (0.5 * (nf * kT))) / (nf * k_now);
+    const double s2 = (c + q * (r * r + sdraw)) + (2.0 * r) * sqrt(c * q);
+    const double s = sqrt(s2);
+    if (isfinite(s) && s > 0.0) row[XEQ_NVT_BATH] = row[XEQ_NVT_BATH] - (s2 - 1.0) * k_now;
+    return s;
+  }
+
+  template <typename T>
+  __device__ __forceinline__ double kinetic(const MdBackArgs<T>& a, int64_t g, int64_t step, double k_sum, int* bad) const {
+    double* row = state + g * XEQ_NVT_ROW;
+    double s = 1.0;
+    const int64_t nf = 3 * n_free[g];
+    if (a.advance && nf > 0 && k_sum > 0.0) {
+      s = kind == XEQ_NVT_BUSSI ? bussi(row, g, step, k_sum, nf) : nose_hoover(row, k_sum, (double)nf);
+      if (!(isfinite(s) && s > 0.0)) {
+        *bad |= !isfinite(s);
+        s = 1.0;
+      }
+    }
+    row[XEQ_NVT_SCALE] = s;
+    return (s * s) * k_sum;
+  }
+};
+
 // What the NVT ensembles add to the back half: nothing; the recorder's cell is the launch's own.
 struct MdNoBox {
   template <typename T>
@@ -368,9 +535,9 @@ struct NptBox {
   }
 };
 
-// The MD join; then ONE lane does the bookkeeping with plain stores.
-template <typename T, typename Box>
-__device__ __forceinline__ void md_join(const MdBackArgs<T>& a, const Box& bx) {
+// The MD join; then ONE lane does the bookkeeping with plain stores.  `th`: MdNoThermostat or NvtThermostat.
+template <typename T, typename Box, typename Thermostat>
+__device__ __forceinline__ void md_join(const MdBackArgs<T>& a, const Box& bx, const Thermostat& th) {
   const int64_t step_after = a.book[0] + (a.advance ? 1 : 0);
   const int64_t row = md_record_row(a, step_after);
   int bad = 0;
@@ -378,7 +545,7 @@ __device__ __forceinline__ void md_join(const MdBackArgs<T>& a, const Box& bx) {
       a.n_graphs, a.n_chunks, a.graph_chunk_ptr, [&]() { return MdKeSum{a.partial, a.partial_bad, 0.0, 0}; },
       [&](int64_t g, const MdKeSum& k) {
         bad |= k.bad;
-        md_join_store(a, g, row, k.s, &bad);
+        md_join_store(a, g, row, th.kinetic(a, g, step_after - (a.advance ? 1 : 0), k.s, &bad), &bad);
       });
   const int any_bad = __syncthreads_or(bad);
   if (threadIdx.x == 0) {
@@ -393,18 +560,23 @@ __device__ __forceinline__ void md_join(const MdBackArgs<T>& a, const Box& bx) {
 
 template <typename T>
 __global__ void __launch_bounds__(MD_JOIN_THREADS) k_md_join(MdBackArgs<T> a) {
-  md_join(a, MdNoBox{});
+  md_join(a, MdNoBox{}, MdNoThermostat{});
+}
+
+template <typename T>
+__global__ void __launch_bounds__(MD_JOIN_THREADS) k_nvt_join(MdBackArgs<T> a, NvtThermostat th) {
+  md_join(a, MdNoBox{}, th);
 }
 
 template <typename T>
 __global__ void __launch_bounds__(MD_JOIN_THREADS) k_npt_join(MdBackArgs<T> a, NptBox<T> bx) {
-  md_join(a, bx);
+  md_join(a, bx, MdNoThermostat{});
 }
 
 // One workgroup per chunk: second half kick, the step's forces into the driver's own copy, the chunk's kinetic energy and non-finite flag.
 // (Behind md_join in this file because a lone chunk's workgroup runs it itself.)
-template <typename T, typename Box>
-__device__ __forceinline__ void md_back_chunk(const MdBackArgs<T>& a, const Box& bx) {
+template <typename T, typename Box, typename Thermostat>
+__device__ __forceinline__ void md_back_chunk(const MdBackArgs<T>& a, const Box& bx, const Thermostat& th) {
   __shared__ double wsum[MD_CHUNK / 64];
   const int c = blockIdx.x;
   const int tid = threadIdx.x;
@@ -444,18 +616,23 @@ __device__ __forceinline__ void md_back_chunk(const MdBackArgs<T>& a, const Box&
   if (a.n_chunks == 1) {   // the only chunk (a small molecule, a small box): its workgroup joins and keeps the books itself, one launch less
     __threadfence_block();
     __syncthreads();
-    md_join(a, bx);
+    md_join(a, bx, th);
   }
 }
 
 template <typename T>
 __global__ void __launch_bounds__(MD_CHUNK) k_md_back(MdBackArgs<T> a) {
-  md_back_chunk(a, MdNoBox{});
+  md_back_chunk(a, MdNoBox{}, MdNoThermostat{});
+}
+
+template <typename T>
+__global__ void __launch_bounds__(MD_CHUNK) k_nvt_back(MdBackArgs<T> a, NvtThermostat th) {
+  md_back_chunk(a, MdNoBox{}, th);
 }
 
 template <typename T>
 __global__ void __launch_bounds__(MD_CHUNK) k_npt_back(MdBackArgs<T> a, NptBox<T> bx) {
-  md_back_chunk(a, bx);
+  md_back_chunk(a, bx, MdNoThermostat{});
 }
 
 // ------------------------------------------------------------------------------------------------------------- cell tables
@@ -795,6 +972,7 @@ int64_t xeq_record_bytes(int which) {
     case XEQ_REC_FIRE: return sizeof(xeq_fire_params);
     case XEQ_REC_NEIGHBORS: return sizeof(xeq_neighbor_search);
     case XEQ_REC_LBFGS: return sizeof(xeq_lbfgs_params);
+    case XEQ_REC_NVT: return sizeof(xeq_nvt_params);
   }
   return -1;
 }
@@ -935,6 +1113,71 @@ int xeq_npt_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_
     if (n_chunks != 1) hipLaunchKernelGGL(k_npt_join<T>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, bx);
   });
   XEQ_CHECK_LAUNCH("xeq_npt_back");
+  return XEQ_OK;
+}
+
+// What both thermostat entries ask of their record.
+static int nvt_params(const char* who, const xeq_res_system* sys, const xeq_nvt_params* nvt) {
+  XEQ_CHECK_ARG(nvt->kind == XEQ_NVT_NOSE_HOOVER || nvt->kind == XEQ_NVT_BUSSI, "%s: thermostat %lld (0 nose-hoover chain, 1 bussi)", who,
+                (long long)nvt->kind);
+  XEQ_CHECK_ARG(nvt->kind != XEQ_NVT_NOSE_HOOVER || (nvt->chain_length >= 1 && nvt->chain_length <= XEQ_NVT_MAX_CHAIN),
+                "%s: chain length %lld (1 .. %d)", who, (long long)nvt->chain_length, XEQ_NVT_MAX_CHAIN);
+  XEQ_CHECK_ARG(res_finite(nvt->kT) && nvt->kT > 0.0 && res_finite(nvt->tau) && nvt->tau > 0.0 && res_finite(nvt->dt) && nvt->dt >= 0.0,
+                "%s: thermostat (k_B T %g > 0, tau %g > 0, dt %g >= 0)", who, nvt->kT, nvt->tau, nvt->dt);
+  XEQ_CHECK_ARG(sys->n_graphs == 0 || (nvt->state && nvt->n_free && (nvt->kind != XEQ_NVT_BUSSI || nvt->graph_rng_id)),
+                "%s: null thermostat state, free-atom counts or graph ids", who);
+  return XEQ_OK;
+}
+
+int xeq_nvt_front(const xeq_res_system* sys, const xeq_md_params* md, const xeq_nvt_params* nvt, double dt, void* stream) {
+  const char* who = "xeq_nvt_front";
+  RES_TRY(res_dtype(who, sys, md && nvt));
+  const int64_t n = sys->n, n_graphs = sys->n_graphs;
+  RES_TRY(res_atoms_graphs(who, sys));
+  XEQ_CHECK_ARG(res_finite(dt) && dt >= 0.0, "xeq_nvt_front: time step %g", dt);
+  RES_TRY(nvt_params(who, sys, nvt));
+  ResBox box;
+  RES_TRY(res_box(who, sys, &box));
+  XEQ_CHECK_ARG(n == 0 || (sys->pos && sys->vel && sys->frc && md->inv_mass), "xeq_nvt_front: null state buffer");
+  XEQ_CHECK_ARG(n == 0 || !box.any || sys->image, "xeq_nvt_front: a periodic system needs the image counts");
+  XEQ_CHECK_ARG(n == 0 || (sys->batch && n_graphs >= 1), "xeq_nvt_front: the factor needs batch and a graph");
+  if (n == 0) return XEQ_OK;
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
+    MdFrontArgs<T> a{n, n_graphs, XEQ_MD_NVE, (T*)sys->pos, (T*)sys->vel, (const T*)sys->frc, (const T*)md->inv_mass, sys->batch, nullptr, nullptr,
+                     nullptr, nullptr, 0, dt, 1.0, 0.0, 0.0, 0.0, sys->image, box};
+    hipLaunchKernelGGL(k_nvt_front<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, NvtFactor{nvt->state, dt > 0.0});
+  });
+  XEQ_CHECK_LAUNCH("xeq_nvt_front");
+  return XEQ_OK;
+}
+
+int xeq_nvt_back(const xeq_res_system* sys, const xeq_res_step* step, const xeq_res_chunks* chunks, const xeq_md_params* md,
+                 const xeq_nvt_params* nvt, const xeq_res_recorder* rec, int advance, void* stream) {
+  const char* who = "xeq_nvt_back";
+  RES_TRY(res_dtype(who, sys, step && chunks && md && nvt));
+  if (!rec) rec = &RES_NO_RECORDER;
+  const int64_t n = sys->n, n_graphs = sys->n_graphs, n_chunks = sys->n_chunks;
+  RES_TRY(res_back_sizes(who, sys, (int64_t)1 << 31));
+  XEQ_CHECK_ARG(res_finite(md->half_dt) && md->half_dt >= 0.0, "xeq_nvt_back: half time step %g", md->half_dt);
+  RES_TRY(nvt_params(who, sys, nvt));
+  RES_TRY(res_recorder(who, rec));
+  ResBox box;
+  RES_TRY(res_box(who, sys, &box));
+  XEQ_CHECK_ARG(sys->book && step->n_edges_step, "xeq_nvt_back: null step counter or edge count");
+  XEQ_CHECK_ARG(n == 0 || (res_back_buffers(sys, step, chunks, true) && md->inv_mass && md->half_mass), "xeq_nvt_back: null per-atom or per-chunk buffer");
+  XEQ_CHECK_ARG(n_graphs == 0 || (step->energy_step && chunks->graph_chunk_ptr && md->ke && md->epot), "xeq_nvt_back: null per-graph buffer");
+  const bool on = advance && rec->every > 0 && rec->rows > 0;
+  if (on) RES_TRY(res_trajectory(who, sys, rec, box));
+  const NvtThermostat th{(int)nvt->kind, (int)nvt->chain_length, nvt->state, nvt->n_free, nvt->graph_rng_id, md->seed, nvt->kT, nvt->tau, nvt->dt};
+  XEQ_DISPATCH_FLOAT(sys->dtype, {
+    const MdBackArgs<T> a = md_back_args<T>(sys, step, chunks, md, rec, n_graphs, advance, box, on);
+    if (n_chunks > 0) {
+      hipLaunchKernelGGL(k_nvt_back<T>, dim3((unsigned)n_chunks), dim3(MD_CHUNK), 0, (hipStream_t)stream, a, th);
+      XEQ_CHECK_LAUNCH("xeq_nvt_back");
+    }
+    if (n_chunks != 1) hipLaunchKernelGGL(k_nvt_join<T>, dim3(1), dim3(n_graphs > 64 ? MD_JOIN_THREADS : 256), 0, (hipStream_t)stream, a, th);
+  });
+  XEQ_CHECK_LAUNCH("xeq_nvt_back");
   return XEQ_OK;
 }
 

@@ -22,6 +22,9 @@ MD_CHUNK = 256          # XEQ_MD_CHUNK of include/xeq.h: atoms per kinetic-energ
 MD_NVE, MD_LANGEVIN, MD_BERENDSEN, MD_PURPOSE_LANGEVIN, MD_PURPOSE_MAXWELL = 0, 1, 2, 0, 1      # XEQ_MD_* of include/xeq.h (md.py)
 NPT_BOX, NPT_CELL, NPT_INV, NPT_CELL_NEXT, NPT_INV_NEXT, NPT_MU, NPT_P, NPT_V = 40, 0, 9, 18, 27, 36, 37, 38      # XEQ_NPT_* of include/xeq.h (md.py)
 FIRE_FRESH, FIRE_ACTIVE, FIRE_CONVERGED = 0, 1, 2      # XEQ_FIRE_* of include/xeq.h
+# XEQ_NVT_* of include/xeq.h (md.py's canonical thermostats; tests/test_nvt_host.py holds these two lines against the header)
+NVT_ROW, NVT_MAX_CHAIN, NVT_GAMMA_TRIES, NVT_PURPOSE, NVT_SCALE, NVT_BATH, NVT_XI, NVT_VXI = 18, 8, 16, 2, 0, 1, 2, 10
+NVT_NOSE_HOOVER, NVT_BUSSI, REC_NVT = 0, 1, 16          # (REC_NVT: XEQ_REC_NVT, the record's number for xeq_record_bytes)
 LBFGS_FRESH, LBFGS_ACTIVE, LBFGS_CONVERGED, LBFGS_MAX_MEMORY = 0, 1, 2, 32      # XEQ_LBFGS_* of include/xeq.h (optimize.LBFGS)
 VIB_MAX_DIM, VIB_MAX_SWEEPS = 96, 30     # XEQ_VIB_MAX_DIM, XEQ_VIB_MAX_SWEEPS of include/xeq.h (vibrations.py)
 VIB_LARGE_MAX_DIM = 768              # XEQ_VIB_LARGE_MAX_DIM: the cap of xeq_vib_eigh_large
@@ -63,6 +66,9 @@ NeighborSearch = _record("xeq_neighbor_search", (c_int64, "dtype kind n_graphs n
 NEIGHBORS_OPEN_SWEEP, NEIGHBORS_OPEN_BINS, NEIGHBORS_PBC_ALL, NEIGHBORS_PBC_PRUNED, NEIGHBORS_PBC_BINS = range(5)
 LbfgsParams = _record("xeq_lbfgs_params", (_P, "fixed hist_s hist_y pending_s gram delta count head status dropped converged_at epot fmax ticket"),
                       (c_int64, "memory max_graph_chunks"), (c_double, "fmax_tol alpha maxstep damping"))
+# The thermostats' record: its number stands apart from the dense run of RECORDS (include/xeq.h: XEQ_REC_NVT)
+NvtParams = _record("xeq_nvt_params", (c_int64, "kind"), (_P, "state n_free graph_rng_id"), (c_int64, "chain_length"), (c_double, "kT tau dt"))
+RECORDS_APART = {REC_NVT: NvtParams}
 RECORDS = [ResSystem, ResStep, ResChunks, ResRecorder, MdParams, NptParams, FireParams, NeighborSearch, LbfgsParams]
 _R = ctypes.POINTER
 
@@ -274,6 +280,8 @@ _PROTOS = {
     "xeq_pbc_tables_device": [c_int, _P, _I3, _I3, c_double, _P, c_int64, _P, _P],
     "xeq_npt_front": [_R(ResSystem), _R(MdParams), _R(NptParams), c_double, _P],
     "xeq_npt_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(MdParams), _R(NptParams), _R(ResRecorder), c_int, _P],
+    "xeq_nvt_front": [_R(ResSystem), _R(MdParams), _R(NvtParams), c_double, _P],
+    "xeq_nvt_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(MdParams), _R(NvtParams), _R(ResRecorder), c_int, _P],
     "xeq_fire_front": [_R(ResSystem), _R(FireParams), _P],
     "xeq_fire_back": [_R(ResSystem), _R(ResStep), _R(ResChunks), _R(FireParams), _R(ResRecorder), _P],
     "xeq_lbfgs_front": [_R(ResSystem), _R(ResChunks), _R(LbfgsParams), _P],
@@ -310,7 +318,7 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = c_int64 if name in _RET_I64 else c_int
-    for which, record in enumerate(RECORDS):      # a binding whose layout is not the library's would hand kernels the wrong buffers
+    for which, record in [*enumerate(RECORDS), *RECORDS_APART.items()]:      # a binding whose layout is not the library's would hand kernels the wrong buffers
         if ctypes.sizeof(record) != lib.xeq_record_bytes(which):
             raise ImportError(f"{LIB_PATH}: {record.__name__} is {lib.xeq_record_bytes(which)} bytes in the library, {ctypes.sizeof(record)} in "
                               "xequinet_amd/lib.py (a library of another version?)")

@@ -19,6 +19,11 @@ lives on the device: the step is built with ``compute_virial=True, device_cell=T
 tables from the static cell), ``xeq_npt_back`` forms pressure, scale factor and the pending cell from the step's virial, ``xeq_npt_front``
 applies them; a box that shrank until the cutoff reaches a further image voids the window as an outgrown edge capacity does (resident.py).
 
+``ensemble="nose_hoover"`` and ``"bussi"`` are the canonical thermostats: a Nose-Hoover chain or a stochastic
+velocity rescaling per graph, run in the back's join by the lane that holds the graph's kinetic energy (``xeq_nvt_back``) as ONE factor
+per graph, which stays PENDING in the thermostat's row until the next front applies it (``xeq_nvt_front``): ``vel`` holds the velocities
+before the factor, and ``velocities``, ``kinetic_energy`` and ``temperature`` are those behind it.
+
 A batch of independent open-boundary molecules (``ptr``) runs on GraphedStep, one periodic box (``cell``) on GraphedStepPBC; the models
 those classes refuse are refused here by constructing them.  There is no CPU fallback.
 """
@@ -39,6 +44,9 @@ from .utils import units as _units
 ENSEMBLES = {"nve": lib.MD_NVE, "langevin": lib.MD_LANGEVIN, "berendsen": lib.MD_BERENDSEN,
              "npt_berendsen": lib.MD_BERENDSEN}               # (its thermostat; the barostat has entries of its own: xeq_npt_front / _back)
 NPT = "npt_berendsen"
+# The canonical thermostats, served by entries of their own (xeq_nvt_front / _back): name -> XEQ_NVT_* kind.  (ENSEMBLES stays the map
+# to the XEQ_MD_* codes of xeq_md_front.)
+THERMOSTATS = {"nose_hoover": lib.NVT_NOSE_HOOVER, "bussi": lib.NVT_BUSSI}
 PURPOSE_LANGEVIN, PURPOSE_MAXWELL = lib.MD_PURPOSE_LANGEVIN, lib.MD_PURPOSE_MAXWELL
 BOLTZMANN_J_PER_K = 1.380649e-23                             # exact (SI 2019)
 
@@ -79,7 +87,10 @@ class Dynamics(ResidentDriver):
     DESIGN.md section 12.  ``masses`` [N] in g / mol (0 or inf: a fixed atom); ``ensemble``: "nve" (velocity Verlet), "langevin" (BAOAB;
     ``temperature_K``, ``friction_per_fs``), "berendsen" (``temperature_K``, ``taut_fs``), "npt_berendsen" (one box periodic along all
     three axes; the Berendsen thermostat and ASE's NPTBerendsen barostat: ``temperature_K``, ``taut_fs``, ``pressure_GPa``, ``taup_fs``,
-    ``compressibility_per_GPa``).  The box of an NPT run lives on the device: ``cell``, ``volume``, ``pressure``
+    ``compressibility_per_GPa``), "nose_hoover" (a Nose-Hoover chain per graph: ``temperature_K``, ``taut_fs``,
+    ``chain_length`` 1 .. 8, default 3) and "bussi" (stochastic velocity rescaling per graph: ``temperature_K``, ``taut_fs``, ``seed``,
+    ``graph_rng_id`` int64 [G] with a zero low word, default ``g << 32``); the two keep ``thermostat_energy`` and
+    ``conserved_energy``.  The box of an NPT run lives on the device: ``cell``, ``volume``, ``pressure``
     and ``virial`` read it; ``min_images`` (three ints) captures the step's graph with more periodic images than the first cell needs."""
 
     def __init__(self, model, pos: torch.Tensor, atomic_numbers: torch.Tensor, masses: torch.Tensor, *, ptr: Optional[torch.Tensor] = None,
@@ -87,9 +98,9 @@ class Dynamics(ResidentDriver):
                  friction_per_fs: Optional[float] = None, taut_fs: Optional[float] = None, seed: int = 0, rng_id: Optional[torch.Tensor] = None,
                  edge_capacity: Optional[int] = None, energy_unit: Optional[str] = None, length_unit: Optional[str] = None,
                  pressure_GPa: Optional[float] = None, taup_fs: Optional[float] = None, compressibility_per_GPa: Optional[float] = None,
-                 min_images=None) -> None:
-        if ensemble not in ENSEMBLES:
-            raise ValueError(f"Dynamics: ensemble {ensemble!r} (one of {sorted(ENSEMBLES)})")
+                 min_images=None, chain_length: Optional[int] = None, graph_rng_id: Optional[torch.Tensor] = None) -> None:
+        if ensemble not in ENSEMBLES and ensemble not in THERMOSTATS:
+            raise ValueError(f"Dynamics: ensemble {ensemble!r} (one of {sorted([*ENSEMBLES, *THERMOSTATS])})")
         self.ensemble = ensemble
         self.dt = float(timestep_fs)
         if not (math.isfinite(self.dt) and self.dt > 0.0):
@@ -98,8 +109,19 @@ class Dynamics(ResidentDriver):
             raise ValueError(f"Dynamics: ensemble {ensemble!r} needs temperature_K >= 0")
         if ensemble == "langevin" and (friction_per_fs is None or not friction_per_fs >= 0.0):
             raise ValueError("Dynamics: ensemble 'langevin' needs friction_per_fs >= 0")
-        if ensemble in ("berendsen", NPT) and (taut_fs is None or not taut_fs > 0.0):
+        if ensemble in ("berendsen", NPT, *THERMOSTATS) and (taut_fs is None or not taut_fs > 0.0):
             raise ValueError(f"Dynamics: ensemble {ensemble!r} needs taut_fs > 0")
+        self._nvt = ensemble in THERMOSTATS
+        if self._nvt and not (temperature_K > 0.0 and math.isfinite(temperature_K) and math.isfinite(taut_fs)):
+            raise ValueError(f"Dynamics: ensemble {ensemble!r} needs a finite temperature_K > 0 and a finite taut_fs > 0")
+        if ensemble == "nose_hoover":
+            chain_length = 3 if chain_length is None else chain_length
+            if int(chain_length) != chain_length or not 1 <= chain_length <= lib.NVT_MAX_CHAIN:
+                raise ValueError(f"Dynamics: ensemble 'nose_hoover' needs 1 <= chain_length <= {lib.NVT_MAX_CHAIN} (got {chain_length})")
+        elif chain_length is not None:
+            raise ValueError(f"Dynamics: chain_length belongs to ensemble 'nose_hoover', not {ensemble!r}")
+        if graph_rng_id is not None and ensemble != "bussi":
+            raise ValueError(f"Dynamics: graph_rng_id belongs to ensemble 'bussi', not {ensemble!r}")
         self._npt = ensemble == NPT
         if self._npt:
             if ptr is not None or cell is None:
@@ -168,7 +190,7 @@ class Dynamics(ResidentDriver):
         self._no_edges = torch.zeros(1, dtype=torch.int32, device=dev)
 
         self._load_system(pos, atomic_numbers, cell, pbc)
-        self._md = lib.fill(lib.MdParams(), ensemble=ENSEMBLES[ensemble], inv_mass=self.inv_mass, half_mass=self.half_mass, ke=self.ke, epot=self.epot,
+        self._md = lib.fill(lib.MdParams(), ensemble=lib.MD_NVE if self._nvt else ENSEMBLES[ensemble], inv_mass=self.inv_mass, half_mass=self.half_mass, ke=self.ke, epot=self.epot,
                             tfac=self.tfac, rng_id=self.rng_id, seed=self.seed, c1=self._c1, noise2=self._noise2, dt_over_tau=self._dt_over_tau,
                             t0=self.temperature_K or 0.0, half_dt=0.5 * self.dt)
         self._own = (ctypes.byref(self._md),)          # the driver's own records, as both of its entries take them
@@ -187,10 +209,23 @@ class Dynamics(ResidentDriver):
             self._npt_rec = lib.fill(lib.NptParams(), box=self.box, step_cell=self.step.cell, virial=self.vir, reps_seen=self.reps_seen,
                                      kappa=self._kappa, p0=self._p0, p_unit=self._p_unit)
             self._own += (ctypes.byref(self._npt_rec),)
+        if self._nvt:
+            # the thermostats' rows of include/xeq.h (XEQ_NVT_*): factor 1, everything else 0
+            ids = (torch.arange(G, dtype=torch.int64, device=dev) << 32) if graph_rng_id is None else graph_rng_id.detach().to(torch.int64).contiguous().clone()
+            if ids.shape != (G,) or bool((ids & 0xFFFFFFFF).ne(0).any()):
+                raise ValueError("Dynamics: graph_rng_id [G] with a zero low word (the word numbers a step's blocks)")
+            self.graph_rng_id = ids
+            self.thermo = torch.zeros((G, lib.NVT_ROW), dtype=torch.float64, device=dev)
+            self.thermo[:, lib.NVT_SCALE] = 1.0
+            self._n_free_dev = on(n_free, torch.int64)
+            self._nvt_rec = lib.fill(lib.NvtParams(), kind=THERMOSTATS[ensemble], state=self.thermo, n_free=self._n_free_dev, graph_rng_id=self.graph_rng_id,
+                                     chain_length=int(chain_length or 0), kT=self.kB * self.temperature_K, tau=float(taut_fs), dt=self.dt)
+            self._own += (ctypes.byref(self._nvt_rec),)
         # the kinetic energies alone (_back_ke): the back on the forces and energies this object holds, which depend on the positions alone
         self._own_step = lib.fill(lib.ResStep(), frc_step=self.frc, energy_step=self.epot, n_edges_step=self._no_edges,
                                   virial_step=self.vir if self._npt else None)
-        self._front_name, self._back_name = ("xeq_npt_front", "xeq_npt_back") if self._npt else ("xeq_md_front", "xeq_md_back")
+        self._front_name, self._back_name = (("xeq_npt_front", "xeq_npt_back") if self._npt else ("xeq_nvt_front", "xeq_nvt_back") if self._nvt else
+                                             ("xeq_md_front", "xeq_md_back"))
         call(self._front_name, *self._front_args(0.0), lib.stream())      # dt = 0: the wrap alone: the search sweeps +- reps images around the box, not around a stray atom
 
     # ------------------------------------------------------------------------------------------------ launches
@@ -209,6 +244,8 @@ class Dynamics(ResidentDriver):
     # ------------------------------------------------------------------------------------------------ check / restore (resident.py)
     def _state(self):
         state = [self._pos, self.image, self.vel, self.frc, self.ke, self.epot, self.book]
+        if self._nvt:
+            return state + [self.thermo]
         return state + [self.step.cell, self.box, self.vir, self.reps_seen] if self._npt else state
 
     def _images_wanted(self):
@@ -256,6 +293,8 @@ class Dynamics(ResidentDriver):
 
     def _velocities_changed(self) -> None:
         self._ke_stale = True        # forces and potential energy depend on the positions alone: only the kinetic energy is redone
+        if self._nvt:
+            self.thermo[:, lib.NVT_SCALE] = 1.0          # set velocities are THE velocities: no factor is pending
 
     def set_velocities(self, v: torch.Tensor) -> None:
         require_hip(v)
@@ -273,7 +312,7 @@ class Dynamics(ResidentDriver):
     def zero_momentum(self) -> None:
         """Per graph: the centre-of-mass velocity of the free atoms is taken off them.  A set-up operation that SYNCHRONISES: the velocities
         go to the host and back, and the sums are formed there in f64 in a fixed order that depends on the graph alone."""
-        v = self.vel.double().cpu().numpy()
+        v = self.velocities.double().cpu().numpy()       # (a thermostat's pending factor applied)
         m = self._mass_host
         for a, b in zip(self.ptr_host[:-1], self.ptr_host[1:]):
             mt = m[a:b].sum()
@@ -289,6 +328,10 @@ class Dynamics(ResidentDriver):
 
     @property
     def velocities(self) -> torch.Tensor:
+        """The velocities of the instant ``kinetic_energy`` belongs to: with a canonical thermostat ``vel`` times the graph's pending
+        factor, rounded once."""
+        if self._nvt:
+            return (self.vel.double() * self.thermo[:, lib.NVT_SCALE][self.step.batch[: self.n_atoms].long()][:, None]).to(self.dtype)
         return self.vel.clone()
 
     @property
@@ -311,6 +354,22 @@ class Dynamics(ResidentDriver):
         """T_g = 2 KE_g / (3 n_free,g k_B); 0 for a graph without a free atom."""
         self._settle()
         return self.ke * self.tfac
+
+    # ------------------------------------------------------------------------------------------------ the canonical thermostats
+    @property
+    def thermostat_energy(self) -> torch.Tensor:
+        """[G] f64: the thermostat's energy term (include/xeq.h: XEQ_NVT_BATH) -- the chain's own energy, or minus the kinetic energy
+        the rescaling has put in so far."""
+        if not self._nvt:
+            raise AttributeError(f"Dynamics: ensemble {self.ensemble!r} keeps no thermostat energy (ensembles 'nose_hoover' and 'bussi' do)")
+        self._settle()
+        return self.thermo[:, lib.NVT_BATH].clone()
+
+    @property
+    def conserved_energy(self) -> torch.Tensor:
+        """[G] f64: potential + kinetic + thermostat energy, the quantity the thermostatted dynamics conserves."""
+        bath = self.thermostat_energy
+        return self.epot.double() + self.ke.double() + bath
 
     # ------------------------------------------------------------------------------------------------ the box of an NPT run
     def _box_entry(self, k: int) -> torch.Tensor:
